@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- faces/sec of the NLML_HPE batched-inference hot path on N MI355X GPUs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    A plain run sets up, settles and warms up, times the K steps, writes the last timed step's poses when --dump-outputs is given and
+    prints the result line; --full adds everything else listed below (value_cold, roofline.traffic, cpu_baseline, extra and, at N > 1,
+    value_no_collective).
     N > 1 works both ways: under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
     (RANK/LOCAL_RANK/WORLD_SIZE from the env), or as a plain `python bench.py --gpus N ...`, which starts the N ranks itself
     as child processes BEFORE anything touches the GPU and relays rank 0's JSON line.
@@ -15,15 +18,19 @@ f16 matrix cores with split accumulators, f32 accumulate -- the strict-fast mode
 the exact result than the reference's own f32 forward), f32 (f32 matrix cores with blocked sums: the strict parity mode) or f16x2
 (opt-in: single accumulators where registers are short, 1.10x the reference's error at +-45 deg poses).  With N > 1 every
 step also all-gathers the [B,3] poses of all ranks over RCCL (the only collective the path has),
-on the communication stream, overlapped with the next step's compute; a second timed region of K steps without
+on the communication stream, overlapped with the next step's compute; with --full a second timed region of K steps without
 the collective gives `value_no_collective` (--no-collective: time only that one).
 
 Prints ONE JSON line (rank 0): the contract fields plus
   roofline      the fused kernel against the dense MFMA peak of its operand type,
-                achieved = algorithmic FLOP per launch / average launch time from HIP events;
-  cpu_baseline  the oracle's torch-CPU restatement of the same arithmetic on this host's cores, plus
+                achieved = algorithmic FLOP per launch / average launch time from HIP events of the timed steps;
+                traffic (--full): HBM-side bytes per step from two rocprofv3 --pmc child runs;
+  cpu_baseline  (--full) the oracle's torch-CPU restatement of the same arithmetic on this host's cores, plus
                 parity_check: the measured kernel's poses against the f64 oracle on a sample of the batch;
-  extra         the other K2 modes and secondary workloads (features-in K2, F=136, K1, K3, video, TD Powell).
+  extra         (--full) the other K2 modes and secondary workloads (features-in K2, F=136, K1, K3, video, TD Powell).
+--dump-outputs DIR writes the poses of the last timed step, f32 [B,3] radians (yaw, pitch, roll), as DIR/pose.npy, and at N > 1
+with the collective the gathered f32 [N*B,3] block as DIR/pose_gathered.npy; an array over 32 MB is written as an evenly strided
+sample of its rows.  The inputs are seeded (encoder seed 0, landmarks seed 1 + rank), so equal arguments give equal inputs.
 """
 from __future__ import annotations
 
@@ -77,7 +84,28 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: value_cold, roofline.traffic, cpu_baseline, extra and, "
+                         "at N > 1, value_no_collective (the --no-* flags above switch parts of it off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's poses as DIR/pose.npy (and DIR/pose_gathered.npy at N > 1 with the collective)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_BYTES = 32 << 20      # per array: two arrays at most, 64 MB in all
+
+
+def dump_array(directory, name, a):
+    """DIR/<name>.npy; an array over DUMP_MAX_BYTES as the evenly strided sample of its rows that fits (fixed for fixed shapes)."""
+    a = np.ascontiguousarray(a)
+    if a.nbytes > DUMP_MAX_BYTES:
+        row_bytes = a.nbytes // a.shape[0]
+        a = a[::-(-a.shape[0] // (DUMP_MAX_BYTES // row_bytes))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def time_kernel(fn, iters, warm=3):
@@ -237,8 +265,8 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
-    traffic, traffic_source = None, "not measured (N > 1, --no-traffic or --pmc-child)"
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_traffic and not args.pmc_child:
+    traffic, traffic_source = None, "not measured (no --full, N > 1, --no-traffic or --pmc-child)"
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_traffic and not args.pmc_child:
         traffic, traffic_source = measure_traffic(args)     # child processes, before anything here touches the GPU
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -321,7 +349,9 @@ def main():
             dist.barrier()
 
     def run_steps(n, events=None, collective=True):
+        """-> (the last step's poses, the gathered block of the last step or None)"""
         g = gatherer if collective else None
+        out = None
         for i in range(n):
             if events is not None:
                 events[i][0].record()
@@ -330,8 +360,7 @@ def main():
                 events[i][1].record()
             if g is not None:
                 g.submit(out)
-        if g is not None:
-            g.drain()
+        return out, (g.drain() if g is not None else None)
 
     def timed_region(collective):
         """W untimed warm-up steps, then EXACTLY K timed steps bracketed by barrier + synchronize; MAX over ranks."""
@@ -341,7 +370,7 @@ def main():
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_steps(args.steps, evs, collective=collective)
+        last = run_steps(args.steps, evs, collective=collective)
         torch.cuda.synchronize()
         barrier()
         elapsed = time.perf_counter() - t0
@@ -349,20 +378,30 @@ def main():
         t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=dev)
         if dist is not None:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return float(t[0].item()), float(t[1].item())
+        return float(t[0].item()), float(t[1].item()), last
 
     with_coll = world > 1 and not args.no_collective
-    # 1. the cold figure: W warm-ups + K steps straight after start-up, before any settling (what `--settle-ms 0` reads)
-    cold_elapsed, cold_kern_ms = timed_region(with_coll) if args.settle_ms > 0 else (None, None)
+    # 1. the cold figure: W warm-ups + K steps straight after start-up, before any settling (what `--settle-ms 0` reads).  Timed
+    #    (value_cold) with --full only; a plain run runs the same steps untimed, so that `value` follows the same steps either way
+    cold_elapsed = None
+    if args.settle_ms > 0:
+        if args.full:
+            cold_elapsed = timed_region(with_coll)[0]
+        else:
+            run_steps(args.warmup + args.steps, collective=with_coll)
     # 2. clock/power settling, untimed (see --settle-ms).  A FIXED number of steps, identical on every rank: the steps
     #    contain a collective
     if args.settle_ms > 0:
         run_steps(int(args.settle_ms), collective=with_coll)
         torch.cuda.synchronize()
     # 3. the reported region
-    elapsed, kern_ms = timed_region(with_coll)
-    # 4. BASELINE config 4 "with and without the collective": the same K steps with no all-gather
-    nocoll_elapsed = timed_region(False)[0] if with_coll else None
+    elapsed, kern_ms, (last_pose, last_gathered) = timed_region(with_coll)
+    if rank == 0 and args.dump_outputs:
+        dump_array(args.dump_outputs, "pose", last_pose.cpu().numpy())
+        if last_gathered is not None:
+            dump_array(args.dump_outputs, "pose_gathered", last_gathered.cpu().numpy())
+    # 4. (--full) BASELINE config 4 "with and without the collective": the same K steps with no all-gather
+    nocoll_elapsed = timed_region(False)[0] if args.full and with_coll else None
 
     if rank == 0:
         value = world * B * args.steps / elapsed
@@ -409,7 +448,7 @@ def main():
             "data": "synthetic" if not rehearsal else "synthetic (REHEARSAL: gloo, shared devices -- not a measurement)",
             "config": {"workload": f"landmarks->pose, batch {B}/GPU, F=1404 (468x3 landmarks), encoder+3 heads "
                                    f"{'layer-per-launch' if layered else 'fused'} HIP forward, {what}, path={args.path}",
-                       "faces_per_gpu": B, "F": F, "path": args.path, "mode": args.mode, "settle_ms": args.settle_ms,
+                       "faces_per_gpu": B, "F": F, "path": args.path, "mode": args.mode, "settle_ms": args.settle_ms, "full": args.full,
                        "seeds": {"encoder": 0, "landmarks": "1+rank"},
                        "collective": "all_gather f32[B,3] per step" if with_coll else "none"},
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
@@ -418,10 +457,10 @@ def main():
                          "flop_per_launch": B * FLOP_PER_FACE[F],
                          "hbm_frac": B * (BYTES_PER_FACE_K2[F]) / (kern_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, **roof_extra},
         }
-        if cold_elapsed is not None:
+        if args.settle_ms > 0:
             rec["warmup_effective"] = args.warmup + args.steps + int(args.settle_ms) + args.warmup
             rec["cold_note"] = (f"`warmup` is the flag as passed; the reported K steps are preceded by warmup_effective = {rec['warmup_effective']} "
-                                f"untimed-or-separately-timed steps: W={args.warmup} warm-ups + K={args.steps} steps timed as value_cold (straight after "
+                                f"untimed-or-separately-timed steps: W={args.warmup} warm-ups + K={args.steps} steps (timed as value_cold with --full; straight after "
                                 f"start-up), {int(args.settle_ms)} settling steps (--settle-ms; the kernel runs at the board's power limit and the clock "
                                 f"needs ~0.25 s of load to reach its sustained level), then W={args.warmup} warm-ups again.  --settle-ms 0 makes "
                                 f"--warmup the only warm-up (value then equals value_cold's definition).")
@@ -432,7 +471,7 @@ def main():
         if nocoll_elapsed is not None:
             rec["value_no_collective"] = world * B * args.steps / nocoll_elapsed
             rec["ms_per_step_no_collective"] = nocoll_elapsed / args.steps * 1e3
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sample = np.arange(0, B, max(1, B // 2048))[:2048]
             got = step_fn()[torch.from_numpy(sample).to(dev)].cpu().numpy()
             rec["cpu_baseline"] = cpu_baseline(raw_np, sd, heads, args.cpu_seconds, sample, got)
@@ -440,7 +479,7 @@ def main():
             rec["cpu_baseline"]["parity_check_operating_range"] = parity_operating_range(ops, weights, dev, heads, mode, args.mode, others)
             if not args.no_extra:
                 rec["cpu_baseline"]["td_path"] = td_cpu_baseline(weights, synth)
-        if world == 1 and not args.no_extra and B == 65536:    # the secondary workloads are defined on the 65,536-face batch
+        if world == 1 and args.full and not args.no_extra and B == 65536:    # the secondary workloads are defined on the 65,536-face batch
             rec["extra"] = extra_workloads(ops, synth, weights, dev, heads, sd, raw, feats, B)
         print(json.dumps(rec), flush=True)
     if dist is not None:

@@ -99,3 +99,19 @@ def test_bench_self_launch_deadline_and_profiler_refusal(tmp_path, repo_root):
     res = subprocess.run([sys.executable, "-c", drv], env=dict(env, LD_PRELOAD="/nonexistent/librocprofiler-sdk-tool.so"),   # (ld.so ignores a missing preload)
                          capture_output=True, text=True, timeout=120)
     assert res.returncode == 2 and "profiler" in res.stderr, (res.returncode, res.stderr)
+
+
+def test_bench_dump_outputs_caps_each_array(tmp_path):
+    """bench.py --dump-outputs: an array within the cap is written whole; a larger one as the evenly strided sample of its rows
+    that fits under the cap (the same rows for the same shape, so two builds' dumps compare row for row)."""
+    import numpy as np
+    import bench
+    small = np.arange(65536 * 3, dtype=np.float32).reshape(65536, 3)
+    bench.dump_array(str(tmp_path / "d"), "pose", small)
+    assert np.array_equal(np.load(tmp_path / "d" / "pose.npy"), small)
+    n = bench.DUMP_MAX_BYTES // 12 * 2 + 5                   # just over twice the cap in rows of three f32
+    big = np.arange(n * 3, dtype=np.float32).reshape(n, 3)
+    bench.dump_array(str(tmp_path / "d"), "pose_gathered", big)
+    got = np.load(tmp_path / "d" / "pose_gathered.npy")
+    assert got.nbytes <= bench.DUMP_MAX_BYTES and got.dtype == np.float32
+    assert np.array_equal(got, big[::3])                     # the smallest whole stride that fits

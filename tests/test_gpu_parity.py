@@ -1456,7 +1456,7 @@ def test_reference_order_objective_on_200k_random_evaluations(tucker_art, device
 
 @pytest.mark.parametrize("mode", [None, "f32", "f16x2"])
 def test_bench_line_carries_the_contract_fields(mode, repo_root, device):
-    """`python bench.py` (short run): ONE JSON line with the contract's fields, a roofline block, the CPU baseline with both live parity
+    """`python bench.py --full` (short run): ONE JSON line with the contract's fields, a roofline block, the CPU baseline with both live parity
     checks -- the seed-0 sample of the timed batch and the operating-range statistics (FX3c) next to the reference's own.  mode None =
     no --mode flag: the default must be the strict-fast mode, and that run also measures roofline.traffic live (two rocprofv3 --pmc
     child passes on this box); the other modes run with --no-traffic and must say `traffic: null`, never a number from elsewhere."""
@@ -1464,7 +1464,7 @@ def test_bench_line_carries_the_contract_fields(mode, repo_root, device):
     import sys
     flags = ["--no-traffic", "--mode", mode] if mode else []
     mode = mode or "f16x2s"
-    res = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--steps", "3", "--warmup", "1", "--settle-ms", "0",
+    res = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--settle-ms", "0",
                           "--no-extra", "--cpu-seconds", "1"] + flags, capture_output=True, text=True, timeout=900, cwd=repo_root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -1495,6 +1495,31 @@ def test_bench_line_carries_the_contract_fields(mode, repo_root, device):
         assert k_["p50_deg"] <= 1.32 * r_["p50_deg"] and k_["max_deg"] <= 1.47e-4
 
 
+def test_bench_plain_run_dumps_the_last_step(repo_root, device, head_sds, tmp_path):
+    """`python bench.py` without --full: the contract fields and nothing of what --full adds, exactly --steps timed steps, and
+    --dump-outputs writes the last timed step's poses -- the same bits as the default-mode forward of the same seeded faces here."""
+    import subprocess
+    import sys
+    from nlml_hpe_amd import _lib
+    res = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--steps", "3", "--warmup", "1", "--settle-ms", "0",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=repo_root)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup_effective"] == 1 and rec["dtype"] == "f16x2s" and rec["config"]["full"] is False
+    assert "cpu_baseline" not in rec and "extra" not in rec and rec["value_cold"] is None and rec["roofline"]["traffic"] is None
+    assert abs(rec["value"] - 65536 / rec["ms_per_step"] * 1e3) <= 1e-6 * rec["value"]
+    assert sorted(os.listdir(tmp_path)) == ["pose.npy"]
+    got = np.load(tmp_path / "pose.npy")
+    assert got.dtype == np.float32 and got.shape == (65536, 3)
+    blob = torch.from_numpy(weights.pack_blob(synth.encoder_state_dict(1404, seed=0), head_sds, _lib.MODE_F16X2S)).to(device)
+    want = ops.landmarks_to_pose(torch.from_numpy(synth.raw_landmarks(65536, seed=1)).to(device), blob, True).cpu().numpy()
+    assert np.array_equal(got, want)
+
+
 def test_bench_two_rank_path_on_one_gpu(repo_root, device):
     """The N > 1 path of bench.py -- self-launched ranks, the untimed VERIFIED all-gather, the timed steps with and without the
     collective -- rehearsed with two ranks that share this GPU over gloo (NLML_BENCH_REHEARSAL=1: plumbing only, never a
@@ -1503,7 +1528,7 @@ def test_bench_two_rank_path_on_one_gpu(repo_root, device):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["NLML_BENCH_REHEARSAL"] = "1"
-    res = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                           "--settle-ms", "0", "--batch", "2000", "--no-extra", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, cwd=repo_root, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -1743,7 +1768,7 @@ def test_rccl_bench_two_ranks(repo_root):
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "NLML_BENCH_REHEARSAL")}
-    res = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--gpus", "2", "--batch", "2000", "--steps", "3", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--full", "--gpus", "2", "--batch", "2000", "--steps", "3", "--warmup", "1",
                           "--settle-ms", "0", "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=repo_root, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
