@@ -33,6 +33,9 @@ def NLML_HPE_Tester(argv=None):
                     help="kernel mode (default: NLML_HPE_MODE or f16x2s = strict-fast: split-f16 operands with split accumulators on the f16 matrix "
                          "cores, inside the reference's own distance from the exact result; f32 = the strict parity mode on the f32 cores; "
                          "f16x2 = opt-in, 1.10x the reference's error at +-45 deg poses; bf16 = throughput only, ~0.1 deg)")
+    ap.add_argument("--metrics", choices=["host", "device"], default="host",
+                    help="host: gather every rank's poses to rank 0 and evaluate there (numpy + ATen); device: every rank evaluates its own "
+                         "shard in one native pass (metrics.evaluate), only the partial records are gathered")
     args = ap.parse_args(argv)
     warnings.filterwarnings("default")
 
@@ -79,6 +82,8 @@ def NLML_HPE_Tester(argv=None):
         pose, valid = torch.from_numpy(pose_np).to(device), torch.from_numpy(valid_np).to(device)
     else:
         pose, valid = torch.zeros((0, 3), device=device), torch.zeros((0,), dtype=torch.bool, device=device)
+    if args.metrics == "device":
+        return _evaluate_on_device(pose, valid, gt_all[start:stop], n_total, lo, hi, intervals, t0, rank, world)
     if world > 1:
         pose = gather_poses(pose, n_total)
         valid = gather_poses(valid.float().unsqueeze(1).expand(-1, 3).contiguous(), n_total)[:, 0] > 0.5
@@ -100,6 +105,32 @@ def NLML_HPE_Tester(argv=None):
         print(f"Average Elapsed time for test: {h:02}:{m:02}:{s:05.2f}  ({n_total / max(elapsed, 1e-9):,.0f} faces/s)")
         return res
     return None
+
+
+def _evaluate_on_device(pose, valid, gt, n_total, lo, hi, intervals, t0, rank, world):
+    """--metrics device: the evaluation block as one native pass per rank (rounding, filters, errors, intervals); the ranks'
+    partial records are merged in rank order and rank 0 prints what the host path prints."""
+    group = None
+    if world > 1:
+        import torch.distributed as dist
+        group = dist.group.WORLD
+    torch.cuda.synchronize()
+    elapsed = time.time() - t0                     # the model's time, as the host path reports it
+    res = metrics.evaluate(pose, valid, torch.from_numpy(np.ascontiguousarray(gt)).to(pose.device), lo, hi, intervals, decimals=3,
+                           group=group, verbose=False)
+    if rank != 0:
+        return None
+    print(f"processed {res['n_processed']} of {n_total} samples "
+          f"({res['n_no_face']} without landmarks, {res['n_out_of_range']} out of range)")
+    print("=============================Metrics for pred_angles_NLML_HPE:")
+    metrics.print_errors(res)
+    print("\n======================================================================")
+    for k, v in res.items():
+        if k.endswith(" - NLML_HPE"):
+            print(f"{k}: {v:.3f}")
+    h, m, s = int(elapsed // 3600), int((elapsed % 3600) // 60), elapsed % 60
+    print(f"Average Elapsed time for test: {h:02}:{m:02}:{s:05.2f}  ({n_total / max(elapsed, 1e-9):,.0f} faces/s)")
+    return res
 
 
 if __name__ == "__main__":

@@ -284,6 +284,42 @@ int nlml_video_post_ex(const float* pose_rad, const float* raw, const uint8_t* v
                        double frame_w, double frame_h, double alpha, double max_jump, double size,
                        double* state, double* smoothed, double* centre, double* endpoints, uint8_t* updated, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K5  Evaluation: the metrics block of the test entry point in one pass over the predictions.
+ * Replaces NLML_HPE_Test.py's evaluation (reference :95-152, :252-273): pred = np.round(np.degrees(pose), d), the GT range
+ * filter lo <= gt <= hi (inclusive) and the no-face filter, then over the kept faces compute_errors (per-axis MAE,
+ * std ddof=1, total MAE, MAEV and the left/down/front vector errors of R = Rx(pitch) Ry(-yaw) Rz(roll)) and the MAE per
+ * half-open GT interval [low, high) of compute_interval_mae.  All per-face arithmetic in f64.
+ *   pose_rad  f32[B,3] radians (the model's output) -- or -- pred_deg f64[B,3] degrees: exactly one of the two (B = 0: either may be NULL)
+ *   valid     u8[B] or NULL (NULL = every row has a face)
+ *   gt_deg    f64[B,3] degrees (yaw, pitch, roll)
+ *   h_lo, h_hi   f64[3] host: the inclusive GT range per axis
+ *   decimals  d >= 0: pred = rint(deg * 10^d) / 10^d (np.round); d < 0: no rounding; at most 15
+ *   h_intervals f64[K,2] host (low, high); h_axes i32[K] host (0 yaw, 1 pitch, 2 roll); K <= NLML_POSE_EVAL_MAX_INTERVALS
+ *   workspace  nlml_pose_eval_workspace_bytes(B, K) bytes, 8-byte aligned (may be NULL when that is 0)
+ *   record_out f64[record_len] or NULL: the merged partial record (what nlml_pose_eval_merge merges across calls or ranks)
+ *   result_out f64[result_len]
+ *   pred_out f64[B,3] or NULL: pred;  keep_out u8[B] or NULL: the keep mask
+ * Record: [kept, no_face, out_of_range, mean e[3], M2 e[3], sum v[3] (left, down, front), (count_k, sum e[a_k]_k) x K].
+ * Result: [mae yaw/pitch/roll, mae_total, maev, v left/down/front, std yaw/pitch/roll, kept, no_face, out_of_range,
+ *          (count_k, mae_k) x K]; no kept face gives NaN means, one kept face NaN std, a count_k of 0 a NaN mae_k (numpy's f64).
+ * Two launches: one record per NLML_POSE_EVAL_FACES_PER_RECORD faces (a constant), then one workgroup merges them in index
+ * order (Chan's pairwise merge for mean / M2, plain sums otherwise).  No atomics, no host-to-device copy (the bounds and the
+ * intervals travel in the kernel arguments): bit-identical from run to run, and capturable in a hipGraph.
+ * nlml_pose_eval_merge merges n records f64[n, record_len] (e.g. one per rank, in rank order) the same way.
+ */
+#define NLML_POSE_EVAL_MAX_INTERVALS    64
+#define NLML_POSE_EVAL_FACES_PER_RECORD 2048
+size_t nlml_pose_eval_record_len(int n_intervals);                 /* 12 + 2K doubles; 0 if K is out of range */
+size_t nlml_pose_eval_result_len(int n_intervals);                 /* 14 + 2K doubles; 0 if K is out of range */
+size_t nlml_pose_eval_workspace_bytes(int64_t B, int n_intervals);
+int nlml_pose_eval(const float* pose_rad, const double* pred_deg, const uint8_t* valid, const double* gt_deg, int64_t B,
+                   const double* h_lo, const double* h_hi, int decimals, const double* h_intervals, const int32_t* h_axes,
+                   int n_intervals, void* workspace, size_t workspace_bytes, double* record_out, double* result_out,
+                   double* pred_out, uint8_t* keep_out, void* stream);
+int nlml_pose_eval_merge(const double* records, int64_t n, int n_intervals, double* record_out, double* result_out,
+                         void* stream);
+
 /* Artefact producers that are pure tensor algebra.
  *
  * nlml_cosine_table replaces the two nested loops over cosine() that build the heads' training inputs

@@ -244,6 +244,62 @@ int nlml_mode5_product(const float* core, const float* U_feat, int Q, int R5, in
   return launch_mode5_product(core, U_feat, Q, R5, M, W, stream);
 }
 
+// ---- K5 evaluation ---------------------------------------------------------------------------------
+static bool eval_k_ok(int K) { return K >= 0 && K <= NLML_POSE_EVAL_MAX_INTERVALS; }
+static int64_t eval_records(int64_t B) { return (B + NLML_POSE_EVAL_FACES_PER_RECORD - 1) / NLML_POSE_EVAL_FACES_PER_RECORD; }
+
+size_t nlml_pose_eval_record_len(int n_intervals) { return eval_k_ok(n_intervals) ? (size_t)(12 + 2 * n_intervals) : 0; }
+size_t nlml_pose_eval_result_len(int n_intervals) { return eval_k_ok(n_intervals) ? (size_t)(14 + 2 * n_intervals) : 0; }
+size_t nlml_pose_eval_workspace_bytes(int64_t B, int n_intervals) {
+  if (B < 0 || !eval_k_ok(n_intervals)) return 0;
+  return (size_t)eval_records(B) * nlml_pose_eval_record_len(n_intervals) * sizeof(double);
+}
+
+static bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+
+int nlml_pose_eval(const float* pose_rad, const double* pred_deg, const uint8_t* valid, const double* gt_deg, int64_t B,
+                   const double* h_lo, const double* h_hi, int decimals, const double* h_intervals, const int32_t* h_axes,
+                   int n_intervals, void* workspace, size_t workspace_bytes, double* record_out, double* result_out,
+                   double* pred_out, uint8_t* keep_out, void* stream) {
+  if (B < 0) return fail(NLML_E_BADARG, "pose_eval: negative B");
+  // an empty tensor's data pointer may be NULL: with B == 0 "neither" is accepted
+  if ((pose_rad && pred_deg) || (B > 0 && !pose_rad && !pred_deg))
+    return fail(NLML_E_BADARG, "pose_eval: give exactly one of pose_rad and pred_deg");
+  if (B > 0 && !gt_deg) return fail(NLML_E_BADARG, "pose_eval: null gt_deg");
+  if (!h_lo || !h_hi || !result_out) return fail(NLML_E_BADARG, "pose_eval: null lo / hi / result_out");
+  if (!eval_k_ok(n_intervals)) return fail(NLML_E_BADARG, "pose_eval: number of intervals outside [0, NLML_POSE_EVAL_MAX_INTERVALS]");
+  if (n_intervals > 0 && (!h_intervals || !h_axes)) return fail(NLML_E_BADARG, "pose_eval: null intervals / axes");
+  if (decimals > 15) return fail(NLML_E_BADARG, "pose_eval: decimals > 15");
+  const size_t need = nlml_pose_eval_workspace_bytes(B, n_intervals);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(NLML_E_BADARG, "pose_eval: workspace too small");
+  if (misaligned8(pred_deg) || misaligned8(gt_deg) || misaligned8(workspace) || misaligned8(record_out) || misaligned8(result_out) ||
+      misaligned8(pred_out) || (reinterpret_cast<uintptr_t>(pose_rad) & 3))
+    return fail(NLML_E_BADARG, "pose_eval: f64 buffers must be 8-byte aligned, pose_rad 4-byte aligned");
+  PoseEvalArgs a{};
+  for (int i = 0; i < 3; ++i) { a.lo[i] = h_lo[i]; a.hi[i] = h_hi[i]; }
+  for (int k = 0; k < n_intervals; ++k) {
+    if (h_axes[k] < 0 || h_axes[k] > 2) return fail(NLML_E_BADARG, "pose_eval: interval axis outside {0, 1, 2}");
+    a.axes[k] = h_axes[k];
+    a.ivl[k][0] = h_intervals[2 * k];
+    a.ivl[k][1] = h_intervals[2 * k + 1];
+  }
+  a.scale = 1.0;
+  for (int i = 0; i < decimals; ++i) a.scale *= 10.0;   // exact: every 10^d, d <= 15, is an integer below 2^53
+  a.K = n_intervals;
+  a.decimals = decimals;
+  return launch_pose_eval(pose_rad, pred_deg, valid, gt_deg, B, a, static_cast<double*>(workspace), record_out, result_out, pred_out,
+                          keep_out, stream);
+}
+
+int nlml_pose_eval_merge(const double* records, int64_t n, int n_intervals, double* record_out, double* result_out, void* stream) {
+  if (n < 0) return fail(NLML_E_BADARG, "pose_eval_merge: negative record count");
+  if (!eval_k_ok(n_intervals)) return fail(NLML_E_BADARG, "pose_eval_merge: number of intervals outside [0, NLML_POSE_EVAL_MAX_INTERVALS]");
+  if ((n > 0 && !records) || !result_out) return fail(NLML_E_BADARG, "pose_eval_merge: null records / result_out");
+  if (misaligned8(records) || misaligned8(record_out) || misaligned8(result_out))
+    return fail(NLML_E_BADARG, "pose_eval_merge: buffers must be 8-byte aligned");
+  return launch_pose_eval_merge(records, n, n_intervals, record_out, result_out, stream);
+}
+
 // ---- host-side stepping of the Powell state machine (powell.h) --------------------------------
 size_t nlml_powell_state_bytes(void) { return sizeof(PowellState); }
 

@@ -3,6 +3,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/nlml_hpe.h"
+
 namespace nlml {
 
 // Records msg in the thread-local error slot and returns code (never 0).
@@ -71,5 +73,18 @@ int launch_tucker_powell(const float* Wm, const float* x, int64_t ldx, const dou
 int launch_video_post(const float* pose_rad, const float* raw, const uint8_t* valid, int64_t S, double frame_w,
                       double frame_h, double alpha, double max_jump, double size, double* state, double* smoothed,
                       double* centre, double* endpoints, uint8_t* updated, void* stream);
+
+// pose_eval.hip: everything of a call that is not a pointer, passed by value in the kernel arguments
+struct PoseEvalArgs {
+  double lo[3], hi[3];
+  double scale;                                      // 10^decimals (exact for decimals <= 15)
+  double ivl[NLML_POSE_EVAL_MAX_INTERVALS][2];
+  int32_t axes[NLML_POSE_EVAL_MAX_INTERVALS];
+  int K, decimals;
+};
+int launch_pose_eval(const float* pose_rad, const double* pred_deg, const uint8_t* valid, const double* gt_deg, int64_t B,
+                     const PoseEvalArgs& args, double* workspace, double* record_out, double* result_out, double* pred_out,
+                     uint8_t* keep_out, void* stream);
+int launch_pose_eval_merge(const double* records, int64_t n, int K, double* record_out, double* result_out, void* stream);
 
 }  // namespace nlml

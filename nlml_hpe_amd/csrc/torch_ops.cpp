@@ -17,6 +17,7 @@
 
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "../../include/nlml_hpe.h"
 
@@ -256,6 +257,56 @@ at::Tensor cosine_table(const at::Tensor& angles_, const at::Tensor& cosp_) {
   return out;
 }
 
+// K5: the evaluation block in one native pass.  pose f32[B,3] radians or f64[B,3] degrees (by dtype), valid bool/u8[B] or None,
+// gt f64[B,3]; lo / hi the inclusive GT range, intervals [K*2] (low, high) with their axes [K]; the records' workspace comes from
+// torch's allocator -> (record f64[12+2K], result f64[14+2K])
+std::tuple<at::Tensor, at::Tensor> pose_eval(const at::Tensor& pose_, const std::optional<at::Tensor>& valid_, const at::Tensor& gt_,
+                                             at::ArrayRef<double> lo, at::ArrayRef<double> hi, int64_t decimals,
+                                             at::ArrayRef<double> intervals, at::ArrayRef<int64_t> axes) {
+  TORCH_CHECK(pose_.is_cuda(), "pose: expected a GPU tensor (there is no CPU fallback), got ", pose_.device());
+  TORCH_CHECK(pose_.scalar_type() == at::kFloat || pose_.scalar_type() == at::kDouble, "pose: expected float32 radians or float64 degrees");
+  need(gt_, "gt", at::kDouble);
+  same_device(pose_, gt_, "gt");
+  const int64_t B = pose_.size(0);
+  TORCH_CHECK(pose_.dim() == 2 && pose_.size(1) == 3 && gt_.dim() == 2 && gt_.size(0) == B && gt_.size(1) == 3,
+              "pose and gt: expected [B,3] each, got ", pose_.sizes(), " and ", gt_.sizes());
+  TORCH_CHECK(lo.size() == 3 && hi.size() == 3, "lo / hi: expected 3 values each");
+  const int64_t K = (int64_t)axes.size();
+  TORCH_CHECK((int64_t)intervals.size() == 2 * K, "intervals: expected 2 values per axis entry");
+  TORCH_CHECK(K <= NLML_POSE_EVAL_MAX_INTERVALS, "at most ", NLML_POSE_EVAL_MAX_INTERVALS, " intervals");
+  std::vector<int32_t> ax(axes.begin(), axes.end());
+  const at::Tensor pose = pose_.contiguous(), gt = gt_.contiguous();
+  at::Tensor valid;
+  if (valid_.has_value()) {
+    TORCH_CHECK(valid_->scalar_type() == at::kBool || valid_->scalar_type() == at::kByte, "valid: expected bool or uint8");
+    same_device(pose_, *valid_, "valid");
+    TORCH_CHECK(valid_->dim() == 1 && valid_->size(0) == B, "valid: expected [B]");
+    valid = valid_->contiguous();
+  }
+  const auto f64 = gt.options();
+  at::Tensor ws = at::empty({std::max<int64_t>(1, (int64_t)nlml_pose_eval_workspace_bytes(B, (int)K) / 8)}, f64);
+  at::Tensor record = at::empty({12 + 2 * K}, f64), result = at::empty({14 + 2 * K}, f64);
+  const bool f32 = pose.scalar_type() == at::kFloat;
+  OnDevice dev(pose);
+  check(nlml_pose_eval(f32 ? pose.data_ptr<float>() : nullptr, f32 ? nullptr : pose.data_ptr<double>(),
+                       valid.defined() ? static_cast<const uint8_t*>(valid.data_ptr()) : nullptr, gt.data_ptr<double>(), B, lo.data(),
+                       hi.data(), (int)decimals, intervals.data(), ax.data(), (int)K, ws.data_ptr(), (size_t)ws.numel() * 8,
+                       record.data_ptr<double>(), result.data_ptr<double>(), nullptr, nullptr, dev.stream), "nlml_pose_eval");
+  return {record, result};
+}
+
+std::tuple<at::Tensor, at::Tensor> pose_eval_merge(const at::Tensor& records_, int64_t K) {
+  need(records_, "records", at::kDouble);
+  TORCH_CHECK(K >= 0 && K <= NLML_POSE_EVAL_MAX_INTERVALS, "K: at most ", NLML_POSE_EVAL_MAX_INTERVALS, " intervals");
+  TORCH_CHECK(records_.dim() == 2 && records_.size(1) == 12 + 2 * K, "records: expected [n,", 12 + 2 * K, "], got ", records_.sizes());
+  const at::Tensor records = records_.contiguous();
+  at::Tensor record = at::empty({12 + 2 * K}, records.options()), result = at::empty({14 + 2 * K}, records.options());
+  OnDevice dev(records);
+  check(nlml_pose_eval_merge(records.data_ptr<double>(), records.size(0), (int)K, record.data_ptr<double>(), result.data_ptr<double>(),
+                             dev.stream), "nlml_pose_eval_merge");
+  return {record, result};
+}
+
 // ---- shapes only (Meta backend: tracing / fake tensors) -------------------------------------------------------------
 at::Tensor normalize_ipd_meta(const at::Tensor& raw, bool) { return at::empty({raw.size(0), F_REF}, raw.options()); }
 at::Tensor pose_meta3(const at::Tensor& x, const at::Tensor&, int64_t) { return at::empty({x.size(0), 3}, x.options()); }
@@ -278,6 +329,16 @@ void video_post_meta(const at::Tensor&, const at::Tensor&, const std::optional<a
                      at::Tensor, at::Tensor, at::Tensor, at::Tensor) {}   // everything in place: nothing to shape
 at::Tensor cosine_table_meta(const at::Tensor& angles, const at::Tensor& cosp) { return at::empty({angles.size(0), cosp.size(0)}, cosp.options()); }
 
+std::tuple<at::Tensor, at::Tensor> pose_eval_meta(const at::Tensor& pose, const std::optional<at::Tensor>&, const at::Tensor& gt,
+                                                  at::ArrayRef<double>, at::ArrayRef<double>, int64_t, at::ArrayRef<double>,
+                                                  at::ArrayRef<int64_t> axes) {
+  const int64_t K = (int64_t)axes.size();
+  return {at::empty({12 + 2 * K}, gt.options()), at::empty({14 + 2 * K}, gt.options())};
+}
+std::tuple<at::Tensor, at::Tensor> pose_eval_merge_meta(const at::Tensor& records, int64_t K) {
+  return {at::empty({12 + 2 * K}, records.options()), at::empty({14 + 2 * K}, records.options())};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nlml_hpe, m) {
@@ -292,6 +353,9 @@ TORCH_LIBRARY(nlml_hpe, m) {
   m.def("video_post(Tensor pose_rad, Tensor raw, Tensor? valid, float frame_w, float frame_h, float alpha, float max_jump, float size, "
         "Tensor(a!) state, Tensor(b!) smoothed, Tensor(c!) centre, Tensor(d!) endpoints, Tensor(e!) updated) -> ()");
   m.def("cosine_table(Tensor angles_rad, Tensor cos_params) -> Tensor");
+  m.def("pose_eval(Tensor pose, Tensor? valid, Tensor gt, float[] lo, float[] hi, int decimals, float[] intervals, int[] axes) "
+        "-> (Tensor, Tensor)");
+  m.def("pose_eval_merge(Tensor records, int K) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CUDA key
@@ -305,6 +369,8 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
   m.impl("tucker_powell", &tucker_powell);
   m.impl("video_post", &video_post);
   m.impl("cosine_table", &cosine_table);
+  m.impl("pose_eval", &pose_eval);
+  m.impl("pose_eval_merge", &pose_eval_merge);
 }
 
 TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
@@ -318,4 +384,6 @@ TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("tucker_powell", &tucker_powell_meta);
   m.impl("video_post", &video_post_meta);
   m.impl("cosine_table", &cosine_table_meta);
+  m.impl("pose_eval", &pose_eval_meta);
+  m.impl("pose_eval_merge", &pose_eval_merge_meta);
 }

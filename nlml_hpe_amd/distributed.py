@@ -64,3 +64,15 @@ def gather_poses(local_pose: torch.Tensor, n_total: int, group=None) -> torch.Te
     out = torch.empty((world * per, 3), dtype=local_pose.dtype, device=local_pose.device)
     dist.all_gather_into_tensor(out, block.contiguous(), group=group)
     return out[:n_total]
+
+
+def gather_records(record: torch.Tensor, group=None) -> torch.Tensor:
+    """All ranks call with their evaluation record f64[L] (ops.pose_eval); returns f64[world, L] in rank order, by the same
+    all-gather gather_poses issues.  A gloo group (the one-GPU rehearsal of the N > 1 path) collates on the host."""
+    world = dist.get_world_size(group)
+    src = record.reshape(1, -1)
+    if dist.get_backend(group) == "gloo":
+        src = src.cpu()
+    out = torch.empty((world, src.shape[1]), dtype=src.dtype, device=src.device)
+    dist.all_gather_into_tensor(out, src.contiguous(), group=group)
+    return out

@@ -82,3 +82,45 @@ def compute_interval_mae(true_angles, pred_angles, yaw_intervals, pitch_interval
             if bool(m.any()):
                 res[f"{name} ({low}, {high}) - {label}"] = (t[m, idx] - p[m, idx]).abs().mean().item()
     return res
+
+
+_ERROR_LINES = (("MAE (Yaw)", "mae_yaw"), ("MAE (Pitch)", "mae_pitch"), ("MAE (Roll)", "mae_roll"), ("Total MAE", "mae_total"),
+                ("MAEV", "maev"), ("Left vector Error (red)", "v_left"), ("Down vector Error (green)", "v_down"),
+                ("Front vector Error (blue)", "v_front"), ("std (Yaw)", "std_yaw"), ("std (Pitch)", "std_pitch"),
+                ("std (Roll)", "std_roll"))
+
+
+def print_errors(out: dict) -> None:
+    """The block compute_errors prints (the reference's :119-129)."""
+    for label, key in _ERROR_LINES:
+        print(f"{label}: {out[key]:.2f}")
+
+
+def evaluate(pose, valid, gt, lo, hi, intervals, decimals: int = 3, label: str = "NLML_HPE", group=None, verbose: bool = True) -> dict:
+    """The whole evaluation block of the test entry point in one native pass (ops.pose_eval) and ONE device-to-host copy.
+
+    pose   f32[B,3] radians (the model's output) or f64[B,3] degrees, on the GPU; valid bool[B] or None; gt f64[B,3] degrees
+    lo, hi the inclusive GT range per axis; intervals (yaw_intervals, pitch_intervals, roll_intervals) of (low, high) pairs
+    -> compute_errors' dict, plus compute_interval_mae's keys ('<Name> (<low>, <high>) - <label>', intervals with kept faces
+    only) and n_processed / n_no_face / n_out_of_range.  With a process group of world > 1 every rank passes its own shard:
+    the ranks' records are all-gathered and merged in rank order, and every rank returns the same dict."""
+    from . import ops
+    flat = [(a, low, high) for a, ivs in enumerate(intervals) for low, high in ivs]
+    if not torch.is_tensor(gt) or gt.device != pose.device:
+        gt = torch.as_tensor(gt, dtype=torch.float64).to(pose.device)
+    record, result = ops.pose_eval(pose, gt.to(torch.float64), valid, lo, hi, flat, decimals)
+    if group is not None:
+        import torch.distributed as dist
+        if dist.get_world_size(group) > 1:
+            from .distributed import gather_records
+            record, result = ops.pose_eval_merge(gather_records(record, group).to(pose.device), len(flat))
+    r = result.cpu().tolist()                                     # the one device-to-host copy
+    out = {"mae_yaw": r[0], "mae_pitch": r[1], "mae_roll": r[2], "mae_total": r[3], "maev": r[4], "v_left": r[5], "v_down": r[6],
+           "v_front": r[7], "std_yaw": r[8], "std_pitch": r[9], "std_roll": r[10]}
+    for k, (a, low, high) in enumerate(flat):
+        if r[14 + 2 * k] > 0:
+            out[f'{("Yaw", "Pitch", "Roll")[a]} ({low}, {high}) - {label}'] = r[15 + 2 * k]
+    out.update(n_processed=int(r[11]), n_no_face=int(r[12]), n_out_of_range=int(r[13]))
+    if verbose:
+        print_errors(out)
+    return out

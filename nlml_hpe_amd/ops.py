@@ -195,7 +195,8 @@ def _load_torch_ops():
     _lib.lib()                                  # the C ABI library the shim links against, checked symbol by symbol first
     torch.ops.load_library(TORCH_OPS_PATH)
     for name in ("normalize_ipd", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
-                 "landmarks_to_pose_valid", "tucker_objective", "tucker_powell", "video_post", "cosine_table"):
+                 "landmarks_to_pose_valid", "tucker_objective", "tucker_powell", "video_post", "cosine_table", "pose_eval",
+                 "pose_eval_merge"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
 
@@ -389,3 +390,94 @@ def landmarks_to_pose_streamed(raw: torch.Tensor, blob: torch.Tensor, normalize:
     if return_valid:
         res.append(valid.bool())
     return res[0] if len(res) == 1 else tuple(res)
+
+
+# ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------
+_eval_ws: dict = {}
+
+
+def _eval_workspace(B: int, K: int, device) -> torch.Tensor:
+    """The per-workgroup records of nlml_pose_eval (f64, 8-byte aligned), cached per device and stream; replaced when it must grow."""
+    need = max(8, _lib.lib().nlml_pose_eval_workspace_bytes(B, K))
+    key = (str(device), _stream_ptr(device))
+    ws = _eval_ws.get(key)
+    if ws is None or ws.numel() * 8 < need:
+        ws = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=device)
+        _eval_ws[key] = ws
+    return ws
+
+
+def _eval_intervals(intervals):
+    """[(axis, low, high), ...] -> (h_intervals f64[K,2], h_axes i32[K]) as ctypes arrays, K."""
+    import ctypes as C
+    iv = [(int(a), float(lo), float(hi)) for a, lo, hi in intervals]
+    K = len(iv)
+    h_iv = (C.c_double * max(1, 2 * K))(*[v for _, lo, hi in iv for v in (lo, hi)])
+    h_ax = (C.c_int32 * max(1, K))(*[a for a, _, _ in iv])
+    return h_iv, h_ax, K
+
+
+def pose_eval(pose: torch.Tensor, gt: torch.Tensor, valid: torch.Tensor | None = None, lo=None, hi=None, intervals=(), decimals: int = 3,
+              return_per_face: bool = False, workspace: torch.Tensor | None = None):
+    """The evaluation block of the test entry point in one native pass (nlml_pose_eval, two launches, no synchronisation).
+
+    pose  f32[B,3] radians (the model's output; rounded as np.round(np.degrees(pose), decimals)) or f64[B,3] degrees (already
+          post-processed; rounded only when decimals >= 0)
+    gt    f64[B,3] degrees;  valid bool/u8[B] or None (every row has a face)
+    lo, hi  3 floats, the inclusive GT range per axis (default: unbounded)
+    intervals  [(axis, low, high), ...] half-open GT intervals, axis 0 yaw / 1 pitch / 2 roll, at most 64
+    -> (record f64[12+2K], result f64[14+2K]) on the device (layouts: include/nlml_hpe.h, K5); with return_per_face also
+       pred f64[B,3] and keep bool[B]."""
+    if not pose.is_cuda:
+        raise _lib.NlmlError(f"pose: expected a GPU tensor (there is no CPU fallback), got device {pose.device}")
+    if pose.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"pose: expected float32 radians or float64 degrees, got {pose.dtype}")
+    _need_cuda(gt, "gt", torch.float64)
+    B = pose.shape[0]
+    if pose.dim() != 2 or pose.shape[1] != 3 or tuple(gt.shape) != (B, 3):
+        raise ValueError(f"pose and gt: expected [B,3] each, got {tuple(pose.shape)}, {tuple(gt.shape)}")
+    if valid is not None:
+        if not valid.is_cuda or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B,):
+            raise ValueError(f"valid: expected a GPU bool/uint8 tensor [{B}], got {valid.dtype} {tuple(valid.shape)} on {valid.device}")
+        valid = valid.contiguous()
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+    pose, gt = pose.contiguous(), gt.contiguous()
+    import ctypes as C
+    h_lo = (C.c_double * 3)(*([-float("inf")] * 3 if lo is None else [float(v) for v in lo]))
+    h_hi = (C.c_double * 3)(*([float("inf")] * 3 if hi is None else [float(v) for v in hi]))
+    h_iv, h_ax, K = _eval_intervals(intervals)
+    L = _lib.lib()
+    dev = pose.device
+    ws = workspace if workspace is not None else _eval_workspace(B, K, dev)
+    record = torch.empty((L.nlml_pose_eval_record_len(K) or 1,), dtype=torch.float64, device=dev)
+    result = torch.empty((L.nlml_pose_eval_result_len(K) or 1,), dtype=torch.float64, device=dev)
+    pred = torch.empty((B, 3), dtype=torch.float64, device=dev) if return_per_face else None
+    keep = torch.empty((B,), dtype=torch.uint8, device=dev) if return_per_face else None
+    f32 = pose.dtype == torch.float32
+    with _on_device_of(("pose", pose), ("gt", gt), ("valid", valid), ("workspace", ws)) as stream:
+        _lib.check(L.nlml_pose_eval(pose.data_ptr() if f32 else None, None if f32 else pose.data_ptr(),
+                                    valid.data_ptr() if valid is not None else None, gt.data_ptr(), B, h_lo, h_hi, int(decimals),
+                                    h_iv, h_ax, K, ws.data_ptr(), ws.numel() * ws.element_size(), record.data_ptr(), result.data_ptr(),
+                                    pred.data_ptr() if pred is not None else None, keep.data_ptr() if keep is not None else None, stream),
+                   "nlml_pose_eval")
+    if return_per_face:
+        return record, result, pred, keep.bool()
+    return record, result
+
+
+def pose_eval_merge(records: torch.Tensor, K: int):
+    """Merge records f64[n, 12+2K] (several calls or ranks, in order) as nlml_pose_eval merges its own -> (record, result)."""
+    _need_cuda(records, "records", torch.float64)
+    Lr = _lib.lib().nlml_pose_eval_record_len(int(K))
+    if Lr == 0:
+        raise ValueError(f"K = {K}: at most {_lib.POSE_EVAL_MAX_INTERVALS} intervals")
+    if records.dim() != 2 or records.shape[1] != Lr:
+        raise ValueError(f"records: expected [n,{Lr}], got {tuple(records.shape)}")
+    records = records.contiguous()
+    dev = records.device
+    record = torch.empty((Lr,), dtype=torch.float64, device=dev)
+    result = torch.empty((_lib.lib().nlml_pose_eval_result_len(int(K)),), dtype=torch.float64, device=dev)
+    with _on_device_of(("records", records)) as stream:
+        _lib.check(_lib.lib().nlml_pose_eval_merge(records.data_ptr(), records.shape[0], int(K), record.data_ptr(), result.data_ptr(),
+                                                   stream), "nlml_pose_eval_merge")
+    return record, result
