@@ -15,33 +15,32 @@ LIB_PATH = os.environ.get("NLML_HPE_LIB") or os.path.join(_HERE, "libnlml_hpe_hi
 
 # Every symbol include/nlml_hpe.h declares: (restype, argtypes)
 _c_f32p = C.c_void_p
+# the K2 forwards: two argument shapes, (x, ldx, B, F | raw, B, normalize) + (blob, blob_bytes, out, latent, valid) [+ (workspace, ws_bytes)]
+# + stream
+_FWD_X = [C.c_void_p, C.c_int64, C.c_int64, C.c_int]
+_FWD_RAW = [C.c_void_p, C.c_int64, C.c_int]
+_FWD_OUT = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+_FWD_WS = [C.c_void_p, C.c_size_t]
+
+
+def _k2_forwards():
+    for form, ws in (("", []), ("_small", _FWD_WS), ("_streamed", _FWD_WS), ("_ws", _FWD_WS)):
+        yield "nlml_encoder_heads_fwd" + form, (C.c_int, _FWD_X + _FWD_OUT + ws + [C.c_void_p])
+        yield "nlml_landmarks_to_pose" + form, (C.c_int, _FWD_RAW + _FWD_OUT + ws + [C.c_void_p])
+
+
 SYMBOLS = {
+    **dict(_k2_forwards()),
     "nlml_abi_version": (C.c_int, []),
     "nlml_last_error": (C.c_char_p, []),
     "nlml_normalize_ipd": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_encoder_heads_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "nlml_encoder_heads_pack": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t]),
-    "nlml_encoder_heads_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_encoder_heads_fwd_debug": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nlml_landmarks_to_pose": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_encoder_heads_small_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
-    "nlml_encoder_heads_fwd_small": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "nlml_landmarks_to_pose_small": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "nlml_encoder_heads_fwd_streamed": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "nlml_landmarks_to_pose_streamed": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "nlml_encoder_heads_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
-    "nlml_encoder_heads_fwd_ws": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "nlml_landmarks_to_pose_ws": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "nlml_tucker_objective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_tucker_powell": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

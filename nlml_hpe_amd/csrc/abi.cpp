@@ -1,5 +1,7 @@
 // abi.cpp -- the extern "C" surface declared in include/nlml_hpe.h: argument checks, then the
 // launchers in the .hip files.  No allocation, no synchronisation, no global mutable state.
+#include <hip/hip_runtime_api.h>
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +16,10 @@ static thread_local char g_err[256] = "";
 int fail(int code, const char* msg) {
   std::snprintf(g_err, sizeof g_err, "%s", msg ? msg : "unknown error");
   return code ? code : NLML_E_BADARG;
+}
+int hip_launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
 }
 }  // namespace nlml
 
@@ -61,15 +67,56 @@ static int check_blob_args(int64_t B, int F, const void* blob, size_t blob_bytes
   return 0;
 }
 
-int nlml_encoder_heads_fwd(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
-                           float* out, float* latent, uint8_t* valid, void* stream) {
+// ---- the K2 forward: one core behind the eight entry points --------------------------------------------------------------------
+// (crossovers measured with tools/k2_crossover.py and bench.py extra.k2_batch_sweep)
+static const int64_t kSmallMax = 4096;     // split-f16 modes: up to here the layer-per-launch path over 64-face tiles
+// The trunk + streamed-tail path (encoder_heads_f16x2_tailws.hip) is bit-identical to the fused kernel and measured 1.4-2.2 % faster at 65,536
+// faces (0.801 against 0.815 ms, same box, alternating; DESIGN.md section 3) -- inside the box-to-box spread, for a 64 MB workspace and a
+// second big launch -- so the dispatcher does not pick it by itself.  NLML_K2_STREAMED_MIN=<faces> routes batches from that size
+// on through it (the explicit _streamed entry points always do).
+static int64_t streamed_min() {
+  static const int64_t v = [] { const char* e = getenv("NLML_K2_STREAMED_MIN"); return e && e[0] ? (int64_t)atoll(e) : (int64_t)-1; }();
+  return v;
+}
+
+// The call forms: the fused kernel of the blob's mode; the split-f16 modes' layer-per-launch path (small batches); the strict-fast
+// mode's trunk + streamed tail (encoder_heads_f16x2_w8.hip TRUNK, encoder_heads_f16x2_tailws.hip); AUTO = the fastest of the three for
+// the batch size and the blob's mode, through a caller-provided workspace.
+enum K2Form { K2_FUSED, K2_SMALL, K2_STREAMED, K2_AUTO };
+
+// landmarks: the input is raw [B,468,3] (x, ldx unused), else the feature rows x / ldx (raw null).  workspace / ws_bytes are read by the
+// forms that need one.
+static int k2_forward(K2Form form, bool landmarks, const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
+                      const void* blob, size_t blob_bytes, float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes,
+                      void* stream) {
+  const char* no_input = nullptr;
+  if (B > 0 && landmarks && !raw) no_input = "landmarks_to_pose: null raw";
+  if (B > 0 && !landmarks && (!x || ldx < F)) no_input = "encoder_heads: null x or ldx < F";
+  // nlml_landmarks_to_pose_ws alone looks at raw before the blob; hosts may match on which of two errors they get
+  if (no_input && form == K2_AUTO && landmarks) return fail(NLML_E_BADARG, no_input);
   int mode = 0;
   if (int rc = check_blob_args(B, F, blob, blob_bytes, out, &mode)) return rc;
-  if (B > 0 && (!x || ldx < F)) return fail(NLML_E_BADARG, "encoder_heads: null x or ldx < F");
-  if (mode == NLML_MODE_BF16) return launch_encoder_heads_bf16(x, ldx, nullptr, 0, B, F, blob, out, latent, valid, stream);
-  if (split_f16(mode))
-    return launch_encoder_heads_f16x2(x, ldx, nullptr, 0, B, F, blob, out, latent, valid, mode == NLML_MODE_F16X2S, stream);
-  return launch_encoder_heads_f32(x, ldx, nullptr, 0, B, F, blob, out, latent, valid, nullptr, nullptr, stream);
+  if (form == K2_SMALL && !split_f16(mode)) return fail(NLML_E_BADARG, "small-batch path: NLML_MODE_F16X2 / NLML_MODE_F16X2S blob only");
+  if (form == K2_STREAMED && mode != NLML_MODE_F16X2S) return fail(NLML_E_BADARG, "streamed-tail path: NLML_MODE_F16X2S blob only");
+  if (no_input) return fail(NLML_E_BADARG, no_input);
+  const int split = mode == NLML_MODE_F16X2S;
+  if (form == K2_AUTO) {
+    if (split_f16(mode) && B <= kSmallMax) form = K2_SMALL;
+    else if (split && streamed_min() >= 0 && B >= streamed_min() && k2_input(x, ldx, raw, normalize, F).vec4) form = K2_STREAMED;
+    else form = K2_FUSED;
+  }
+  if (form == K2_SMALL)
+    return launch_encoder_heads_f16x2_small(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, split, stream);
+  if (form == K2_STREAMED)
+    return launch_encoder_heads_f16x2_tailws(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, stream);
+  if (mode == NLML_MODE_BF16) return launch_encoder_heads_bf16(x, ldx, raw, normalize, B, F, blob, out, latent, valid, stream);
+  if (split_f16(mode)) return launch_encoder_heads_f16x2(x, ldx, raw, normalize, B, F, blob, out, latent, valid, split, stream);
+  return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, blob, out, latent, valid, nullptr, nullptr, stream);
+}
+
+int nlml_encoder_heads_fwd(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
+                           float* out, float* latent, uint8_t* valid, void* stream) {
+  return k2_forward(K2_FUSED, false, x, ldx, nullptr, 0, B, F, blob, blob_bytes, out, latent, valid, nullptr, 0, stream);
 }
 
 int nlml_encoder_heads_fwd_debug(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
@@ -83,77 +130,29 @@ int nlml_encoder_heads_fwd_debug(const float* x, int64_t ldx, int64_t B, int F, 
 
 int nlml_landmarks_to_pose(const float* raw, int64_t B, int normalize, const void* blob, size_t blob_bytes,
                            float* out, float* latent, uint8_t* valid, void* stream) {
-  int mode = 0;
-  if (int rc = check_blob_args(B, NLML_F_REFERENCE, blob, blob_bytes, out, &mode)) return rc;
-  if (B > 0 && !raw) return fail(NLML_E_BADARG, "landmarks_to_pose: null raw");
-  if (mode == NLML_MODE_BF16)
-    return launch_encoder_heads_bf16(nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, out, latent, valid, stream);
-  if (split_f16(mode))
-    return launch_encoder_heads_f16x2(nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, out, latent, valid,
-                                      mode == NLML_MODE_F16X2S, stream);
-  return launch_encoder_heads_f32(nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, out, latent, valid, nullptr, nullptr, stream);
+  return k2_forward(K2_FUSED, true, nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, nullptr, 0, stream);
 }
 
-// ---- split-f16 mode, one launch per layer (small batches) -------------------------------------------------------
 size_t nlml_encoder_heads_small_workspace_bytes(int64_t B, int F) { return small_workspace_bytes(B, F); }
-
-static int check_small(int64_t B, int F, const void* blob, size_t blob_bytes, const float* out, int* split) {
-  int mode = 0;
-  if (int rc = check_blob_args(B, F, blob, blob_bytes, out, &mode)) return rc;
-  if (!split_f16(mode)) return fail(NLML_E_BADARG, "small-batch path: NLML_MODE_F16X2 / NLML_MODE_F16X2S blob only");
-  *split = mode == NLML_MODE_F16X2S;
-  return 0;
-}
 
 int nlml_encoder_heads_fwd_small(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
                                  float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
-  int split = 0;
-  if (int rc = check_small(B, F, blob, blob_bytes, out, &split)) return rc;
-  if (B > 0 && (!x || ldx < F)) return fail(NLML_E_BADARG, "encoder_heads: null x or ldx < F");
-  return launch_encoder_heads_f16x2_small(x, ldx, nullptr, 0, B, F, blob, out, latent, valid, workspace, ws_bytes, split, stream);
+  return k2_forward(K2_SMALL, false, x, ldx, nullptr, 0, B, F, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
 }
 
 int nlml_landmarks_to_pose_small(const float* raw, int64_t B, int normalize, const void* blob, size_t blob_bytes,
                                  float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
-  int split = 0;
-  if (int rc = check_small(B, NLML_F_REFERENCE, blob, blob_bytes, out, &split)) return rc;
-  if (B > 0 && !raw) return fail(NLML_E_BADARG, "landmarks_to_pose: null raw");
-  return launch_encoder_heads_f16x2_small(nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, out, latent, valid, workspace,
-                                          ws_bytes, split, stream);
+  return k2_forward(K2_SMALL, true, nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
 }
 
-// ---- strict-fast mode, LARGE batches: trunk launch + streamed tail launch (encoder_heads_f16x2_w8.hip TRUNK, encoder_heads_f16x2_tailws.hip) ----
-static int check_streamed(int64_t B, int F, const void* blob, size_t blob_bytes, const float* out) {
-  int mode = 0;
-  if (int rc = check_blob_args(B, F, blob, blob_bytes, out, &mode)) return rc;
-  if (mode != NLML_MODE_F16X2S) return fail(NLML_E_BADARG, "streamed-tail path: NLML_MODE_F16X2S blob only");
-  return 0;
-}
 int nlml_encoder_heads_fwd_streamed(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
                                     float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
-  if (int rc = check_streamed(B, F, blob, blob_bytes, out)) return rc;
-  if (B > 0 && (!x || ldx < F)) return fail(NLML_E_BADARG, "encoder_heads: null x or ldx < F");
-  return launch_encoder_heads_f16x2_tailws(x, ldx, nullptr, 0, B, F, blob, out, latent, valid, workspace, ws_bytes, stream);
+  return k2_forward(K2_STREAMED, false, x, ldx, nullptr, 0, B, F, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
 }
 
 int nlml_landmarks_to_pose_streamed(const float* raw, int64_t B, int normalize, const void* blob, size_t blob_bytes,
                                     float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
-  if (int rc = check_streamed(B, NLML_F_REFERENCE, blob, blob_bytes, out)) return rc;
-  if (B > 0 && !raw) return fail(NLML_E_BADARG, "landmarks_to_pose: null raw");
-  return launch_encoder_heads_f16x2_tailws(nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, out, latent, valid, workspace,
-                                           ws_bytes, stream);
-}
-
-// ---- the forward with a caller-provided workspace: the fastest path for the batch size and the blob's mode -------------------------
-// (measured crossovers, tools/k2_crossover.py and bench.py extra.k2_batch_sweep)
-static const int64_t kSmallMax = 4096;     // split-f16 modes: up to here the layer-per-launch path over 64-face tiles
-// The trunk + streamed-tail path (encoder_heads_f16x2_tailws.hip) is bit-identical to the fused kernel and measured 1.4-2.2 % faster at 65,536
-// faces (0.801 against 0.815 ms, same box, alternating; DESIGN.md section 3) -- inside the box-to-box spread, for a 64 MB workspace and a
-// second big launch -- so the dispatcher does not pick it by itself.  NLML_K2_STREAMED_MIN=<faces> routes batches from that size
-// on through it (the explicit _streamed entry points always do).
-static int64_t streamed_min() {
-  static const int64_t v = [] { const char* e = getenv("NLML_K2_STREAMED_MIN"); return e && e[0] ? (int64_t)atoll(e) : (int64_t)-1; }();
-  return v;
+  return k2_forward(K2_STREAMED, true, nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
 }
 
 size_t nlml_encoder_heads_workspace_bytes(int64_t B, int F) {
@@ -161,30 +160,14 @@ size_t nlml_encoder_heads_workspace_bytes(int64_t B, int F) {
   return a > b ? a : b;
 }
 
-static int fwd_ws(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F, const void* blob, size_t blob_bytes,
-                  float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
-  int mode = 0;
-  if (int rc = check_blob_args(B, F, blob, blob_bytes, out, &mode)) return rc;
-  if (B > 0 && !raw && (!x || ldx < F)) return fail(NLML_E_BADARG, "encoder_heads: null x or ldx < F");
-  if (mode == NLML_MODE_BF16) return launch_encoder_heads_bf16(x, ldx, raw, normalize, B, F, blob, out, latent, valid, stream);
-  if (!split_f16(mode)) return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, blob, out, latent, valid, nullptr, nullptr, stream);
-  const int split = mode == NLML_MODE_F16X2S;
-  if (B <= kSmallMax)
-    return launch_encoder_heads_f16x2_small(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, split, stream);
-  if (split && streamed_min() >= 0 && B >= streamed_min() && tailws_supported(raw ? raw : x, raw ? NLML_F_REFERENCE : ldx, F))
-    return launch_encoder_heads_f16x2_tailws(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, stream);
-  return launch_encoder_heads_f16x2(x, ldx, raw, normalize, B, F, blob, out, latent, valid, split, stream);
-}
-
 int nlml_encoder_heads_fwd_ws(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
                               float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
-  return fwd_ws(x, ldx, nullptr, 0, B, F, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
+  return k2_forward(K2_AUTO, false, x, ldx, nullptr, 0, B, F, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
 }
 
 int nlml_landmarks_to_pose_ws(const float* raw, int64_t B, int normalize, const void* blob, size_t blob_bytes,
                               float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
-  if (B > 0 && !raw) return fail(NLML_E_BADARG, "landmarks_to_pose: null raw");
-  return fwd_ws(nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
+  return k2_forward(K2_AUTO, true, nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
 }
 
 // The matrix-core order reads Wm and the x rows with 16-byte vector loads (tucker_common.h load11 / tucker_few)

@@ -3,12 +3,39 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/nlml_hpe.h"
 
 namespace nlml {
 
 // Records msg in the thread-local error slot and returns code (never 0).
 int fail(int code, const char* msg);
+// The tail of every launcher: 0, or the pending HIP launch error recorded through fail() (abi.cpp).
+int hip_launch_status();
+
+// ---- K2 (encoder + heads): what every launcher shares --------------------------------------------------------------------
+// The rows a K2 kernel reads.  `raw` given: the landmarks [B,468,3] themselves, row stride 1404 (without normalisation they ARE the
+// feature rows); else x with row stride ldx.  vec4: rows may be read with 16-byte loads.
+struct K2Input { const float* src; int64_t ld; int norm; bool vec4; };
+inline K2Input k2_input(const float* x, int64_t ldx, const float* raw, int normalize, int F) {
+  K2Input a;
+  if (raw) {
+    a.src = raw; a.ld = NLML_F_REFERENCE; a.norm = normalize ? 1 : 0;
+  } else {
+    a.src = x; a.ld = ldx; a.norm = 0;
+  }
+  a.vec4 = (F % 4 == 0) && (a.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.src) & 15) == 0);
+  return a;
+}
+// The <VEC4, NORM> kernel instance of an input: calls fn(std::bool_constant<VEC4>{}, std::bool_constant<NORM>{}).
+template <class Fn> void k2_with_variant(const K2Input& in, Fn&& fn) {
+  if (in.norm) {
+    if (in.vec4) fn(std::true_type{}, std::true_type{}); else fn(std::false_type{}, std::true_type{});
+  } else {
+    if (in.vec4) fn(std::true_type{}, std::false_type{}); else fn(std::false_type{}, std::false_type{});
+  }
+}
 
 // pack.cpp
 size_t blob_bytes_for(int F, int mode);
@@ -23,6 +50,9 @@ int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int 
                              int reeval_over = -1);   // >= 0: re-evaluation launch behind a split-f16 one (encoder_heads.hip)
 // the f32 image inside an NLML_MODE_F16X2S blob (pack.cpp): byte offset from the blob's start
 size_t strict_f32_image_offset(int F);
+// the strict-fast mode's re-evaluation launch behind its split-f16 kernels (fused, streamed, layer-per-launch): the f32 kernel on that image
+int launch_strict_reeval(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F, const void* blob,
+                         float* out, float* latent, void* stream);
 // faces of a tile the strict-fast kernels re-evaluate themselves on the vector ALUs (as NLML_MODE_F16X2 does); a tile with more goes
 // to the f32 re-evaluation launch.  0: every face beyond f16's range is re-evaluated on the f32 matrix cores -- one rule, one
 // accuracy class (the strict parity kernel's bits), and no slow-path code inside the strict kernels.
@@ -41,7 +71,6 @@ int launch_encoder_heads_f16x2_w8(const float* x, int64_t ldx, const float* raw,
 // the same forward as TWO launches (+ the re-evaluation launch): the trunk (layers 0-2, the eight-wave kernel ending with layer 2's output
 // in `workspace`) and the streamed tail (encoder_heads_f16x2_tailws.hip: layers E3.. and the heads with the weights through LDS once per
 // 256 faces); bit-identical to the fused kernel
-bool tailws_supported(const float* x, int64_t ldx, int F);
 size_t tailws_workspace_bytes(int64_t B, int F);
 int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
                                       const void* blob, float* out, float* latent, uint8_t* valid, void* workspace,

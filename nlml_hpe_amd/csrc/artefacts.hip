@@ -59,16 +59,14 @@ int launch_cosine_table(const float* angles, int64_t n, const double* cos_params
   const int64_t total = n * R;
   hipLaunchKernelGGL(cosine_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), angles, n, cos_params, R, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
 }
 
 int launch_mode5_product(const float* core, const float* U, int Q, int R5, int M, float* W, void* stream) {
   if (Q == 0 || M == 0) return 0;
   hipLaunchKernelGGL(mode5_product_kernel, dim3((unsigned)((M + 15) / 16), (unsigned)((Q + 15) / 16)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), core, U, Q, R5, M, W);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
 }
 
 }  // namespace nlml

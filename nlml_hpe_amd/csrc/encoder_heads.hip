@@ -880,16 +880,10 @@ int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int 
   a.pre_tanh = pre_tanh;
   a.stamps = stamps;
   const bool dbg = pre_tanh || stamps;
-  a.norm = 0;
-  if (raw) {  // raw landmarks [B,468,3]; without normalisation they ARE the feature rows
-    a.x = raw;
-    a.ldx = NLML_F_REFERENCE;
-    a.norm = normalize ? 1 : 0;
-  } else {
-    a.x = x;
-    a.ldx = ldx;
-  }
-  const bool vec4 = (F % 4 == 0) && (a.ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0);
+  const K2Input in = k2_input(x, ldx, raw, normalize, F);
+  a.x = in.src;
+  a.ldx = in.ld;
+  a.norm = in.norm;
   // 64-face tiles halve the weight stream per face (a 64-face tile takes ~1.9x a 32-face tile, measured), but the
   // launch lasts whole ROUNDS of tiles over the 256 CUs (one tile per CU, LDS-bound): pick the tiling whose
   // rounds x tile time is smaller, so small batches and awkward tile counts (257 tiles = 2 rounds) do not pay for it.
@@ -898,22 +892,24 @@ int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int 
   const int tile = wide ? 64 : 32;
   const dim3 grid((unsigned)((B + tile - 1) / tile)), block(256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define NLML_LAUNCH(V, N, D)                                                                          \
-  do {                                                                                                \
-    if (wide) hipLaunchKernelGGL((encoder_heads_f32_kernel<V, N, D, 2>), grid, block, 0, st, a);      \
-    else hipLaunchKernelGGL((encoder_heads_f32_kernel<V, N, D, 1>), grid, block, 0, st, a);           \
-  } while (0)
   if (dbg) {
-    if (a.norm || !vec4) return fail(NLML_E_BADARG, "debug build: features input, F % 4 == 0 only");
+    if (in.norm || !in.vec4) return fail(NLML_E_BADARG, "debug build: features input, F % 4 == 0 only");
     hipLaunchKernelGGL((encoder_heads_f32_kernel<true, false, true, 2>), dim3((unsigned)((B + 63) / 64)), block, 0, st, a);
-  } else if (a.norm) {
-    if (vec4) NLML_LAUNCH(true, true, false); else NLML_LAUNCH(false, true, false);
   } else {
-    if (vec4) NLML_LAUNCH(true, false, false); else NLML_LAUNCH(false, false, false);
+    k2_with_variant(in, [&](auto V, auto N) {
+      if (wide) hipLaunchKernelGGL((encoder_heads_f32_kernel<decltype(V)::value, decltype(N)::value, false, 2>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((encoder_heads_f32_kernel<decltype(V)::value, decltype(N)::value, false, 1>), grid, block, 0, st, a);
+    });
   }
-#undef NLML_LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
+}
+
+// tiles with faces beyond f16's range (more than STRICT_INKERNEL_RESCUE_MAX = 0 of them): the whole tile again on the f32 matrix cores, from the
+// f32 image behind the split-f16 one; every other tile of that launch ends after one 768-byte read
+int launch_strict_reeval(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F, const void* blob,
+                         float* out, float* latent, void* stream) {
+  return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, static_cast<const char*>(blob) + strict_f32_image_offset(F), out, latent,
+                                  nullptr, nullptr, nullptr, stream, STRICT_INKERNEL_RESCUE_MAX);
 }
 
 }  // namespace nlml

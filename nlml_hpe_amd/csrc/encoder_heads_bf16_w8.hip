@@ -240,24 +240,15 @@ int launch_encoder_heads_bf16(const float* x, int64_t ldx, const float* raw, int
                               const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
   if (B == 0) return 0;
   bf::w8::Args a;
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid; a.norm = 0;
-  if (raw) {
-    a.x = raw; a.ldx = NLML_F_REFERENCE; a.norm = normalize ? 1 : 0;
-  } else {
-    a.x = x; a.ldx = ldx;
-  }
-  const bool vec4 = (F % 4 == 0) && (a.ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0);
+  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid;
+  const K2Input in = k2_input(x, ldx, raw, normalize, F);
+  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
   const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a.norm) {
-    if (vec4) hipLaunchKernelGGL((bf::w8::encoder_heads_bf16_w8_kernel<true, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((bf::w8::encoder_heads_bf16_w8_kernel<false, true>), grid, block, 0, st, a);
-  } else {
-    if (vec4) hipLaunchKernelGGL((bf::w8::encoder_heads_bf16_w8_kernel<true, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((bf::w8::encoder_heads_bf16_w8_kernel<false, false>), grid, block, 0, st, a);
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  k2_with_variant(in, [&](auto V, auto N) {
+    hipLaunchKernelGGL((bf::w8::encoder_heads_bf16_w8_kernel<decltype(V)::value, decltype(N)::value>), grid, block, 0, st, a);
+  });
+  return hip_launch_status();
 }
 
 }  // namespace nlml

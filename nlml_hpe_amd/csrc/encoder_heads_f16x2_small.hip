@@ -18,7 +18,6 @@
 //   64*tile + 32*fb + (lane&31).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "../../include/nlml_hpe.h"
@@ -504,15 +503,13 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
   h8* bufA = reinterpret_cast<h8*>(workspace);
   h8* bufB = bufA + (size_t)ntiles * buf_steps * STEP_UNITS;
 
-  const float* src = raw ? raw : x;
-  const int64_t sld = raw ? NLML_F_REFERENCE : ldx;
-  const bool vec4 = F % 4 == 0 && F >= 4 && sld % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-  if (vec4)
-    hipLaunchKernelGGL(prepass_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, src, sld, B, F,
-                       raw ? (normalize ? 1 : 0) : 0, k16, buf_steps, bufA, valid);
+  const K2Input rows = k2_input(x, ldx, raw, normalize, F);
+  if (rows.vec4)
+    hipLaunchKernelGGL(prepass_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, rows.src, rows.ld, B, F,
+                       rows.norm, k16, buf_steps, bufA, valid);
   else
-    hipLaunchKernelGGL(prepass_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, src, sld, B, F,
-                       raw ? (normalize ? 1 : 0) : 0, k16, buf_steps, bufA, valid);
+    hipLaunchKernelGGL(prepass_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, rows.src, rows.ld, B, F,
+                       rows.norm, k16, buf_steps, bufA, valid);
 
   // the three big layers: {stage, K16, blocks per job, jobs}; ReLU; job j covers output columns 32 * blocks * j ..
   struct S { int stage, K16, nb, jobs; };
@@ -549,8 +546,7 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
     constexpr int kMinUnits = 2048;   // measured: 8 waves per CU keep enough loads in flight (256 units: 153 us at B = 2,000; 2,048: 114 us)
     while (nbw > 1 && (int64_t)ntiles * a.jobs * (a.nb_stage / nbw) < kMinUnits) nbw >>= 1;
     const int64_t units = (int64_t)ntiles * a.jobs * (a.nb_stage / nbw);
-    static const bool fb_units = [] { const char* e = getenv("NLML_K2_SMALL_FB2"); return !(e && e[0] == '1'); }();   // A/B: =1 keeps both face blocks in a unit
-    if (fb_units && nbw == 1 && units <= 256) {   // (wider thresholds, 512 .. 4,096 units, measured: no change)   // at most one wave per CU even so: one unit per (.., face block), see layer_kernel
+    if (nbw == 1 && units <= 256) {   // (wider thresholds, 512 .. 4,096 units, measured: no change)   // at most one wave per CU even so: one unit per (.., face block), see layer_kernel
       const dim3 grid((unsigned)(2 * units)), block(64);
       if (!use_split) hipLaunchKernelGGL((layer_kernel<1, 8, 0, 1>), grid, block, 0, st, a);
       else if (a.split_from == 0) hipLaunchKernelGGL((layer_kernel<1, HXS_RS1, 1, 1>), grid, block, 0, st, a);
@@ -572,7 +568,7 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
   {
     hx::Args ta{};
     ta.B = B; ta.F = F; ta.blob = blob; ta.out = out; ta.latent = latent; ta.valid = nullptr;
-    ta.x = src; ta.ldx = sld; ta.norm = raw ? (normalize ? 1 : 0) : 0;   // the tail's slow path re-reads the face's input
+    ta.x = rows.src; ta.ldx = rows.ld; ta.norm = rows.norm;   // the tail's slow path re-reads the face's input
     if (split) {   // E3..E5, then the three heads as workgroups of their own; the latent image passes through the free buffer
       hipLaunchKernelGGL(hx::tail_encoder_kernel, dim3((unsigned)(2 * ntiles)), dim3(256), 0, st, ta, (const h8*)in, buf_steps, reinterpret_cast<char*>(outb));
       hipLaunchKernelGGL(hx::head_kernel, dim3((unsigned)(6 * ntiles)), dim3(256), 0, st, ta, reinterpret_cast<const char*>(outb));
@@ -580,12 +576,9 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
       hipLaunchKernelGGL(tail_kernel<64>, dim3((unsigned)(2 * ntiles)), dim3(256), 0, st, ta, (const h8*)in, buf_steps);
     }
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-  if (split)   // the strict-fast mode's f32 re-evaluation launch, as behind its fused kernel (encoder_heads_f16x2_w8.hip)
-    return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, static_cast<const char*>(blob) + strict_f32_image_offset(F), out, latent,
-                                    nullptr, nullptr, nullptr, stream, STRICT_INKERNEL_RESCUE_MAX);
-  return 0;
+  if (int rc = hip_launch_status()) return rc;
+  // the strict-fast mode's f32 re-evaluation launch, as behind its fused kernel (encoder_heads_f16x2_w8.hip)
+  return split ? launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream) : 0;
 }
 
 }  // namespace nlml

@@ -427,9 +427,7 @@ int launch_tail_ws(const void* blob, const void* h3, int64_t nfb, int64_t B, flo
   hx::TwArgs a;
   a.blob = blob; a.h3 = reinterpret_cast<const hx::u4*>(h3); a.out = out; a.latent = latent; a.B = B; a.nfb = nfb;
   hipLaunchKernelGGL(hx::tail_ws_kernel, dim3((unsigned)((nfb + 7) / 8)), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-  return 0;
+  return hip_launch_status();
 }
 
 }  // namespace nlml

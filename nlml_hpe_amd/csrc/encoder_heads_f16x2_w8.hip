@@ -493,9 +493,6 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
 }  // namespace hx
 
 // ---- the strict-fast forward as trunk launch + streamed tail launch (+ the f32 re-evaluation launch) -------------------------------
-bool tailws_supported(const float* x, int64_t ldx, int F) {
-  return (F % 4 == 0) && (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-}
 size_t tailws_workspace_bytes(int64_t B, int F) {
   if (B <= 0 || F <= 0) return 0;
   return (size_t)((B + TILE_FACES - 1) / TILE_FACES) * (2 * 16 * 2 * 1024);   // 1 KB per face of whole 64-face tiles
@@ -508,51 +505,34 @@ int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* 
   if (!workspace || ws_bytes < tailws_workspace_bytes(B, F)) return fail(NLML_E_BADARG, "streamed-tail path: workspace too small");
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(NLML_E_BADARG, "streamed-tail path: workspace must be 16-byte aligned");
   hx::Args a;
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid; a.norm = 0; a.h3ws = workspace;
-  if (raw) {
-    a.x = raw; a.ldx = NLML_F_REFERENCE; a.norm = normalize ? 1 : 0;
-  } else {
-    a.x = x; a.ldx = ldx;
-  }
-  if (!tailws_supported(a.x, a.ldx, F)) return fail(NLML_E_BADARG, "streamed-tail path: x must be 16-byte aligned with F and ldx multiples of 4");
+  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid; a.h3ws = workspace;
+  const K2Input in = k2_input(x, ldx, raw, normalize, F);
+  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
+  if (!in.vec4) return fail(NLML_E_BADARG, "streamed-tail path: x must be 16-byte aligned with F and ldx multiples of 4");
   const int64_t ntiles = (B + TILE_FACES - 1) / TILE_FACES;
   const dim3 grid((unsigned)ntiles), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (a.norm) hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<true, true, true>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<true, false, true>), grid, block, 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
+  if (int rc = hip_launch_status()) return rc;
   if (int rc = launch_tail_ws(blob, workspace, 2 * ntiles, B, out, latent, stream)) return rc;
-  return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, static_cast<const char*>(blob) + strict_f32_image_offset(F), out, latent,
-                                  nullptr, nullptr, nullptr, stream, STRICT_INKERNEL_RESCUE_MAX);
+  return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
 }
 
 int launch_encoder_heads_f16x2_w8(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
                                   const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
   if (B == 0) return 0;
   hx::Args a;
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid; a.norm = 0;
-  if (raw) {
-    a.x = raw; a.ldx = NLML_F_REFERENCE; a.norm = normalize ? 1 : 0;
-  } else {
-    a.x = x; a.ldx = ldx;
-  }
-  const bool vec4 = (F % 4 == 0) && (a.ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0);
+  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid;
+  const K2Input in = k2_input(x, ldx, raw, normalize, F);
+  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
   const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a.norm) {
-    if (vec4) hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<true, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<false, true>), grid, block, 0, st, a);
-  } else {
-    if (vec4) hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<true, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<false, false>), grid, block, 0, st, a);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
-  // tiles with faces beyond f16's range (more than STRICT_INKERNEL_RESCUE_MAX = 0 of them): the whole tile again on the f32 matrix cores, from the
-  // f32 image behind the split-f16 one; every other tile of that launch ends after one 768-byte read (encoder_heads.hip)
-  return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, static_cast<const char*>(blob) + strict_f32_image_offset(F), out, latent,
-                                  nullptr, nullptr, nullptr, stream, STRICT_INKERNEL_RESCUE_MAX);
+  k2_with_variant(in, [&](auto V, auto N) {
+    hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<decltype(V)::value, decltype(N)::value>), grid, block, 0, st, a);
+  });
+  if (int rc = hip_launch_status()) return rc;
+  return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
 }
 
 }  // namespace nlml

@@ -89,8 +89,7 @@ int launch_normalize_ipd(const float* raw, int64_t B, int normalize, float* out,
   const dim3 grid((unsigned)((B + 3) / 4)), block(256);
   hipLaunchKernelGGL(normalize_ipd_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), raw, B,
                      normalize, out, valid);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
 }
 
 }  // namespace nlml

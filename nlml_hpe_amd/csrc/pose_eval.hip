@@ -289,8 +289,7 @@ int launch_pose_eval(const float* pose_rad, const double* pred_deg, const uint8_
   if (nrec > 0) {
     hipLaunchKernelGGL(pose_eval_records, dim3((unsigned)nrec), dim3(kThreads), 0, s, pose_rad, pred_deg, valid, gt_deg, B, args,
                        workspace, pred_out, keep_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
+    if (int rc = hip_launch_status()) return rc;
   }
   return launch_pose_eval_merge(workspace, nrec, args.K, record_out, result_out, stream);
 }
@@ -298,8 +297,7 @@ int launch_pose_eval(const float* pose_rad, const double* pred_deg, const uint8_
 int launch_pose_eval_merge(const double* records, int64_t n, int K, double* record_out, double* result_out, void* stream) {
   hipLaunchKernelGGL(pose_eval_merge_kernel, dim3(1), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), records, n, K,
                      record_out, result_out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
 }
 
 }  // namespace nlml

@@ -72,98 +72,70 @@ at::Tensor normalize_ipd(const at::Tensor& raw_, bool normalize) {
   return out;
 }
 
-at::Tensor encoder_heads_fwd(const at::Tensor& x_, const at::Tensor& blob, int64_t F) {
-  need(x_, "x", at::kFloat);
+// The K2 forwards: the checks, the allocation and the call behind the five forward ops and landmarks_to_pose_valid.  in_ is the raw
+// landmarks [B,468,3] (landmarks) or the feature rows [B,F]; ws given = the layer-per-launch path through that workspace, else the fused
+// launch; want_valid adds the "a face was found" mask u8[B] (row not all-zero).
+struct K2Out { at::Tensor pose, valid; };
+K2Out k2_forward(const at::Tensor& in_, bool landmarks, const at::Tensor& blob, int64_t F, bool normalize, const at::Tensor* ws,
+                 bool want_valid) {
+  need(in_, landmarks ? "raw" : "x", at::kFloat);
   need(blob, "packed_w", at::kByte);
   need_dense(blob, "packed_w");
-  same_device(x_, blob, "packed_w");
-  TORCH_CHECK(x_.dim() == 2 && x_.size(1) == F, "x: expected [B,", F, "], got ", x_.sizes());
-  const at::Tensor x = x_.stride(1) == 1 ? x_ : x_.contiguous();
-  const int64_t B = x.size(0), ldx = B > 1 ? x.stride(0) : F;
-  at::Tensor out = at::empty({B, 3}, x.options());
-  OnDevice dev(x);
-  check(nlml_encoder_heads_fwd(x.data_ptr<float>(), ldx, B, (int)F, blob.data_ptr(), (size_t)blob.numel(), out.data_ptr<float>(),
-                               nullptr, nullptr, dev.stream), "nlml_encoder_heads_fwd");
-  return out;
-}
-
-at::Tensor landmarks_to_pose(const at::Tensor& raw_, const at::Tensor& blob, bool normalize) {
-  need(raw_, "raw", at::kFloat);
-  need(blob, "packed_w", at::kByte);
-  need_dense(blob, "packed_w");
-  same_device(raw_, blob, "packed_w");
-  TORCH_CHECK(raw_.dim() == 3 && raw_.size(1) == 468 && raw_.size(2) == 3, "raw: expected [B,468,3], got ", raw_.sizes());
-  const at::Tensor raw = raw_.contiguous();
-  const int64_t B = raw.size(0);
-  at::Tensor out = at::empty({B, 3}, raw.options());
-  OnDevice dev(raw);
-  check(nlml_landmarks_to_pose(raw.data_ptr<float>(), B, normalize ? 1 : 0, blob.data_ptr(), (size_t)blob.numel(),
-                               out.data_ptr<float>(), nullptr, nullptr, dev.stream), "nlml_landmarks_to_pose");
-  return out;
-}
-
-at::Tensor encoder_heads_fwd_small(const at::Tensor& x_, const at::Tensor& blob, int64_t F, const at::Tensor& ws) {
-  need(x_, "x", at::kFloat);
-  need(blob, "packed_w", at::kByte);
-  need_dense(blob, "packed_w");
-  need(ws, "workspace", at::kByte);
-  need_dense(ws, "workspace");
-  same_device(x_, blob, "packed_w");
-  same_device(x_, ws, "workspace");
-  TORCH_CHECK(x_.dim() == 2 && x_.size(1) == F, "x: expected [B,", F, "], got ", x_.sizes());
-  const at::Tensor x = x_.stride(1) == 1 ? x_ : x_.contiguous();
-  const int64_t B = x.size(0), ldx = B > 1 ? x.stride(0) : F;
-  at::Tensor out = at::empty({B, 3}, x.options());
-  OnDevice dev(x);
-  check(nlml_encoder_heads_fwd_small(x.data_ptr<float>(), ldx, B, (int)F, blob.data_ptr(), (size_t)blob.numel(), out.data_ptr<float>(),
-                                     nullptr, nullptr, ws.data_ptr(), (size_t)ws.numel(), dev.stream), "nlml_encoder_heads_fwd_small");
-  return out;
-}
-
-at::Tensor landmarks_to_pose_small(const at::Tensor& raw_, const at::Tensor& blob, bool normalize, const at::Tensor& ws) {
-  need(raw_, "raw", at::kFloat);
-  need(blob, "packed_w", at::kByte);
-  need_dense(blob, "packed_w");
-  need(ws, "workspace", at::kByte);
-  need_dense(ws, "workspace");
-  same_device(raw_, blob, "packed_w");
-  same_device(raw_, ws, "workspace");
-  TORCH_CHECK(raw_.dim() == 3 && raw_.size(1) == 468 && raw_.size(2) == 3, "raw: expected [B,468,3], got ", raw_.sizes());
-  const at::Tensor raw = raw_.contiguous();
-  const int64_t B = raw.size(0);
-  at::Tensor out = at::empty({B, 3}, raw.options());
-  OnDevice dev(raw);
-  check(nlml_landmarks_to_pose_small(raw.data_ptr<float>(), B, normalize ? 1 : 0, blob.data_ptr(), (size_t)blob.numel(),
-                                     out.data_ptr<float>(), nullptr, nullptr, ws.data_ptr(), (size_t)ws.numel(), dev.stream),
-        "nlml_landmarks_to_pose_small");
-  return out;
-}
-
-// the video tick's forward: pose AND the "a face was found" mask (row not all-zero) in one call; `ws` empty = the fused launch,
-// else the layer-per-launch path through that workspace
-std::tuple<at::Tensor, at::Tensor> landmarks_to_pose_valid(const at::Tensor& raw_, const at::Tensor& blob, bool normalize,
-                                                           const std::optional<at::Tensor>& ws) {
-  need(raw_, "raw", at::kFloat);
-  need(blob, "packed_w", at::kByte);
-  need_dense(blob, "packed_w");
-  same_device(raw_, blob, "packed_w");
-  TORCH_CHECK(raw_.dim() == 3 && raw_.size(1) == 468 && raw_.size(2) == 3, "raw: expected [B,468,3], got ", raw_.sizes());
-  const at::Tensor raw = raw_.contiguous();
-  const int64_t B = raw.size(0);
-  at::Tensor out = at::empty({B, 3}, raw.options()), valid = at::empty({B}, raw.options().dtype(at::kByte));
-  OnDevice dev(raw);
-  if (ws.has_value()) {
+  if (ws) {
     need(*ws, "workspace", at::kByte);
     need_dense(*ws, "workspace");
-    same_device(raw_, *ws, "workspace");
-    check(nlml_landmarks_to_pose_small(raw.data_ptr<float>(), B, normalize ? 1 : 0, blob.data_ptr(), (size_t)blob.numel(),
-                                       out.data_ptr<float>(), nullptr, valid.data_ptr<uint8_t>(), ws->data_ptr(), (size_t)ws->numel(),
-                                       dev.stream), "nlml_landmarks_to_pose_small");
-  } else {
-    check(nlml_landmarks_to_pose(raw.data_ptr<float>(), B, normalize ? 1 : 0, blob.data_ptr(), (size_t)blob.numel(),
-                                 out.data_ptr<float>(), nullptr, valid.data_ptr<uint8_t>(), dev.stream), "nlml_landmarks_to_pose");
   }
-  return {out, valid};
+  same_device(in_, blob, "packed_w");
+  if (ws) same_device(in_, *ws, "workspace");
+  if (landmarks) {
+    TORCH_CHECK(in_.dim() == 3 && in_.size(1) == 468 && in_.size(2) == 3, "raw: expected [B,468,3], got ", in_.sizes());
+  } else {
+    TORCH_CHECK(in_.dim() == 2 && in_.size(1) == F, "x: expected [B,", F, "], got ", in_.sizes());
+  }
+  const at::Tensor in = !landmarks && in_.stride(1) == 1 ? in_ : in_.contiguous();
+  const int64_t B = in.size(0);
+  K2Out r{at::empty({B, 3}, in.options()), want_valid ? at::empty({B}, in.options().dtype(at::kByte)) : at::Tensor()};
+  uint8_t* const valid = want_valid ? r.valid.data_ptr<uint8_t>() : nullptr;
+  float* const out = r.pose.data_ptr<float>();
+  const size_t blob_bytes = (size_t)blob.numel();
+  OnDevice dev(in);
+  if (landmarks) {
+    const int norm = normalize ? 1 : 0;
+    if (ws)
+      check(nlml_landmarks_to_pose_small(in.data_ptr<float>(), B, norm, blob.data_ptr(), blob_bytes, out, nullptr, valid, ws->data_ptr(),
+                                         (size_t)ws->numel(), dev.stream), "nlml_landmarks_to_pose_small");
+    else
+      check(nlml_landmarks_to_pose(in.data_ptr<float>(), B, norm, blob.data_ptr(), blob_bytes, out, nullptr, valid, dev.stream),
+            "nlml_landmarks_to_pose");
+  } else {
+    const int64_t ldx = B > 1 ? in.stride(0) : F;
+    if (ws)
+      check(nlml_encoder_heads_fwd_small(in.data_ptr<float>(), ldx, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr, valid,
+                                         ws->data_ptr(), (size_t)ws->numel(), dev.stream), "nlml_encoder_heads_fwd_small");
+    else
+      check(nlml_encoder_heads_fwd(in.data_ptr<float>(), ldx, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr, valid, dev.stream),
+            "nlml_encoder_heads_fwd");
+  }
+  return r;
+}
+
+at::Tensor encoder_heads_fwd(const at::Tensor& x, const at::Tensor& blob, int64_t F) {
+  return k2_forward(x, false, blob, F, false, nullptr, false).pose;
+}
+at::Tensor landmarks_to_pose(const at::Tensor& raw, const at::Tensor& blob, bool normalize) {
+  return k2_forward(raw, true, blob, F_REF, normalize, nullptr, false).pose;
+}
+at::Tensor encoder_heads_fwd_small(const at::Tensor& x, const at::Tensor& blob, int64_t F, const at::Tensor& ws) {
+  return k2_forward(x, false, blob, F, false, &ws, false).pose;
+}
+at::Tensor landmarks_to_pose_small(const at::Tensor& raw, const at::Tensor& blob, bool normalize, const at::Tensor& ws) {
+  return k2_forward(raw, true, blob, F_REF, normalize, &ws, false).pose;
+}
+// the video tick's forward: pose AND the face mask in one call; `ws` empty = the fused launch
+std::tuple<at::Tensor, at::Tensor> landmarks_to_pose_valid(const at::Tensor& raw, const at::Tensor& blob, bool normalize,
+                                                           const std::optional<at::Tensor>& ws) {
+  K2Out r = k2_forward(raw, true, blob, F_REF, normalize, ws.has_value() ? &*ws : nullptr, true);
+  return {r.pose, r.valid};
 }
 
 void check_td(const at::Tensor& Wm, const at::Tensor& x, const at::Tensor& cosp) {
@@ -309,10 +281,7 @@ std::tuple<at::Tensor, at::Tensor> pose_eval_merge(const at::Tensor& records_, i
 
 // ---- shapes only (Meta backend: tracing / fake tensors) -------------------------------------------------------------
 at::Tensor normalize_ipd_meta(const at::Tensor& raw, bool) { return at::empty({raw.size(0), F_REF}, raw.options()); }
-at::Tensor pose_meta3(const at::Tensor& x, const at::Tensor&, int64_t) { return at::empty({x.size(0), 3}, x.options()); }
-at::Tensor pose_metab(const at::Tensor& x, const at::Tensor&, bool) { return at::empty({x.size(0), 3}, x.options()); }
-at::Tensor pose_meta3w(const at::Tensor& x, const at::Tensor&, int64_t, const at::Tensor&) { return at::empty({x.size(0), 3}, x.options()); }
-at::Tensor pose_metabw(const at::Tensor& x, const at::Tensor&, bool, const at::Tensor&) { return at::empty({x.size(0), 3}, x.options()); }
+template <class... Rest> at::Tensor pose_meta(const at::Tensor& x, const at::Tensor&, Rest...) { return at::empty({x.size(0), 3}, x.options()); }
 at::Tensor tucker_objective_meta(const at::Tensor&, const at::Tensor&, const at::Tensor& params, const at::Tensor&, std::string) {
   return at::empty({params.size(0)}, params.options());
 }
@@ -375,10 +344,10 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
 
 TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("normalize_ipd", &normalize_ipd_meta);
-  m.impl("encoder_heads_fwd", &pose_meta3);
-  m.impl("landmarks_to_pose", &pose_metab);
-  m.impl("encoder_heads_fwd_small", &pose_meta3w);
-  m.impl("landmarks_to_pose_small", &pose_metabw);
+  m.impl("encoder_heads_fwd", &pose_meta<int64_t>);
+  m.impl("landmarks_to_pose", &pose_meta<bool>);
+  m.impl("encoder_heads_fwd_small", &pose_meta<int64_t, const at::Tensor&>);
+  m.impl("landmarks_to_pose_small", &pose_meta<bool, const at::Tensor&>);
   m.impl("tucker_objective", &tucker_objective_meta);
   m.impl("landmarks_to_pose_valid", &pose_valid_meta);
   m.impl("tucker_powell", &tucker_powell_meta);

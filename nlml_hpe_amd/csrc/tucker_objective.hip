@@ -146,8 +146,7 @@ int launch_tucker_objective(const float* Wm, const float* x, int64_t ldx, const 
   else
   hipLaunchKernelGGL(tucker_objective_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), Wm, x, ldx,
                      x_index, params, cos_params, N, err, x_hat);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
 }
 
 }  // namespace nlml

@@ -249,8 +249,7 @@ int launch_tucker_powell(const float* Wm, const float* x, int64_t ldx, const dou
   else
   hipLaunchKernelGGL((tucker_powell_kernel<NLML_TD_ORDER_FAST>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), Wm, x, ldx,
                      cos_params, N, x0, result, fval, nfev, nit, status);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
 }
 
 }  // namespace nlml

@@ -76,8 +76,7 @@ int launch_video_post(const float* pose_rad, const float* raw, const uint8_t* va
   const dim3 grid((unsigned)((S + 63) / 64)), block(64);
   hipLaunchKernelGGL(video_post_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), pose_rad, raw, valid, S,
                      frame_w, frame_h, alpha, max_jump, size, state, smoothed, centre, endpoints, updated);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+  return hip_launch_status();
 }
 
 }  // namespace nlml

@@ -49,12 +49,16 @@ class _on_device_of:
         return self.guard.__exit__(*exc)
 
 
+def _raw_rows(raw: torch.Tensor) -> torch.Tensor:
+    if raw.dim() != 3 or raw.shape[1:] != (468, 3):
+        raise ValueError(f"raw: expected [B,468,3], got {tuple(raw.shape)}")
+    return raw.contiguous()
+
+
 def normalize_ipd(raw: torch.Tensor, normalize: bool = True, return_valid: bool = False):
     """raw f32[B,468,3] -> features f32[B,1404] (FeatureExtractor.py:30-66,101), bit-exact."""
     _need_cuda(raw, "raw", torch.float32)
-    if raw.dim() != 3 or raw.shape[1:] != (468, 3):
-        raise ValueError(f"raw: expected [B,468,3], got {tuple(raw.shape)}")
-    raw = raw.contiguous()
+    raw = _raw_rows(raw)
     B = raw.shape[0]
     out = torch.empty((B, F_REF), dtype=torch.float32, device=raw.device)
     valid = torch.empty((B,), dtype=torch.uint8, device=raw.device) if return_valid else None
@@ -65,31 +69,77 @@ def normalize_ipd(raw: torch.Tensor, normalize: bool = True, return_valid: bool 
     return (out, valid.bool()) if return_valid else out
 
 
-def encoder_heads_fwd(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
-                      return_valid: bool = False):
-    """x f32[B,F] -> radians f32[B,3] (CombinedAnglePredictionModel.forward, Model_Builder.py:115-126)."""
-    _need_cuda(x, "x", torch.float32)
-    _need_cuda(blob, "blob", torch.uint8)
-    if x.dim() != 2 or x.shape[1] != F:
-        raise ValueError(f"x: expected [B,{F}], got {tuple(x.shape)}")
-    if x.stride(1) != 1:
-        x = x.contiguous()
-    B = x.shape[0]
-    ldx = x.stride(0) if B > 1 else F
-    out = torch.empty((B, 3), dtype=torch.float32, device=x.device)
-    latent = torch.empty((B, LATENT), dtype=torch.float32, device=x.device) if return_latent else None
-    valid = torch.empty((B,), dtype=torch.uint8, device=x.device) if return_valid else None
-    with _on_device_of(("x", x), ("blob", blob)) as stream:
-        _lib.check(_lib.lib().nlml_encoder_heads_fwd(
-            x.data_ptr(), ldx, B, F, blob.data_ptr(), blob.numel(), out.data_ptr(),
+# ---- the K2 forward (encoder + heads): one private forward behind the five public wrappers ---------------------------------------
+_k2_ws: dict = {}
+
+
+def _k2_workspace(form: str, B: int, F: int, device, floor_faces: int = 0) -> torch.Tensor:
+    """Scratch of the K2 call forms that need one (its contents never matter).  Buffers are cached per form, device and stream and
+    NEVER released or replaced: a captured hipGraph keeps replaying into the pointer it was captured with, so growing means
+    adding a larger buffer next to the old one.  floor_faces: a new buffer holds at least that many faces of the reference width."""
+    size_of = _lib.lib().nlml_encoder_heads_small_workspace_bytes if form == "small" else _lib.lib().nlml_encoder_heads_workspace_bytes
+    need = max(16, size_of(B, F))
+    # one pool per (device, stream): launches on different streams may overlap and must not share scratch
+    pool = _k2_ws.setdefault((form, str(device), _stream_ptr(device)), [])
+    for ws in pool:
+        if ws.numel() >= need:
+            return ws
+    ws = torch.empty((max(need, size_of(floor_faces, F_REF)),), dtype=torch.uint8, device=device)
+    pool.append(ws)
+    return ws
+
+
+def _small_workspace(B: int, F: int, device) -> torch.Tensor:
+    """The layer-per-launch path's scratch; the first buffer is sized for 4,096 faces of the reference width (46 MB)."""
+    return _k2_workspace("small", B, F, device, floor_faces=4096)
+
+
+def _k2_forward(form: str, x, raw, blob: torch.Tensor, F: int, normalize, return_latent: bool, return_valid: bool, workspace=None):
+    """x f32[B,F] (raw None) or raw f32[B,468,3] (x None) -> out f32[B,3][, latent f32[B,9]][, valid bool[B]] through the C entry
+    point of the call form: "" (the fused kernel), "small" or "streamed" (both through a workspace, pooled unless given)."""
+    if raw is None:
+        _need_cuda(x, "x", torch.float32)
+        _need_cuda(blob, "blob", torch.uint8)
+        if x.dim() != 2 or x.shape[1] != F:
+            raise ValueError(f"x: expected [B,{F}], got {tuple(x.shape)}")
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        src, name, symbol = x, "x", "nlml_encoder_heads_fwd"
+        B = x.shape[0]
+        head = (x.data_ptr(), x.stride(0) if B > 1 else F, B, F)
+    else:
+        _need_cuda(raw, "raw", torch.float32)
+        _need_cuda(blob, "blob", torch.uint8)
+        src, name, symbol = _raw_rows(raw), "raw", "nlml_landmarks_to_pose"
+        B = src.shape[0]
+        head = (src.data_ptr(), B, int(bool(normalize)))
+    dev = src.device
+    tail = ()
+    if form:
+        symbol += "_" + form
+        if workspace is None:
+            workspace = _small_workspace(B, F, dev) if form == "small" else _k2_workspace(form, B, F, dev)
+        tail = (workspace.data_ptr(), workspace.numel())
+    out = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    latent = torch.empty((B, LATENT), dtype=torch.float32, device=dev) if return_latent else None
+    valid = torch.empty((B,), dtype=torch.uint8, device=dev) if return_valid else None
+    with _on_device_of((name, src), ("blob", blob), ("workspace", workspace)) as stream:
+        _lib.check(getattr(_lib.lib(), symbol)(
+            *head, blob.data_ptr(), blob.numel(), out.data_ptr(),
             latent.data_ptr() if latent is not None else None,
-            valid.data_ptr() if valid is not None else None, stream), "nlml_encoder_heads_fwd")
+            valid.data_ptr() if valid is not None else None, *tail, stream), symbol)
     res = [out]
     if return_latent:
         res.append(latent)
     if return_valid:
         res.append(valid.bool())
     return res[0] if len(res) == 1 else tuple(res)
+
+
+def encoder_heads_fwd(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
+                      return_valid: bool = False):
+    """x f32[B,F] -> radians f32[B,3] (CombinedAnglePredictionModel.forward, Model_Builder.py:115-126)."""
+    return _k2_forward("", x, None, blob, F, None, return_latent, return_valid)
 
 
 def encoder_heads_fwd_debug(x: torch.Tensor, blob: torch.Tensor, F: int, want_stamps: bool = False):
@@ -115,26 +165,7 @@ def encoder_heads_fwd_debug(x: torch.Tensor, blob: torch.Tensor, F: int, want_st
 def landmarks_to_pose(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
                       return_valid: bool = False):
     """Fused K1+K2: raw f32[B,468,3] -> radians f32[B,3]; normalised features never reach HBM."""
-    _need_cuda(raw, "raw", torch.float32)
-    _need_cuda(blob, "blob", torch.uint8)
-    if raw.dim() != 3 or raw.shape[1:] != (468, 3):
-        raise ValueError(f"raw: expected [B,468,3], got {tuple(raw.shape)}")
-    raw = raw.contiguous()
-    B = raw.shape[0]
-    out = torch.empty((B, 3), dtype=torch.float32, device=raw.device)
-    latent = torch.empty((B, LATENT), dtype=torch.float32, device=raw.device) if return_latent else None
-    valid = torch.empty((B,), dtype=torch.uint8, device=raw.device) if return_valid else None
-    with _on_device_of(("raw", raw), ("blob", blob)) as stream:
-        _lib.check(_lib.lib().nlml_landmarks_to_pose(
-            raw.data_ptr(), B, int(bool(normalize)), blob.data_ptr(), blob.numel(), out.data_ptr(),
-            latent.data_ptr() if latent is not None else None,
-            valid.data_ptr() if valid is not None else None, stream), "nlml_landmarks_to_pose")
-    res = [out]
-    if return_latent:
-        res.append(latent)
-    if return_valid:
-        res.append(valid.bool())
-    return res[0] if len(res) == 1 else tuple(res)
+    return _k2_forward("", None, raw, blob, F_REF, normalize, return_latent, return_valid)
 
 
 def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, cos_params: torch.Tensor,
@@ -180,9 +211,8 @@ def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, co
 # ---------------------------------------------------------------------------------------------
 # torch.ops.nlml_hpe.* (SURVEY.md 8b "Underlying op") come from COMPILED code: csrc/torch_ops.cpp, a TORCH_LIBRARY shim over the same
 # C ABI (shape / dtype checks, torch's allocator, the operand device's current stream), built next to this file as
-# libnlml_torch_ops.so by csrc/Makefile.  Registered: normalize_ipd, encoder_heads_fwd, landmarks_to_pose, encoder_heads_fwd_small,
-# landmarks_to_pose_small (explicit workspace), landmarks_to_pose_valid (pose + face mask: the video tick's forward), tucker_objective, tucker_powell, video_post, cosine_table.  GPU backend only: a CPU
-# tensor has no kernel to dispatch to and raises.  A missing library raises here -- the ops are part of the boundary.
+# libnlml_torch_ops.so by csrc/Makefile.  GPU backend only: a CPU tensor has no kernel to dispatch to and raises.  A missing library
+# raises here -- the ops are part of the boundary.
 import os as _os
 
 TORCH_OPS_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "libnlml_torch_ops.so")
@@ -194,6 +224,7 @@ def _load_torch_ops():
                              "(make -C nlml_hpe_amd/csrc); torch.ops.nlml_hpe.* are registered from it")
     _lib.lib()                                  # the C ABI library the shim links against, checked symbol by symbol first
     torch.ops.load_library(TORCH_OPS_PATH)
+    # the registered ops; *_small take an explicit workspace, landmarks_to_pose_valid is the video tick's forward (pose + face mask)
     for name in ("normalize_ipd", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_powell", "video_post", "cosine_table", "pose_eval",
                  "pose_eval_merge"):
@@ -277,84 +308,18 @@ def mode5_product(core: torch.Tensor, U_feat: torch.Tensor) -> torch.Tensor:
     return W.reshape(lead + (M,))
 
 
-_small_ws: dict = {}
-
-
-def _small_workspace(B: int, F: int, device) -> torch.Tensor:
-    """Scratch for the layer-per-launch path (its contents never matter).  Buffers are cached per device and stream and NEVER
-    released or replaced: a captured hipGraph keeps replaying into the pointer it was captured with, so growing means
-    adding a larger buffer next to the old one.  The first one is sized for 4,096 faces of the reference width (46 MB)."""
-    need = _lib.lib().nlml_encoder_heads_small_workspace_bytes(B, F)
-    # one pool per (device, stream): launches on different streams may overlap and must not share scratch
-    pool = _small_ws.setdefault((str(device), _stream_ptr(device)), [])
-    for ws in pool:
-        if ws.numel() >= need:
-            return ws
-    size = max(need, _lib.lib().nlml_encoder_heads_small_workspace_bytes(4096, F_REF))
-    ws = torch.empty((size,), dtype=torch.uint8, device=device)
-    pool.append(ws)
-    return ws
-
-
 def encoder_heads_fwd_small(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
                             return_valid: bool = False, workspace: torch.Tensor | None = None):
     """encoder_heads_fwd for small batches (split-f16 blob only): one launch per big layer (five launches; seven with a strict blob: its
     tail is two launches and the f32 re-evaluation launch follows) spread over the whole chip, bit-identical results."""
-    _need_cuda(x, "x", torch.float32)
-    _need_cuda(blob, "blob", torch.uint8)
-    if x.dim() != 2 or x.shape[1] != F:
-        raise ValueError(f"x: expected [B,{F}], got {tuple(x.shape)}")
-    if x.stride(1) != 1:
-        x = x.contiguous()
-    B = x.shape[0]
-    ldx = x.stride(0) if B > 1 else F
-    ws = workspace if workspace is not None else _small_workspace(B, F, x.device)
-    out = torch.empty((B, 3), dtype=torch.float32, device=x.device)
-    latent = torch.empty((B, LATENT), dtype=torch.float32, device=x.device) if return_latent else None
-    valid = torch.empty((B,), dtype=torch.uint8, device=x.device) if return_valid else None
-    with _on_device_of(("x", x), ("blob", blob), ("workspace", ws)) as stream:
-        _lib.check(_lib.lib().nlml_encoder_heads_fwd_small(
-            x.data_ptr(), ldx, B, F, blob.data_ptr(), blob.numel(), out.data_ptr(),
-            latent.data_ptr() if latent is not None else None,
-            valid.data_ptr() if valid is not None else None, ws.data_ptr(), ws.numel(), stream),
-            "nlml_encoder_heads_fwd_small")
-    res = [out]
-    if return_latent:
-        res.append(latent)
-    if return_valid:
-        res.append(valid.bool())
-    return res[0] if len(res) == 1 else tuple(res)
+    return _k2_forward("small", x, None, blob, F, None, return_latent, return_valid, workspace)
 
 
 def landmarks_to_pose_small(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
                             return_valid: bool = False, workspace: torch.Tensor | None = None):
     """landmarks_to_pose for small batches (split-f16 blob only): one launch per big layer (five launches; seven with a strict blob) spread
     over the whole chip, bit-identical results."""
-    _need_cuda(raw, "raw", torch.float32)
-    _need_cuda(blob, "blob", torch.uint8)
-    if raw.dim() != 3 or raw.shape[1:] != (468, 3):
-        raise ValueError(f"raw: expected [B,468,3], got {tuple(raw.shape)}")
-    raw = raw.contiguous()
-    B = raw.shape[0]
-    ws = workspace if workspace is not None else _small_workspace(B, F_REF, raw.device)
-    out = torch.empty((B, 3), dtype=torch.float32, device=raw.device)
-    latent = torch.empty((B, LATENT), dtype=torch.float32, device=raw.device) if return_latent else None
-    valid = torch.empty((B,), dtype=torch.uint8, device=raw.device) if return_valid else None
-    with _on_device_of(("raw", raw), ("blob", blob), ("workspace", ws)) as stream:
-        _lib.check(_lib.lib().nlml_landmarks_to_pose_small(
-            raw.data_ptr(), B, int(bool(normalize)), blob.data_ptr(), blob.numel(), out.data_ptr(),
-            latent.data_ptr() if latent is not None else None,
-            valid.data_ptr() if valid is not None else None, ws.data_ptr(), ws.numel(), stream),
-            "nlml_landmarks_to_pose_small")
-    res = [out]
-    if return_latent:
-        res.append(latent)
-    if return_valid:
-        res.append(valid.bool())
-    return res[0] if len(res) == 1 else tuple(res)
-
-
-_streamed_ws: dict = {}
+    return _k2_forward("small", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
 
 
 def landmarks_to_pose_streamed(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
@@ -362,34 +327,7 @@ def landmarks_to_pose_streamed(raw: torch.Tensor, blob: torch.Tensor, normalize:
     """landmarks_to_pose (strict-fast blob only) as trunk launch + streamed tail launch + the f32 re-evaluation launch
     (nlml_landmarks_to_pose_streamed): bit-identical to the fused kernel, measured 1.4-2.2 % faster at 65,536 faces; nothing calls it by default
     (DESIGN.md section 3).  The hand-over buffer (1 KB per face) is cached per device and stream like the layer-per-launch path's scratch."""
-    _need_cuda(raw, "raw", torch.float32)
-    _need_cuda(blob, "blob", torch.uint8)
-    if raw.dim() != 3 or raw.shape[1:] != (468, 3):
-        raise ValueError(f"raw: expected [B,468,3], got {tuple(raw.shape)}")
-    raw = raw.contiguous()
-    B = raw.shape[0]
-    if workspace is None:
-        need = max(16, _lib.lib().nlml_encoder_heads_workspace_bytes(B, F_REF))
-        pool = _streamed_ws.setdefault((str(raw.device), _stream_ptr(raw.device)), [])
-        workspace = next((w for w in pool if w.numel() >= need), None)
-        if workspace is None:
-            workspace = torch.empty((need,), dtype=torch.uint8, device=raw.device)
-            pool.append(workspace)
-    out = torch.empty((B, 3), dtype=torch.float32, device=raw.device)
-    latent = torch.empty((B, LATENT), dtype=torch.float32, device=raw.device) if return_latent else None
-    valid = torch.empty((B,), dtype=torch.uint8, device=raw.device) if return_valid else None
-    with _on_device_of(("raw", raw), ("blob", blob), ("workspace", workspace)) as stream:
-        _lib.check(_lib.lib().nlml_landmarks_to_pose_streamed(
-            raw.data_ptr(), B, int(bool(normalize)), blob.data_ptr(), blob.numel(), out.data_ptr(),
-            latent.data_ptr() if latent is not None else None,
-            valid.data_ptr() if valid is not None else None, workspace.data_ptr(), workspace.numel(), stream),
-            "nlml_landmarks_to_pose_streamed")
-    res = [out]
-    if return_latent:
-        res.append(latent)
-    if return_valid:
-        res.append(valid.bool())
-    return res[0] if len(res) == 1 else tuple(res)
+    return _k2_forward("streamed", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
 
 
 # ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------
