@@ -260,6 +260,28 @@ int nlml_tucker_powell_ex(const float* Wm, const float* x, int64_t ldx, const do
                           int32_t* status, int order, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The TD path for ANY Tucker identity rank R (configs/config_TD_main.yaml tensor_decom_ranks.R_identity).  The reference reads the
+ * rank from the artefact (TD_Inference.py:51, u_id_shape = factors_data['U_id'][1].size) and runs objective() and Test() with
+ * 3 + R parameters whatever it is (TD_Tester.py:31-58,162-199); slicing W to fewer identity components is its own advice
+ * (TD_Inference.py:54-55).  The angle ranks stay 3.
+ *   r_id       NLML_TUCKER_RANK_MIN..NLML_TUCKER_RANK_MAX, else NLML_E_SHAPE
+ *   Wm         f32[27 r_id, 1404] = W.reshape(-1, 1404), W f32[r_id,3,3,3,1404]
+ *   params, x0, result   f64[N, 3 + r_id]: (w_y, w_p, w_r, u_id[r_id])
+ *   everything else, the two orders and their alignment rules: as for nlml_tucker_objective_ex / nlml_tucker_powell_ex.
+ * scipy's defaults follow the number of parameters: maxiter = maxfev = 1000 (3 + r_id).
+ * NLML_TD_ORDER_REFERENCE is bit-identical to the reference's objective and walks scipy's trajectory for every rank (FX10: ranks 1, 3
+ * and 8); NLML_TD_ORDER_FAST keeps its <= 1e-12 relative.  r_id == 5 runs the kernels of the entry points above: the same bits.
+ */
+#define NLML_TUCKER_RANK_MIN 1
+#define NLML_TUCKER_RANK_MAX 16
+int nlml_tucker_objective_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index,
+                            const double* params, const double* cos_params, int64_t N,
+                            double* err, double* x_hat, int r_id, int order, void* stream);
+int nlml_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N,
+                         const double* x0, double* result, double* fval, int32_t* nfev, int32_t* nit,
+                         int32_t* status, int r_id, int order, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K4  Video post-processing for S concurrent streams, one frame tick per call.
  * Replaces, per stream (generatePose_on_video.py): round(np.degrees(.), 2) (:211), the exponential
  * smoothing s = alpha*new + (1-alpha)*s seeded by the first prediction (:215-224, alpha 0.4 at :179),
@@ -346,6 +368,12 @@ size_t nlml_powell_state_bytes(void);
 int    nlml_powell_init(void* h_state, const double* h_x0, double xtol, double ftol);
 int    nlml_powell_step(void* h_state, double fin, double* h_xeval);
 int    nlml_powell_result(const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status);
+/* The same machine for n = 3 + r_id parameters, n = 4..19 (the rank-aware device kernel runs this one): h_x0, h_xeval and h_x hold n
+ * doubles.  nlml_powell_state_bytes_n returns 0, the others NLML_E_SHAPE, for an n outside that range; the state remembers its n. */
+size_t nlml_powell_state_bytes_n(int n);
+int    nlml_powell_init_n(void* h_state, int n, const double* h_x0, double xtol, double ftol);
+int    nlml_powell_step_n(void* h_state, double fin, double* h_xeval);
+int    nlml_powell_result_n(const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 _cache: dict = {}
 
@@ -22,15 +22,25 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+RANK_MIN, RANK_MAX = _lib.TUCKER_RANK_MIN, _lib.TUCKER_RANK_MAX   # identity ranks u_id_shape the device path takes
+
+
+def _rank(u_id_shape) -> int:
+    r = int(u_id_shape)
+    if not RANK_MIN <= r <= RANK_MAX:
+        raise ValueError(f"u_id_shape = {u_id_shape}: the device path takes identity ranks {RANK_MIN}..{RANK_MAX} "
+                         "(W of shape [R,3,3,3,1404], 3 + R parameters)")
+    return r
+
+
 def _wm(W) -> torch.Tensor:
-    """W f32[5,3,3,3,1404] -> device f32[135,1404], cached per array (W is immutable shipped data)."""
+    """W f32[R,3,3,3,1404] -> device f32[27R,1404], cached per array (W is immutable shipped data); R = 1..16."""
     key = (id(W), str(_dev()))
     hit = _cache.get(key)
     if hit is None or hit[0] is not W:
         Wn = np.ascontiguousarray(np.asarray(W, dtype=np.float32)).reshape(-1, 1404)
-        if Wn.shape[0] != 135:
-            raise ValueError(f"W must have 5*3*3*3 = 135 coefficient rows, got {Wn.shape[0]} "
-                             "(TD_Inference.py:51-56 uses u_id of size 5 and the first 3 cosine rows)")
+        # R*3*3*3 rows, R in RANK_MIN..RANK_MAX (TD_Inference.py:51-56 takes R from the artefact and the first 3 cosine rows)
+        _lib.tucker_rank_of_rows(Wn.shape[0], "W.reshape(-1, 1404)")
         hit = (W, torch.from_numpy(Wn).to(_dev()))
         _cache[key] = hit
     return hit[1]
@@ -68,10 +78,11 @@ ORDER_REFERENCE, ORDER_FAST = "reference", "fast"
 
 
 def objective_batch(params, W, X, params_y, params_p, params_r, x_index=None, return_xhat=False, order=ORDER_REFERENCE):
-    """params f64[N,8]; X f32[M,1404] (M == N, or rows selected by x_index i32[N]) -> err f64[N] (numpy)."""
-    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 8)).to(_dev())
+    """params f64[N,3+R] (R = W's identity rank); X f32[M,1404] (M == N, or rows selected by x_index i32[N]) -> err f64[N] (numpy)."""
+    Wm = _wm(W)
+    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3 + Wm.shape[0] // 27)).to(_dev())
     xi = None if x_index is None else torch.from_numpy(np.ascontiguousarray(x_index, dtype=np.int32)).to(_dev())
-    out = ops.tucker_objective(_wm(W), _x(X), P, _cos(params_y, params_p, params_r), x_index=xi, return_xhat=return_xhat,
+    out = ops.tucker_objective(Wm, _x(X), P, _cos(params_y, params_p, params_r), x_index=xi, return_xhat=return_xhat,
                                order=order)
     if return_xhat:
         return out[0].cpu().numpy(), out[1].cpu().numpy()
@@ -91,11 +102,12 @@ def compute_gradient_batch(params, W, X, params_y, params_p, params_r):
     gradient einsums are dot products with g:  d/dw_a = -<dc/dw_a, g>, dc/dw_y = u (x) f_y' (x) f_p (x) f_r with
     f' = f32(-a b sin(b w + c)) (:80-95).  The identity-mode term is reproduced as the reference writes it (:96): its inner
     einsum also sums over i, so grad_u[i] = -sum_m S[i,m] r[m] v[m], v = (1 (x) f_y (x) f_p (x) f_r)^T Wm, S[i] = sum_jkl W[i,j,k,l].
-    The three small GEMMs are library f64 matmuls (rocBLAS through torch).  -> f64[N,8] (numpy)."""
+    The three small GEMMs are library f64 matmuls (rocBLAS through torch).  -> f64[N,3+R] (numpy), R = W's identity rank."""
     dev = _dev()
-    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 8)).to(dev)
-    cp = _cos(params_y, params_p, params_r)                                   # [3 angles, 3 rows, (a,b,c,d)]
     Wm = _wm(W)
+    R = Wm.shape[0] // 27
+    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3 + R)).to(dev)
+    cp = _cos(params_y, params_p, params_r)                                   # [3 angles, 3 rows, (a,b,c,d)]
     Xd = _x(X)
     _, xh = ops.tucker_objective(Wm, Xd, P, cp, return_xhat=True)
     r = Xd.double() - xh                                                      # residuals, :77
@@ -110,29 +122,31 @@ def compute_gradient_batch(params, W, X, params_y, params_p, params_r):
         return torch.einsum("ni,nj,nk,nl->nijkl", uu, fy, fp, fr).reshape(P.shape[0], -1)
 
     W64 = Wm.double()
-    g = r @ W64.T                                                             # [N,135]
+    g = r @ W64.T                                                             # [N,27R]
     gy = -(coef(u, df[:, 0], f[:, 1], f[:, 2]) * g).sum(1)
     gp = -(coef(u, f[:, 0], df[:, 1], f[:, 2]) * g).sum(1)
     gr = -(coef(u, f[:, 0], f[:, 1], df[:, 2]) * g).sum(1)
     # 'ijklm,j,k,l->m' (:96) sums over i as well, and all its operands are f32, so numpy evaluates it in f32: v is an f32
     # quantity in the reference (this part of the gradient is therefore pinned to f32 rounding only, ~1e-7 relative)
     v = (coef(ones, f[:, 0], f[:, 1], f[:, 2]).float() @ Wm).double()
-    S = W64.reshape(5, 27, -1).sum(1)                                         # [5,1404]
+    S = W64.reshape(R, 27, -1).sum(1)                                         # [R,1404]
     gu = -((r * v) @ S.T)
     return torch.cat([gy[:, None], gp[:, None], gr[:, None], gu], dim=1).cpu().numpy()
 
 
 def compute_gradient(params, W, x, params_y, params_p, params_r):
-    """Same signature as the reference (:60); x may be a torch tensor or an array.  -> f64[8]."""
+    """Same signature as the reference (:60); x may be a torch tensor or an array.  -> f64[3+R]."""
     return compute_gradient_batch(np.asarray(params, dtype=np.float64)[None], W, x, params_y, params_p, params_r)[0]
 
 
 def Test_batch(W, X, u_id_shape, optimized_params_y, optimized_params_p, optimized_params_r, return_info=False,
                order=ORDER_REFERENCE):
     """Rows of X f32[N,1404] -> degrees f64[N,3] by device-side lock-step Powell (one launch)."""
-    if u_id_shape != 5:
-        raise ValueError("the device minimiser is built for u_id of size 5 (outputs/features/Factor_Matrices.npz)")
-    res = ops.tucker_powell(_wm(W), _x(X), _cos(optimized_params_y, optimized_params_p, optimized_params_r), order=order)
+    R = _rank(u_id_shape)
+    Wm = _wm(W)
+    if Wm.shape[0] != 27 * R:
+        raise ValueError(f"u_id_shape = {R} but W has {Wm.shape[0]} = 27 * {Wm.shape[0] // 27} coefficient rows")
+    res = ops.tucker_powell(Wm, _x(X), _cos(optimized_params_y, optimized_params_p, optimized_params_r), order=order)
     deg = np.degrees(res["x"].cpu().numpy())[:, :3]                               # :196-199
     if return_info:
         return deg, {k: v.cpu().numpy() for k, v in res.items()}

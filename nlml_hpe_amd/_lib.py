@@ -49,6 +49,11 @@ SYMBOLS = {
                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nlml_tucker_powell_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    # the TD path for any identity rank: ..., r_id, order, stream
+    "nlml_tucker_objective_r": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "nlml_tucker_powell_r": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nlml_video_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_video_post_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
@@ -66,6 +71,10 @@ SYMBOLS = {
     "nlml_powell_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "nlml_powell_step": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "nlml_powell_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlml_powell_state_bytes_n": (C.c_size_t, [C.c_int]),
+    "nlml_powell_init_n": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double]),
+    "nlml_powell_step_n": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "nlml_powell_result_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 MODE_F32 = 0
@@ -81,6 +90,7 @@ DEFAULT_MODE_NAME = "f16x2s"
 TD_ORDER_FAST = 0          # GEMM on the f64 matrix cores (<= 1e-12 rel. of the reference's objective)
 TD_ORDER_REFERENCE = 1     # np.einsum's own operation order + numpy's pairwise sum: the reference's bits
 TD_ORDER_NAMES = {"fast": TD_ORDER_FAST, "reference": TD_ORDER_REFERENCE}
+TUCKER_RANK_MIN, TUCKER_RANK_MAX = 1, 16   # NLML_TUCKER_RANK_MIN / NLML_TUCKER_RANK_MAX: identity ranks of the *_r entry points
 POSE_EVAL_MAX_INTERVALS = 64       # NLML_POSE_EVAL_MAX_INTERVALS
 POSE_EVAL_FACES_PER_RECORD = 2048  # NLML_POSE_EVAL_FACES_PER_RECORD
 
@@ -93,6 +103,15 @@ def td_order_from_name(order) -> int:
     if int(order) not in TD_ORDER_NAMES.values():
         raise ValueError(f"unknown TD order {order!r}")
     return int(order)
+
+
+def tucker_rank_of_rows(rows: int, what: str = "Wm") -> int:
+    """Identity rank R of a Wm with `rows` = 27 R rows; ValueError (naming the range) for anything else."""
+    r, rem = divmod(int(rows), 27)
+    if rem or not TUCKER_RANK_MIN <= r <= TUCKER_RANK_MAX:
+        raise ValueError(f"{what}: expected 27*R rows (R*3*3*3) for an identity rank R in [{TUCKER_RANK_MIN}, {TUCKER_RANK_MAX}], "
+                         f"got {rows}")
+    return r
 
 
 def mode_from_name(mode) -> int:

@@ -35,7 +35,7 @@ def heads_training_table(config: dict, optimized: dict, device="cuda") -> dict:
 
 
 def core_to_W(core, U_feat, device="cuda") -> torch.Tensor:
-    """core f32[5,3,3,3,R5], U_feat f32[M,R5] -> W f32[5,3,3,3,M] on the device."""
+    """core f32[R,3,3,3,R5], U_feat f32[M,R5] -> W f32[R,3,3,3,M] on the device (R: the identity rank, 5 in the shipped files)."""
     c = torch.as_tensor(np.ascontiguousarray(core, dtype=np.float32)) if not torch.is_tensor(core) else core
     u = torch.as_tensor(np.ascontiguousarray(U_feat, dtype=np.float32)) if not torch.is_tensor(U_feat) else U_feat
     return ops.mode5_product(c.to(device), u.to(device))

@@ -329,4 +329,77 @@ int nlml_tucker_powell(const float* Wm, const float* x, int64_t ldx, const doubl
   return nlml_tucker_powell_ex(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, NLML_TD_ORDER_REFERENCE, stream);
 }
 
+// ---- the TD path for any identity rank -------------------------------------------------------------------------------------
+static_assert(PW_NMAX == 3 + NLML_TUCKER_RANK_MAX && PW_N == 3 + 5, "powell.h's state sizes follow the ranks");
+static bool rank_ok(int r_id) { return r_id >= NLML_TUCKER_RANK_MIN && r_id <= NLML_TUCKER_RANK_MAX; }
+static int bad_rank(const char* who, int r_id) {
+  static thread_local char msg[160];
+  snprintf(msg, sizeof msg, "%s: identity rank %d outside [%d, %d]", who, r_id, NLML_TUCKER_RANK_MIN, NLML_TUCKER_RANK_MAX);
+  return fail(NLML_E_SHAPE, msg);
+}
+
+int nlml_tucker_objective_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                            const double* cos_params, int64_t N, double* err, double* x_hat, int r_id, int order, void* stream) {
+  if (!rank_ok(r_id)) return bad_rank("tucker_objective_r", r_id);
+  // rank 5: the shipped artefacts' kernels (the same argument checks, in the same order)
+  if (r_id == 5) return nlml_tucker_objective_ex(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, order, stream);
+  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) return fail(NLML_E_BADARG, "tucker_objective_r: unknown order");
+  if (N < 0) return fail(NLML_E_BADARG, "tucker_objective_r: negative N");
+  if (N > 0 && (!Wm || !x || !params || !cos_params || !err)) return fail(NLML_E_BADARG, "tucker_objective_r: null buffer");
+  if (N > 0 && ldx < NLML_F_REFERENCE) return fail(NLML_E_BADARG, "tucker_objective_r: ldx < 1404");
+  if (N > 0 && order == NLML_TD_ORDER_FAST)
+    if (int rc = check_td_fast_alignment(Wm, x, ldx, "tucker_objective_r")) return rc;
+  return launch_tucker_objective_r(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, r_id, order, stream);
+}
+
+int nlml_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
+                         double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order,
+                         void* stream) {
+  if (!rank_ok(r_id)) return bad_rank("tucker_powell_r", r_id);
+  if (r_id == 5) return nlml_tucker_powell_ex(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, order, stream);
+  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) return fail(NLML_E_BADARG, "tucker_powell_r: unknown order");
+  if (N < 0) return fail(NLML_E_BADARG, "tucker_powell_r: negative N");
+  if (N > 0 && (!Wm || !x || !cos_params || !result)) return fail(NLML_E_BADARG, "tucker_powell_r: null buffer");
+  if (N > 0 && ldx < NLML_F_REFERENCE) return fail(NLML_E_BADARG, "tucker_powell_r: ldx < 1404");
+  if (N > 0 && order == NLML_TD_ORDER_FAST)
+    if (int rc = check_td_fast_alignment(Wm, x, ldx, "tucker_powell_r")) return rc;
+  return launch_tucker_powell_r(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, r_id, order, stream);
+}
+
+// host-side stepping for n = 3 + r_id parameters: the state the rank-aware device kernel runs
+static bool dim_ok(int n) { return n >= 3 + NLML_TUCKER_RANK_MIN && n <= 3 + NLML_TUCKER_RANK_MAX; }
+
+size_t nlml_powell_state_bytes_n(int n) { return dim_ok(n) ? sizeof(PowellStateN) : 0; }
+
+int nlml_powell_init_n(void* h_state, int n, const double* h_x0, double xtol, double ftol) {
+  if (!dim_ok(n)) return bad_rank("powell_init_n", n - 3);
+  if (!h_state || !h_x0) return fail(NLML_E_BADARG, "powell_init_n: null pointer");
+  PowellStateN& s = *static_cast<PowellStateN*>(h_state);
+  std::memset(h_state, 0, sizeof(PowellStateN));
+  s.set_dim(n);
+  powell_init(s, h_x0, xtol, ftol);
+  return 0;
+}
+
+int nlml_powell_step_n(void* h_state, double fin, double* h_xeval) {
+  if (!h_state || !h_xeval) return fail(NLML_E_BADARG, "powell_step_n: null pointer");
+  PowellStateN& s = *static_cast<PowellStateN*>(h_state);
+  if (!dim_ok(s.n)) return bad_rank("powell_step_n", s.n - 3);
+  const bool need = powell_step(s, fin);
+  if (need) std::memcpy(h_xeval, s.xeval, sizeof(double) * s.n);
+  return need ? 1 : 0;
+}
+
+int nlml_powell_result_n(const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status) {
+  if (!h_state || !h_x) return fail(NLML_E_BADARG, "powell_result_n: null pointer");
+  const PowellStateN& s = *static_cast<const PowellStateN*>(h_state);
+  if (!dim_ok(s.n)) return bad_rank("powell_result_n", s.n - 3);
+  std::memcpy(h_x, s.x, sizeof(double) * s.n);
+  if (h_fval) *h_fval = s.fval;
+  if (h_nfev) *h_nfev = s.nfev;
+  if (h_nit) *h_nit = s.iter;
+  if (h_status) *h_status = s.status;
+  return 0;
+}
+
 }  // extern "C"

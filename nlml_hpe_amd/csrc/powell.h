@@ -30,26 +30,46 @@
 
 namespace nlml {
 
-constexpr int PW_N = 8;  // (w_y, w_p, w_r, u_id[5]) -- TD_Tester.py:166
+constexpr int PW_N = 8;      // (w_y, w_p, w_r, u_id[5]) -- TD_Tester.py:166
+constexpr int PW_NMAX = 19;  // 3 + the largest identity rank of the rank-aware entry points (NLML_TUCKER_RANK_MAX)
 
-struct PowellState {
+// The number of parameters: a constant of the type (the shipped artefacts' 8: every loop below unrolls as it always has), or a
+// field of the state (the rank-aware entry points: n = 3 + R up to the arrays' extent).
+template <int NMAX>
+struct PowellDimFixed {
+  static constexpr bool kDyn = false;
+  NLML_HD int dim() const { return NMAX; }
+  NLML_HD void set_dim(int) {}
+};
+struct PowellDimDyn {
+  static constexpr bool kDyn = true;
+  int n;
+  NLML_HD int dim() const { return n; }
+  NLML_HD void set_dim(int v) { n = v; }
+};
+
+template <int NMAX, typename Dim>
+struct PowellStateT : Dim {
+  static constexpr int kMax = NMAX;
   // --- outer Powell ---
   int pc;          // resume label of the outer machine
   int ls_pc;       // resume label of the line-search machine
   int i, iter, bigind, nfev, maxfun, maxiter, status, any;
   double xtol, ftol;
-  double x[PW_N], x1[PW_N], direc[PW_N][PW_N];
+  double x[NMAX], x1[NMAX], direc[NMAX][NMAX];
   double fval, fx, fx2, delta, t, temp;
   // --- line search (bracket + Brent) along xi from p ---
-  double p[PW_N], xi[PW_N], d1[PW_N];
+  double p[NMAX], xi[NMAX], d1[NMAX];
   double alpha_min, fret;
   double xa, xb, xc, fa, fb, fc, w, fw, wlim, tmp1, tmp2, val, denom;
   int biter, bracket_ok, brk;
   double bx, bw, bv, bfx, bfw, bfv, a, b, deltax, rat, u, fu, tol1, tol2, xmid, pp, dx_temp;
   int it;
   // --- the point whose objective value the caller must supply next ---
-  double xeval[PW_N];
+  double xeval[NMAX];
 };
+typedef PowellStateT<PW_N, PowellDimFixed<PW_N>> PowellState;   // the 8-parameter machine of the shipped artefacts
+typedef PowellStateT<PW_NMAX, PowellDimDyn> PowellStateN;        // n = 4..19 parameters (identity ranks 1..16)
 
 enum { PW_RUNNING = 0, PW_CONVERGED = 1, PW_MAXFEV = 2, PW_MAXITER = 3, PW_NAN = 4 };
 
@@ -59,25 +79,30 @@ enum { PW_RUNNING = 0, PW_CONVERGED = 1, PW_MAXFEV = 2, PW_MAXITER = 3, PW_NAN =
 #define NLML_FP_STRICT
 #endif
 
-NLML_HD void powell_init(PowellState& s, const double* x0, double xtol = 1e-4, double ftol = 1e-4) {
+// A rank-aware state has its n set (set_dim) before this call.  scipy's defaults: maxiter = maxfev = 1000 n.
+template <typename S>
+NLML_HD void powell_init(S& s, const double* x0, double xtol = 1e-4, double ftol = 1e-4) {
+  const int N = s.dim();
   s.pc = 0; s.ls_pc = 0; s.iter = 0; s.nfev = 0; s.status = PW_RUNNING;
-  s.maxfun = PW_N * 1000; s.maxiter = PW_N * 1000;
+  s.maxfun = N * 1000; s.maxiter = N * 1000;
   s.xtol = xtol; s.ftol = ftol;
-  for (int k = 0; k < PW_N; ++k) {
+  for (int k = 0; k < N; ++k) {
     s.x[k] = x0[k];
-    for (int j = 0; j < PW_N; ++j) s.direc[k][j] = (k == j) ? 1.0 : 0.0;
+    for (int j = 0; j < N; ++j) s.direc[k][j] = (k == j) ? 1.0 : 0.0;
   }
 }
 
 // Line search from s.p along s.xi with Brent tolerance tol.  Returns true when it needs the
 // objective at s.xeval (resume with its value in fin); false when finished, with s.fret,
 // s.alpha_min set.  Mirrors scipy's bracket() + Brent.optimize() + bracket-error recovery.
-NLML_HD bool linesearch_step(PowellState& s, double fin, double tol) {
+template <typename S>
+NLML_HD bool linesearch_step(S& s, double fin, double tol) {
   NLML_FP_STRICT
+  const int N = s.dim();
   const double gold = 1.618034, verysmall = 1e-21, grow_limit = 110.0, cg = 0.3819660, mintol = 1.0e-11;
 #define LS_EVAL(LABEL, ALPHA)                                                        \
   do {                                                                               \
-    for (int k_ = 0; k_ < PW_N; ++k_) s.xeval[k_] = s.p[k_] + (ALPHA) * s.xi[k_];    \
+    for (int k_ = 0; k_ < N; ++k_) s.xeval[k_] = s.p[k_] + (ALPHA) * s.xi[k_];    \
     s.ls_pc = LABEL;                                                                 \
     return true;                                                                     \
     case LABEL:;                                                                     \
@@ -220,13 +245,16 @@ NLML_HD bool linesearch_step(PowellState& s, double fin, double tol) {
 // front and written back once.  Same operations in the same order as linesearch_step's loop body.  Returns true when the
 // iteration suspended again at label 10 (state committed); false when it would leave the loop (converged, iteration limit) --
 // then NOTHING has been written and the caller runs the generic machine on the untouched state.
-NLML_HD bool brent_resume_fast(PowellState& s, double fin, double tol) {
+template <typename S>
+NLML_HD bool brent_resume_fast(S& s, double fin, double tol) {
   NLML_FP_STRICT
+  const int N = s.dim();
   const double cg = 0.3819660, mintol = 1.0e-11;
   double bx = s.bx, bw = s.bw, bv = s.bv, bfx = s.bfx, bfw = s.bfw, bfv = s.bfv, a = s.a, b = s.b;
   double deltax = s.deltax, rat = s.rat, u = s.u;
-  double pk[PW_N], xk[PW_N];
-  for (int k = 0; k < PW_N; ++k) { pk[k] = s.p[k]; xk[k] = s.xi[k]; }
+  double pk[S::kMax], xk[S::kMax];   // (a rank-aware state reads p and xi where they are used: arrays indexed by a run-time loop would leave the registers)
+  if constexpr (!S::kDyn)
+    for (int k = 0; k < N; ++k) { pk[k] = s.p[k]; xk[k] = s.xi[k]; }
   const int it = s.it + 1;
   const double fu = fin;
   if (fu > bfx) {
@@ -271,15 +299,20 @@ NLML_HD bool brent_resume_fast(PowellState& s, double fin, double tol) {
   else u = bx + rat;
   s.bx = bx; s.bw = bw; s.bv = bv; s.bfx = bfx; s.bfw = bfw; s.bfv = bfv; s.a = a; s.b = b;
   s.deltax = deltax; s.rat = rat; s.u = u; s.fu = fu; s.it = it;
-  for (int k = 0; k < PW_N; ++k) s.xeval[k] = pk[k] + u * xk[k];
+  if constexpr (S::kDyn)
+    for (int k = 0; k < N; ++k) s.xeval[k] = s.p[k] + u * s.xi[k];
+  else
+    for (int k = 0; k < N; ++k) s.xeval[k] = pk[k] + u * xk[k];
   return true;
 }
 
 // Advance the minimiser.  First call: fin is ignored.  Returns true when the caller must evaluate
 // the objective at s.xeval and call again with the value; false when finished (s.x, s.fval,
 // s.nfev, s.iter, s.status hold the result: scipy's res.x, res.fun, res.nfev, res.nit).
-NLML_HD bool powell_step(PowellState& s, double fin) {
+template <typename S>
+NLML_HD bool powell_step(S& s, double fin) {
   NLML_FP_STRICT
+  const int N = s.dim();
   // scipy's function wrapper raises _MaxFuncCallError BEFORE evaluation number maxfun+1; the
   // driver loop catches it and stops with the current x.
 #define PW_EVAL_AT_XEVAL(LABEL)                          \
@@ -313,22 +346,22 @@ NLML_HD bool powell_step(PowellState& s, double fin) {
 #endif
   switch (s.pc) {
     case 0:
-      for (int k = 0; k < PW_N; ++k) s.xeval[k] = s.x[k];
+      for (int k = 0; k < N; ++k) s.xeval[k] = s.x[k];
       PW_EVAL_AT_XEVAL(1);
       s.fval = fin;
-      for (int k = 0; k < PW_N; ++k) s.x1[k] = s.x[k];
+      for (int k = 0; k < N; ++k) s.x1[k] = s.x[k];
       s.iter = 0;
       while (true) {
         s.fx = s.fval;
         s.bigind = 0;
         s.delta = 0.0;
-        for (s.i = 0; s.i < PW_N; ++s.i) {
+        for (s.i = 0; s.i < N; ++s.i) {
           s.fx2 = s.fval;
           s.any = 0;
-          for (int k = 0; k < PW_N; ++k) { s.xi[k] = s.direc[s.i][k]; s.p[k] = s.x[k]; s.any |= (s.xi[k] != 0.0); }
+          for (int k = 0; k < N; ++k) { s.xi[k] = s.direc[s.i][k]; s.p[k] = s.x[k]; s.any |= (s.xi[k] != 0.0); }
           if (s.any) {  // a zero direction is skipped (_linesearch_powell: "if not np.any(xi)")
             PW_LINESEARCH(2);
-            for (int k = 0; k < PW_N; ++k) { s.d1[k] = s.alpha_min * s.xi[k]; s.x[k] = s.p[k] + s.d1[k]; }
+            for (int k = 0; k < N; ++k) { s.d1[k] = s.alpha_min * s.xi[k]; s.x[k] = s.p[k] + s.d1[k]; }
             s.fval = s.fret;
           }
           if ((s.fx2 - s.fval) > s.delta) { s.delta = s.fx2 - s.fval; s.bigind = s.i; }
@@ -339,7 +372,7 @@ NLML_HD bool powell_step(PowellState& s, double fin) {
         if (s.iter >= s.maxiter) { s.status = PW_MAXITER; break; }
         if (isnan(s.fx) && isnan(s.fval)) { s.status = PW_NAN; break; }
         // extrapolated point
-        for (int k = 0; k < PW_N; ++k) { s.d1[k] = s.x[k] - s.x1[k]; s.x1[k] = s.x[k]; s.xeval[k] = s.x[k] + s.d1[k]; }
+        for (int k = 0; k < N; ++k) { s.d1[k] = s.x[k] - s.x1[k]; s.x1[k] = s.x[k]; s.xeval[k] = s.x[k] + s.d1[k]; }
         PW_EVAL_AT_XEVAL(3);
         s.fx2 = fin;
         if (s.fx > s.fx2) {
@@ -350,18 +383,18 @@ NLML_HD bool powell_step(PowellState& s, double fin) {
           s.t -= s.delta * s.temp * s.temp;
           if (s.t < 0.0) {
             s.any = 0;
-            for (int k = 0; k < PW_N; ++k) { s.xi[k] = s.d1[k]; s.p[k] = s.x[k]; s.any |= (s.xi[k] != 0.0); }
+            for (int k = 0; k < N; ++k) { s.xi[k] = s.d1[k]; s.p[k] = s.x[k]; s.any |= (s.xi[k] != 0.0); }
             if (s.any) {
               PW_LINESEARCH(4);
               s.any = 0;
-              for (int k = 0; k < PW_N; ++k) {
+              for (int k = 0; k < N; ++k) {
                 s.d1[k] = s.alpha_min * s.xi[k];
                 s.x[k] = s.p[k] + s.d1[k];
                 s.any |= (s.d1[k] != 0.0);
               }
               s.fval = s.fret;
               if (s.any) {
-                for (int k = 0; k < PW_N; ++k) { s.direc[s.bigind][k] = s.direc[PW_N - 1][k]; s.direc[PW_N - 1][k] = s.d1[k]; }
+                for (int k = 0; k < N; ++k) { s.direc[s.bigind][k] = s.direc[N - 1][k]; s.direc[N - 1][k] = s.d1[k]; }
               }
             }
           }
@@ -369,7 +402,7 @@ NLML_HD bool powell_step(PowellState& s, double fin) {
       }
       if (s.status == PW_CONVERGED) {
         s.any = isnan(s.fval) ? 1 : 0;
-        for (int k = 0; k < PW_N; ++k) s.any |= isnan(s.x[k]) ? 1 : 0;
+        for (int k = 0; k < N; ++k) s.any |= isnan(s.x[k]) ? 1 : 0;
         if (s.any) s.status = PW_NAN;
       }
       s.pc = -1;

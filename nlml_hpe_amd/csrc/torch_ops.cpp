@@ -138,46 +138,50 @@ std::tuple<at::Tensor, at::Tensor> landmarks_to_pose_valid(const at::Tensor& raw
   return {r.pose, r.valid};
 }
 
-void check_td(const at::Tensor& Wm, const at::Tensor& x, const at::Tensor& cosp) {
+// -> the identity rank R of Wm [27 R, 1404]
+int check_td(const at::Tensor& Wm, const at::Tensor& x, const at::Tensor& cosp) {
   need(Wm, "Wm", at::kFloat);
   need(x, "x", at::kFloat);
   need(cosp, "cos_params", at::kDouble);
   same_device(x, Wm, "Wm");
   same_device(x, cosp, "cos_params");
-  TORCH_CHECK(Wm.dim() == 2 && Wm.size(0) == 135 && Wm.size(1) == F_REF, "Wm: expected [135,1404], got ", Wm.sizes());
+  TORCH_CHECK(Wm.dim() == 2 && Wm.size(1) == F_REF && Wm.size(0) % 27 == 0 && Wm.size(0) >= 27 * NLML_TUCKER_RANK_MIN &&
+                  Wm.size(0) <= 27 * NLML_TUCKER_RANK_MAX,
+              "Wm: expected [27*R,1404] for an identity rank R in [", NLML_TUCKER_RANK_MIN, ", ", NLML_TUCKER_RANK_MAX, "], got ", Wm.sizes());
   TORCH_CHECK(x.dim() == 2 && x.size(1) == F_REF, "x: expected [N,1404], got ", x.sizes());
   TORCH_CHECK(cosp.dim() == 3 && cosp.size(0) == 3 && cosp.size(1) == 3 && cosp.size(2) == 4, "cos_params: expected [3,3,4], got ", cosp.sizes());
+  return (int)(Wm.size(0) / 27);
 }
 
 at::Tensor tucker_objective(const at::Tensor& Wm_, const at::Tensor& x_, const at::Tensor& params_, const at::Tensor& cosp_,
                             std::string order) {
-  check_td(Wm_, x_, cosp_);
+  const int r_id = check_td(Wm_, x_, cosp_);
   need(params_, "params", at::kDouble);
   same_device(x_, params_, "params");
-  TORCH_CHECK(params_.dim() == 2 && params_.size(1) == 8, "params: expected [N,8], got ", params_.sizes());
+  TORCH_CHECK(params_.dim() == 2 && params_.size(1) == 3 + r_id, "params: expected [N,", 3 + r_id, "], got ", params_.sizes());
   TORCH_CHECK(x_.size(0) == params_.size(0), "x has ", x_.size(0), " rows but params has ", params_.size(0));
   const at::Tensor Wm = Wm_.contiguous(), x = x_.contiguous(), params = params_.contiguous(), cosp = cosp_.contiguous();
   const int64_t N = params.size(0);
   at::Tensor err = at::empty({N}, params.options());
   OnDevice dev(x);
-  check(nlml_tucker_objective_ex(Wm.data_ptr<float>(), x.data_ptr<float>(), F_REF, nullptr, params.data_ptr<double>(),
-                                 cosp.data_ptr<double>(), N, err.data_ptr<double>(), nullptr, td_order(order), dev.stream),
-        "nlml_tucker_objective_ex");
+  check(nlml_tucker_objective_r(Wm.data_ptr<float>(), x.data_ptr<float>(), F_REF, nullptr, params.data_ptr<double>(),
+                                cosp.data_ptr<double>(), N, err.data_ptr<double>(), nullptr, r_id, td_order(order), dev.stream),
+        "nlml_tucker_objective_r");
   return err;
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> tucker_powell(const at::Tensor& Wm_, const at::Tensor& x_,
                                                                                       const at::Tensor& cosp_, std::string order) {
-  check_td(Wm_, x_, cosp_);
+  const int r_id = check_td(Wm_, x_, cosp_);
   const at::Tensor Wm = Wm_.contiguous(), x = x_.contiguous(), cosp = cosp_.contiguous();
   const int64_t N = x.size(0);
   const auto f64 = x.options().dtype(at::kDouble), i32 = x.options().dtype(at::kInt);
-  at::Tensor res = at::empty({N, 8}, f64), fun = at::empty({N}, f64), nfev = at::empty({N}, i32), nit = at::empty({N}, i32),
+  at::Tensor res = at::empty({N, 3 + r_id}, f64), fun = at::empty({N}, f64), nfev = at::empty({N}, i32), nit = at::empty({N}, i32),
              status = at::empty({N}, i32);
   OnDevice dev(x);
-  check(nlml_tucker_powell_ex(Wm.data_ptr<float>(), x.data_ptr<float>(), F_REF, cosp.data_ptr<double>(), N, nullptr,
-                              res.data_ptr<double>(), fun.data_ptr<double>(), nfev.data_ptr<int32_t>(), nit.data_ptr<int32_t>(),
-                              status.data_ptr<int32_t>(), td_order(order), dev.stream), "nlml_tucker_powell_ex");
+  check(nlml_tucker_powell_r(Wm.data_ptr<float>(), x.data_ptr<float>(), F_REF, cosp.data_ptr<double>(), N, nullptr,
+                             res.data_ptr<double>(), fun.data_ptr<double>(), nfev.data_ptr<int32_t>(), nit.data_ptr<int32_t>(),
+                             status.data_ptr<int32_t>(), r_id, td_order(order), dev.stream), "nlml_tucker_powell_r");
   return {res, fun, nfev, nit, status};
 }
 
@@ -288,11 +292,11 @@ at::Tensor tucker_objective_meta(const at::Tensor&, const at::Tensor&, const at:
 std::tuple<at::Tensor, at::Tensor> pose_valid_meta(const at::Tensor& raw, const at::Tensor&, bool, const std::optional<at::Tensor>&) {
   return {at::empty({raw.size(0), 3}, raw.options()), at::empty({raw.size(0)}, raw.options().dtype(at::kByte))};
 }
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> tucker_powell_meta(const at::Tensor&, const at::Tensor& x, const at::Tensor&,
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> tucker_powell_meta(const at::Tensor& Wm, const at::Tensor& x, const at::Tensor&,
                                                                                            std::string) {
-  const int64_t N = x.size(0);
+  const int64_t N = x.size(0), n_par = 3 + Wm.size(0) / 27;   // Wm [27 R, 1404] -> 3 + R parameters per face
   const auto f64 = x.options().dtype(at::kDouble), i32 = x.options().dtype(at::kInt);
-  return {at::empty({N, 8}, f64), at::empty({N}, f64), at::empty({N}, i32), at::empty({N}, i32), at::empty({N}, i32)};
+  return {at::empty({N, n_par}, f64), at::empty({N}, f64), at::empty({N}, i32), at::empty({N}, i32), at::empty({N}, i32)};
 }
 void video_post_meta(const at::Tensor&, const at::Tensor&, const std::optional<at::Tensor>&, double, double, double, double, double, at::Tensor,
                      at::Tensor, at::Tensor, at::Tensor, at::Tensor) {}   // everything in place: nothing to shape

@@ -78,11 +78,13 @@ __device__ __forceinline__ void load11(const float* __restrict__ p, int j, float
   v[8] = c[0]; v[9] = c[1]; v[10] = c[2];
 }
 
-struct TuckerShared {
-  double coef[TQS * 4][EV];   // [q][evaluation]; row 135 is zero
+template <int QROWS>
+struct TuckerSharedT {
+  double coef[QROWS][EV];     // [q][evaluation]; the rows from Q up to the next multiple of 4 are zero
   double fvec[EV][3][3];
   double red[TNW][EV];
 };
+typedef TuckerSharedT<TQS * 4> TuckerShared;   // the shipped artefacts' 135 rows (row 135 is zero); other identity ranks: tucker_rank.h
 
 // Sum over the 16 lanes of a DPP row as the balanced tree ((v0+v1)+(v2+v3))+... -- the tree the xor butterfly
 // v[c] += v[c^1], v[c^2], v[c^4], v[c^8] builds in every lane (the C oracle's device order) -- on the vector ALUs' DPP path
@@ -331,7 +333,8 @@ __device__ __attribute__((noinline)) void tucker_mfma4(TuckerShared& sh, const f
 
 // Residual norms of the 16 evaluations.  xv[mb][r] = x of evaluation (lane>>4) + 4r at this lane's column of
 // block mb.  After the call (barrier inside) tucker_err(e) is valid for every thread.
-__device__ __forceinline__ void tucker_residual(TuckerShared& sh, const float (&xv)[MBW][4], const f64x4 (&acc)[MBW],
+template <typename SH>
+__device__ __forceinline__ void tucker_residual(SH& sh, const float (&xv)[MBW][4], const f64x4 (&acc)[MBW],
                                                 int tid) {
   const int lane = tid & 63, wv = tid >> 6, col = lane & 15;
   double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -357,7 +360,8 @@ __device__ __forceinline__ void tucker_load_x(const float* __restrict__ xrow, in
   load11(xrow + tcol0(tid >> 6), tid & 15, v);
 }
 
-__device__ __forceinline__ double tucker_err(const TuckerShared& sh, int e) {
+template <typename SH>
+__device__ __forceinline__ double tucker_err(const SH& sh, int e) {
   return 0.5 * (((sh.red[0][e] + sh.red[1][e]) + (sh.red[2][e] + sh.red[3][e])) +
                 ((sh.red[4][e] + sh.red[5][e]) + (sh.red[6][e] + sh.red[7][e])));
 }

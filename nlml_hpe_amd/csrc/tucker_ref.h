@@ -72,12 +72,27 @@ struct TrPairs {
   }
 };
 
-struct TuckerRefShared {
-  double d2[TR_MAXE][TM + 4];              // squared residuals of the pass's evaluations
-  double leaf8[TR_MAXE][TR_LEAVES][8];     // strided partial sums of every leaf
-  double leaf[TR_MAXE][TR_LEAVES];
-  double fac[TR_MAXE][TR_NFAC + 2];        // the pass's factors, by evaluation
+template <int MAXE, int NFAC>
+struct TuckerRefSharedT {
+  static constexpr int kMaxE = MAXE;       // evaluations per pass over Wm
+  static constexpr int kFS = NFAC + 2;     // row stride of fac
+  double d2[MAXE][TM + 4];                 // squared residuals of the pass's evaluations
+  double leaf8[MAXE][TR_LEAVES][8];        // strided partial sums of every leaf
+  double leaf[MAXE][TR_LEAVES];
+  double fac[MAXE][NFAC + 2];              // the pass's factors, by evaluation
   double err[EV];                          // objective values of the round, by machine slot
+};
+typedef TuckerRefSharedT<TR_MAXE, TR_NFAC> TuckerRefShared;   // identity rank 5; the rank-aware kernels' tables: tucker_rank.h
+
+// The identity rank R of a pass (Wm has 27 R rows, an evaluation R + 9 factors): a constant of the type for the shipped artefacts'
+// 5 -- the pass is then the code it has always been -- or a run-time value, 1..16 (tucker_rank.h).
+template <int R>
+struct TrFixedRank {
+  __device__ __forceinline__ constexpr int r() const { return R; }
+};
+struct TrDynRank {
+  int rid;
+  __device__ __forceinline__ int r() const { return __builtin_amdgcn_readfirstlane(rid); }   // (arguments of a non-inlined function arrive in vector registers)
 };
 
 __device__ __forceinline__ int tr_leaf_start(int L) { return L == 0 ? 0 : 80 + 88 * (L - 1); }
@@ -111,15 +126,16 @@ __device__ __forceinline__ double uniform_f64(double v) {
 #ifndef TR_BAL_FROM
 #define TR_BAL_FROM 2
 #endif
-template <int NE, typename ParT, typename XRow, typename XhRow>
-__device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh, TuckerRefShared& rs, const float* __restrict__ Wm_,
+template <int NE, typename ParT, typename XRow, typename XhRow, typename SH, typename RS, typename Rank = TrFixedRank<5>>
+__device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, const float* __restrict__ Wm_,
                                                           const ParT par, const unsigned slots, const XRow xrow,
-                                                          const XhRow xhrow, const int tid) {
+                                                          const XhRow xhrow, const int tid, const Rank rank = Rank()) {
 #pragma clang fp contract(off)
   // LDS through address-space-3 pointers taken ONCE: every access is then a ds_ instruction with an immediate offset from one base
   // register (per-element casts of generic addresses cost an address register each -- ~30 of the 168 this function may use)
-  typedef __attribute__((address_space(3))) TuckerRefShared LdsRef;
-  typedef __attribute__((address_space(3))) const TuckerShared LdsSh;
+  typedef __attribute__((address_space(3))) RS LdsRef;
+  typedef __attribute__((address_space(3))) const SH LdsSh;
+  const int RID = rank.r(), TQR = 27 * RID, NFAC = RID + 9;   // rows of Wm; factors of an evaluation: u[R], f_y[3], f_p[3], f_r[3]
   LdsRef* const rl = (LdsRef*)&rs;
   LdsSh* const sl = (LdsSh*)&sh;
 #ifdef TR_STAMPS   // timing-only diagnostic build (tools/td_ref_stamps.py): s_memtime at the phase boundaries of each pass into the x_hat buffer
@@ -132,13 +148,13 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
   TRS(0);
   // Wm as a buffer resource: a load is (scalar row offset) + (the lane's column offset in a vector register), so the ring costs no
   // address arithmetic on the vector ALUs.  Every load stays INSIDE Wm by construction, not by the descriptor's range check (the
-  // scalar offset is not part of that check): the two prefetches past the last block re-read row 134 (scalar min), and a dead
+  // scalar offset is not part of that check): the two prefetches past the last block re-read the last row (scalar min), and a dead
   // lane (column >= 1404) reads column 0 of its row; neither value is used.  Arguments of a non-inlined function arrive in vector
   // registers: the base is made uniform first.
   const float* Wm = reinterpret_cast<const float*>(
       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)Wm_ >> 32)) << 32) |
       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint64_t)Wm_));
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)Wm, 0, TQ * TM * 4, 0x00027000);
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)Wm, 0, TQR * TM * 4, 0x00027000);
   constexpr bool BAL = NE >= TR_BAL_FROM && TR_NT == 768 && TR_COLS == 2;
   unsigned mc[TR_COLS];
   bool livec[TR_COLS];
@@ -168,19 +184,19 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
   auto wload = [&](int b, float (&dst)[3][TR_COLS]) {
 #pragma unroll
     for (int l = 0; l < 3; ++l) {
-      const int row = 3 * b + l < TQ ? 3 * b + l : TQ - 1;
+      const int row = 3 * b + l < TQR ? 3 * b + l : TQR - 1;
 #pragma unroll
       for (int c = 0; c < TR_COLS; ++c)
         dst[l][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, voff[c], row * (TM * 4), 0));
     }
   };
-  // the pass's factors -> rs.fac[n][0..4] = u, [5..7] = f_y, [8..10] = f_p, [11..13] = f_r.  Their loads are issued first, the
+  // the pass's factors -> rs.fac[n][0..R-1] = u, [R..R+2] = f_y, [R+3..R+5] = f_p, [R+6..R+8] = f_r (R = 5: 0..4, 5..7, 8..10, 11..13).  Their loads are issued first, the
   // first two blocks of the ring next (memory loads return in order), so the ring's latency overlaps the table and its barrier
   double facv = 0.0;
-  if (tid < NE * TR_NFAC) {
-    const int n = tid / TR_NFAC, f = tid % TR_NFAC;
+  if (tid < NE * NFAC) {
+    const int n = tid / NFAC, f = tid % NFAC;
     const int slot = (slots >> (4 * n)) & 15;
-    facv = f < 5 ? par(slot, 3 + f) : sl->fvec[slot][(f - 5) / 3][(f - 5) % 3];
+    facv = f < RID ? par(slot, 3 + f) : sl->fvec[slot][(f - RID) / 3][(f - RID) % 3];
   }
   __builtin_amdgcn_sched_barrier(0);
   wload(0, wr[0]);
@@ -206,7 +222,7 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
   }
 #endif
   __builtin_amdgcn_sched_barrier(0);
-  if (tid < NE * TR_NFAC) rl->fac[tid / TR_NFAC][tid % TR_NFAC] = facv;
+  if (tid < NE * NFAC) rl->fac[tid / NFAC][tid % NFAC] = facv;
   __syncthreads();
 
   // the factor table through ONE opaque base register: its LDS address is a compile-time constant beyond the 16-bit offset field,
@@ -214,12 +230,13 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
   unsigned fac_addr = (unsigned)(uintptr_t)&rl->fac[0][0];
   asm volatile("" : "+v"(fac_addr));
   const __attribute__((address_space(3))) double* const fac = (const __attribute__((address_space(3))) double*)(uintptr_t)fac_addr;
-  constexpr int FS = TR_NFAC + 2;          // row stride of rs.fac
+  const __attribute__((address_space(3))) double* const facf = fac + RID;   // the f-vectors behind u
+  constexpr int FS = RS::kFS;              // row stride of rs.fac
   double fr[3][NE];
 #pragma unroll
   for (int l = 0; l < 3; ++l)
 #pragma unroll
-    for (int n = 0; n < NE; ++n) fr[l][n] = uniform_f64(fac[n * FS + 11 + l]);
+    for (int n = 0; n < NE; ++n) fr[l][n] = uniform_f64(facf[n * FS + 6 + l]);
 
   double acc[TR_COLS][NE];
 #pragma unroll
@@ -232,7 +249,7 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
 #pragma unroll
   for (int k = 0; k < 3; ++k)
 #pragma unroll
-    for (int n = 0; n < NE; ++n) fpr[k][n] = fac[n * FS + 8 + k];
+    for (int n = 0; n < NE; ++n) fpr[k][n] = facf[n * FS + 3 + k];
 #endif
   TRS(1);
 
@@ -242,7 +259,7 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
   constexpr TrPairs<NE, VAR> PR{};
   constexpr int CNT = PR.cnt, NG = (CNT + 2 * TR_ILV - 1) / (2 * TR_ILV), G = (CNT + NG - 1) / NG;
 #pragma unroll 1
-  for (int i = 0; i < 5; ++i) {
+  for (int i = 0; i < RID; ++i) {
     double u[NE];
 #pragma unroll
     for (int n = 0; n < NE; ++n) u[n] = fac[n * FS + i];
@@ -250,7 +267,7 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
     for (int j = 0; j < 3; ++j) {
       double fy[NE];
 #pragma unroll
-      for (int n = 0; n < NE; ++n) fy[n] = fac[n * FS + 5 + j];
+      for (int n = 0; n < NE; ++n) fy[n] = facf[n * FS + j];
       const int b0 = (i * 3 + j) * 3;
 #ifndef TR_NO_PRIO
       {  // Issue priority falls with progress (s_setprio takes an immediate: four levels).  The arbiter serves the OLDEST wave of a SIMD
@@ -259,11 +276,12 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
          // ahead now has the lower priority: it still fills the slots its siblings leave, but cannot run away -- only the last
          // segment's imbalance is left, hence segments of 8, 4, 2 and 1 of the 15 (i, j) steps: 119.8 k / 122.6 k / 121.6 k ticks
          // against 118.8 k of pure issue (135 rows x 44 chains x 5 operations x 4 cycles), the pass 143.3 k -> 132.5 k.
-        const int ij = i * 3 + j;
+        // (Other ranks keep the last three segments: 4, 2 and 1 steps before the end of their 3 R.)
+        const int ij = i * 3 + j, NIJ = 3 * RID;
         if (ij == 0) __builtin_amdgcn_s_setprio(3);
-        else if (ij == 8) __builtin_amdgcn_s_setprio(2);
-        else if (ij == 12) __builtin_amdgcn_s_setprio(1);
-        else if (ij == 14) __builtin_amdgcn_s_setprio(0);
+        else if (ij == NIJ - 7) __builtin_amdgcn_s_setprio(2);
+        else if (ij == NIJ - 3) __builtin_amdgcn_s_setprio(1);
+        else if (ij == NIJ - 1) __builtin_amdgcn_s_setprio(0);
       }
 #endif
 #pragma unroll
@@ -276,7 +294,7 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
 #ifdef TR_FP_RESIDENT
         for (int n = 0; n < NE; ++n) fp[n] = fpr[k][n];
 #else
-        for (int n = 0; n < NE; ++n) fp[n] = fac[n * FS + 8 + k];
+        for (int n = 0; n < NE; ++n) fp[n] = facf[n * FS + 3 + k];
 #endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -406,8 +424,8 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const TuckerShared& sh
 }
 
 // f-vectors of all 16 slots into sh.fvec (tucker_coef's first half; the coefficient table is not used in this order)
-template <typename ParT>
-__device__ __forceinline__ void tucker_fvec(TuckerShared& sh, const ParT& par, const double (&cp4)[4], int tid) {
+template <typename SH, typename ParT>
+__device__ __forceinline__ void tucker_fvec(SH& sh, const ParT& par, const double (&cp4)[4], int tid) {
 #pragma clang fp contract(off)   // numpy rounds b*w, + c, a*cos, + d separately (TD_Tester.py:25-28)
   if (tid < EV * 9) {
     const int e = tid / 9, a = (tid % 9) / 3;

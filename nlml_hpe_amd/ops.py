@@ -170,8 +170,8 @@ def landmarks_to_pose(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = T
 
 def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, cos_params: torch.Tensor,
                      x_index: torch.Tensor | None = None, return_xhat: bool = False, order="reference"):
-    """Batched objective (TD_Tester.py:31-58): Wm f32[135,1404], x f32[M,1404], params f64[N,8],
-    cos_params f64[3,3,4] -> err f64[N] (+ x_hat f64[N,1404]).  order: "reference" (the default and the parity mode: np.einsum's
+    """Batched objective (TD_Tester.py:31-58): Wm f32[27R,1404], x f32[M,1404], params f64[N,3+R],
+    cos_params f64[3,3,4] -> err f64[N] (+ x_hat f64[N,1404]); R = the identity rank, 1..16 (5 for the shipped artefacts).  order: "reference" (the default and the parity mode: np.einsum's
     operation order and numpy's pairwise sum -- the reference's bits) or "fast" (opt-in: a GEMM on the f64 matrix cores, <= 1e-12
     relative, ~5x the evaluations/s)."""
     order = _lib.td_order_from_name(order)
@@ -179,12 +179,13 @@ def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, co
     _need_cuda(x, "x", torch.float32)
     _need_cuda(params, "params", torch.float64)
     _need_cuda(cos_params, "cos_params", torch.float64)
-    if tuple(Wm.shape) != (135, F_REF):
-        raise ValueError(f"Wm: expected [135,1404], got {tuple(Wm.shape)}")
+    if Wm.dim() != 2 or Wm.shape[1] != F_REF:
+        raise ValueError(f"Wm: expected [27*R,1404], got {tuple(Wm.shape)}")
+    r_id = _lib.tucker_rank_of_rows(Wm.shape[0])
     if x.dim() != 2 or x.shape[1] != F_REF:
         raise ValueError(f"x: expected [M,1404], got {tuple(x.shape)}")
-    if params.dim() != 2 or params.shape[1] != 8:
-        raise ValueError(f"params: expected [N,8], got {tuple(params.shape)}")
+    if params.dim() != 2 or params.shape[1] != 3 + r_id:
+        raise ValueError(f"params: expected [N,{3 + r_id}] for Wm of identity rank {r_id}, got {tuple(params.shape)}")
     if tuple(cos_params.shape) != (3, 3, 4):
         raise ValueError(f"cos_params: expected [3,3,4], got {tuple(cos_params.shape)}")
     Wm, x, params, cos_params = Wm.contiguous(), x.contiguous(), params.contiguous(), cos_params.contiguous()
@@ -201,10 +202,10 @@ def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, co
     err = torch.empty((N,), dtype=torch.float64, device=x.device)
     xh = torch.empty((N, F_REF), dtype=torch.float64, device=x.device) if return_xhat else None
     with _on_device_of(("x", x), ("Wm", Wm), ("params", params), ("cos_params", cos_params), ("x_index", x_index)) as stream:
-        _lib.check(_lib.lib().nlml_tucker_objective_ex(
+        _lib.check(_lib.lib().nlml_tucker_objective_r(
             Wm.data_ptr(), x.data_ptr(), F_REF, x_index.data_ptr() if x_index is not None else None,
             params.data_ptr(), cos_params.data_ptr(), N, err.data_ptr(),
-            xh.data_ptr() if xh is not None else None, order, stream), "nlml_tucker_objective_ex")
+            xh.data_ptr() if xh is not None else None, r_id, order, stream), "nlml_tucker_objective_r")
     return (err, xh) if return_xhat else err
 
 
@@ -241,13 +242,18 @@ def tucker_powell(Wm: torch.Tensor, x: torch.Tensor, cos_params: torch.Tensor, x
     of the objective -- 6e-3 deg from scipy on clean grid faces (FX5), and on BASELINE config 3's noisy faces median 1.8e-3 deg (per face, largest of the three angles),
     10 % of the faces > 0.02 deg, 0.3 % > 1 deg, max 8.7 deg (bench.py extra.td_powell_fast_order reports it live).
 
-    Returns dict(x=f64[N,8] (w_y,w_p,w_r radians + u_id), fun=f64[N], nfev=i32[N], nit=i32[N], status=i32[N]).
+    Wm f32[27R,1404] for an identity rank R = 1..16 (5 for the shipped artefacts): n = 3 + R parameters per face, scipy's limits
+    maxiter = maxfev = 1000 n.
+
+    Returns dict(x=f64[N,3+R] (w_y,w_p,w_r radians + u_id), fun=f64[N], nfev=i32[N], nit=i32[N], status=i32[N]).
     """
     _need_cuda(Wm, "Wm", torch.float32)
     _need_cuda(x, "x", torch.float32)
     _need_cuda(cos_params, "cos_params", torch.float64)
-    if tuple(Wm.shape) != (135, F_REF):
-        raise ValueError(f"Wm: expected [135,1404], got {tuple(Wm.shape)}")
+    if Wm.dim() != 2 or Wm.shape[1] != F_REF:
+        raise ValueError(f"Wm: expected [27*R,1404], got {tuple(Wm.shape)}")
+    r_id = _lib.tucker_rank_of_rows(Wm.shape[0])
+    n_par = 3 + r_id
     if x.dim() != 2 or x.shape[1] != F_REF:
         raise ValueError(f"x: expected [N,1404], got {tuple(x.shape)}")
     if tuple(cos_params.shape) != (3, 3, 4):
@@ -256,21 +262,21 @@ def tucker_powell(Wm: torch.Tensor, x: torch.Tensor, cos_params: torch.Tensor, x
     N = x.shape[0]
     if x0 is not None:
         _need_cuda(x0, "x0", torch.float64)
-        if tuple(x0.shape) != (N, 8):
-            raise ValueError(f"x0: expected [{N},8], got {tuple(x0.shape)}")
+        if tuple(x0.shape) != (N, n_par):
+            raise ValueError(f"x0: expected [{N},{n_par}], got {tuple(x0.shape)}")
         x0 = x0.contiguous()
     order = _lib.td_order_from_name(order)
     dev = x.device
-    res = torch.empty((N, 8), dtype=torch.float64, device=dev)
+    res = torch.empty((N, n_par), dtype=torch.float64, device=dev)
     fun = torch.empty((N,), dtype=torch.float64, device=dev)
     nfev = torch.empty((N,), dtype=torch.int32, device=dev)
     nit = torch.empty((N,), dtype=torch.int32, device=dev)
     status = torch.empty((N,), dtype=torch.int32, device=dev)
     with _on_device_of(("x", x), ("Wm", Wm), ("cos_params", cos_params), ("x0", x0)) as stream:
-        _lib.check(_lib.lib().nlml_tucker_powell_ex(Wm.data_ptr(), x.data_ptr(), F_REF, cos_params.data_ptr(), N,
-                                                    x0.data_ptr() if x0 is not None else None, res.data_ptr(), fun.data_ptr(),
-                                                    nfev.data_ptr(), nit.data_ptr(), status.data_ptr(), order, stream),
-                   "nlml_tucker_powell_ex")
+        _lib.check(_lib.lib().nlml_tucker_powell_r(Wm.data_ptr(), x.data_ptr(), F_REF, cos_params.data_ptr(), N,
+                                                   x0.data_ptr() if x0 is not None else None, res.data_ptr(), fun.data_ptr(),
+                                                   nfev.data_ptr(), nit.data_ptr(), status.data_ptr(), r_id, order, stream),
+                   "nlml_tucker_powell_r")
     return {"x": res, "fun": fun, "nfev": nfev, "nit": nit, "status": status}
 
 

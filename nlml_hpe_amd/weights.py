@@ -99,10 +99,24 @@ def pack_blob(encoder_sd: dict, head_sds: dict, mode: int = _lib.MODE_F32) -> np
     return blob
 
 
+def check_tucker_rank(W, U_id) -> int:
+    """The identity rank R of a TD artefact pair: W [R,3,3,3,1404] and U_id [., R]; ValueError where they disagree or R is outside
+    the device path's range."""
+    W, U_id = np.asarray(W), np.asarray(U_id)
+    if W.ndim != 5 or W.shape[1:] != (3, 3, 3, 1404):
+        raise ValueError(f"W: expected [R,3,3,3,1404], got {W.shape}")
+    R = _lib.tucker_rank_of_rows(27 * W.shape[0], "W")
+    if U_id.ndim != 2 or U_id.shape[1] != R:
+        raise ValueError(f"U_id: expected [., {R}] next to W {W.shape}, got {U_id.shape}")
+    return R
+
+
 def load_tucker_artefacts(feature_dir: str = "outputs/features") -> dict:
-    """W, cosine parameters and factor matrices exactly as TD_Inference.py:40-51 reads them."""
+    """W, cosine parameters and factor matrices exactly as TD_Inference.py:40-51 reads them.  The identity rank R is the artefact's:
+    W [R,3,3,3,1404] with U_id [., R], R = 1..16 (5 in the shipped files)."""
     td = np.load(os.path.join(feature_dir, "Trained_data.npz"))
     fm = np.load(os.path.join(feature_dir, "Factor_Matrices.npz"))
+    check_tucker_rank(td["W"], fm["U_id"])
     return {
         "W": td["W"], "CoreTensor": td["CoreTensor"],
         "optimized_yaw": td["optimized_yaw"], "optimized_pitch": td["optimized_pitch"], "optimized_roll": td["optimized_roll"],
