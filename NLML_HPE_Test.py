@@ -36,6 +36,10 @@ def NLML_HPE_Tester(argv=None):
     ap.add_argument("--metrics", choices=["host", "device"], default="host",
                     help="host: gather every rank's poses to rank 0 and evaluate there (numpy + ATen); device: every rank evaluates its own "
                          "shard in one native pass (metrics.evaluate), only the partial records are gathered")
+    ap.add_argument("--normalization", choices=["ipd", "centroid"], default="ipd",
+                    help="landmark normalisation the encoder was trained on (helpers/FeatureExtractor.py:86-98 offers both): ipd = nose-tip origin and inter-pupillary distance (default, fused into the forward); centroid = centroid and RMS radius (its own kernel, then the forward)")
+    ap.add_argument("--print-poses", action="store_true",
+                    help="also print every processed face's rounded pose (index, yaw, pitch, roll in degrees; --metrics host, rank 0)")
     args = ap.parse_args(argv)
     warnings.filterwarnings("default")
 
@@ -78,7 +82,7 @@ def NLML_HPE_Tester(argv=None):
     if stop > start:
         # host-resident landmarks: copies overlapped with the kernel, straight out of the loaded array where it can be page-locked in place
         from nlml_hpe_amd.pipeline import HostPipeline
-        pose_np, valid_np = HostPipeline(model, batch=min(batch, 8192, stop - start)).run(raw_all[start:stop])
+        pose_np, valid_np = HostPipeline(model, batch=min(batch, 8192, stop - start), normalization=args.normalization).run(raw_all[start:stop])
         pose, valid = torch.from_numpy(pose_np).to(device), torch.from_numpy(valid_np).to(device)
     else:
         pose, valid = torch.zeros((0, 3), device=device), torch.zeros((0,), dtype=torch.bool, device=device)
@@ -96,6 +100,9 @@ def NLML_HPE_Tester(argv=None):
         keep = in_range & valid.cpu().numpy()                                         # zero rows = no face, :257-260
         print(f"processed {int(keep.sum())} of {n_total} samples "
               f"({int((~valid.cpu().numpy()).sum())} without landmarks, {int((~in_range).sum())} out of range)")
+        if args.print_poses:
+            for i in np.flatnonzero(keep):
+                print(f"pose {i}: {pred[i, 0]:.3f} {pred[i, 1]:.3f} {pred[i, 2]:.3f}")
         print("=============================Metrics for pred_angles_NLML_HPE:")
         res = metrics.compute_errors(gt_all[keep], pred[keep])
         print("\n======================================================================")

@@ -25,11 +25,17 @@ def inference(argv=None):
                     help="objective's operation order: reference = the reference's bits and scipy's own end point (default); "
                          "fast = f64 matrix cores (~3x the faces/s; NOT a parity mode: the end point is sensitive to the last bits of the "
                          "objective -- 6e-3 deg from scipy on clean grid faces, up to degrees on noisy ones)")
+    ap.add_argument("--normalization", choices=["ipd", "centroid"], default="ipd",
+                    help="landmark normalisation the decomposition was trained on (helpers/FeatureExtractor.py:86-98 offers both): ipd (default) "
+                         "or centroid = centroid and RMS radius")
     args = ap.parse_args(argv)
     torch.cuda.set_device(torch.device(args.device))
 
     raw = load_landmarks(args.image_path)
-    x = ops.normalize_ipd(torch.from_numpy(raw).cuda(), True)                  # get_feature_vector(..., normalize=True), :37
+    if args.normalization == "centroid":
+        x = ops.normalize_centroid(torch.from_numpy(raw).cuda())                # Normalization_using_Centroid, FeatureExtractor.py:17-28
+    else:
+        x = ops.normalize_ipd(torch.from_numpy(raw).cuda(), True)              # get_feature_vector(..., normalize=True), :37
     art = weights.load_tucker_artefacts("./outputs/features")
     u_id_shape = art["U_id"][1].size                                            # :51
     t0 = time.time()

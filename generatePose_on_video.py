@@ -53,7 +53,7 @@ def _collate(local: torch.Tensor, per: int, S: int, world: int) -> torch.Tensor:
     return out.transpose(0, 1).reshape((T, world * per) + tuple(local.shape[2:]))[:, :S]
 
 
-def process_video(source, output_path, model, save_output, device="cuda:0", world=1, rank=0):
+def process_video(source, output_path, model, save_output, device="cuda:0", world=1, rank=0, normalization="ipd"):
     if source == "synthetic":
         clips, width, height = _synthetic_clips(), 1920, 1080
     else:
@@ -72,7 +72,7 @@ def process_video(source, output_path, model, save_output, device="cuda:0", worl
     s0, s1, per = shard_bounds(S_all, world, rank)            # this rank's contiguous block of streams
     clips = clips[:, s0:s1]
     S = s1 - s0
-    tracker = VideoPoseTracker(model, S, width, height)
+    tracker = VideoPoseTracker(model, S, width, height, normalization=normalization)
     frames = torch.from_numpy(np.ascontiguousarray(clips)).to(device)
     lat = []
     out_sm, out_ep, out_valid = [], [], []
@@ -109,6 +109,8 @@ if __name__ == "__main__":
     parser.add_argument("--device", default="cuda:0")
     parser.add_argument("--mode", choices=["f16x2", "f16x2s", "f32", "bf16"], default=None,
                         help="kernel mode (default: NLML_HPE_MODE or f16x2s = strict-fast; f32 = strict parity; f16x2 = opt-in, 1.10x the reference's error; bf16 = throughput only)")
+    parser.add_argument("--normalization", choices=["ipd", "centroid"], default="ipd",
+                        help="landmark normalisation the encoder was trained on (helpers/FeatureExtractor.py:86-98 offers both): ipd = nose-tip origin and inter-pupillary distance (default, fused into the forward); centroid = centroid and RMS radius (its own kernel, then the forward)")
     args = parser.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world > 1:                                             # one rank per GPU; RCCL ("nccl") unless rehearsing on one GPU
@@ -123,6 +125,6 @@ if __name__ == "__main__":
     # the reference loads models/combined_model_scripted_prev.pth here (:289)
     mdl = resolve_model(dev, scripted_name="models/combined_model_scripted_prev.pth", mode=args.mode)
     mdl.eval()
-    process_video(args.source, args.output_path, mdl, args.save_output, dev, world, rank)
+    process_video(args.source, args.output_path, mdl, args.save_output, dev, world, rank, normalization=args.normalization)
     if world > 1:
         torch.distributed.destroy_process_group()

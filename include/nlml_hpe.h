@@ -57,6 +57,34 @@ int nlml_normalize_ipd(const float* raw, int64_t B, int normalize,
                        float* out, uint8_t* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K1c  Landmark normalisation by centroid and RMS radius: the reference's OTHER normalisation.
+ * Replaces Normalization_using_Centroid (helpers/FeatureExtractor.py:17-28), which get_feature_vector*
+ * offer as the alternative to the IPD form (:86-98), plus the f32 cast of its callers (:101).
+ *   raw      f32[B,468,3]
+ *   out      f32[B,1404]
+ *   valid    u8[B] or NULL: 0 where the RAW row is all zero (+0 or -0) -- the extractor's "no face"
+ *            sentinel (:105-106); that row's output is all zero (the bare function would give NaN;
+ *            the zero row is what get_feature_vector returns).  1 for every other row.
+ *   stats    f64[B,4] or NULL: centroid x, y, z and the scale (0, 0, 0, 0 for a sentinel row)
+ * The contract is the operation order, numpy's own, per face, with a[i][c] = (double)raw[i][c]:
+ *   1. sum_c = ((0.0 + a[0][c]) + a[1][c]) + ... + a[467][c], sequentially;  centroid_c = sum_c / 468.0
+ *   2. d[i][c] = a[i][c] - centroid_c;  q[i][c] = d[i][c] * d[i][c], each rounded on its own (no fma)
+ *   3. n[i] = (q[i][0] + q[i][1]) + q[i][2]
+ *   4. m = pairwise(n[0..467]) / 468.0 with numpy's pairwise sum: 468 -> 232 + 236 -> (112 + 120) +
+ *      (112 + 124); a leaf has eight accumulators seeded from its first eight elements, strides by 8,
+ *      combines as ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)) and adds the remainder sequentially
+ *   5. s = sqrt(m), correctly rounded;  out[i][c] = (float)(d[i][c] / s): an IEEE f64 divide, one
+ *      rounding to f32
+ * Identical landmarks give 0/0 = NaN as numpy does; NaN and Inf inputs propagate.  Bit-exact with the
+ * reference.  Errors and alignment as nlml_normalize_ipd (raw / out 16-byte aligned); stats 8-byte aligned.
+ *
+ * nlml_normalize_centroid_host evaluates the same order on HOST buffers in plain C++ (no HIP call, no
+ * alignment rule): the order can be pinned on a machine without a GPU.
+ */
+int nlml_normalize_centroid(const float* raw, int64_t B, float* out, uint8_t* valid, double* stats, void* stream);
+int nlml_normalize_centroid_host(const float* h_raw, int64_t B, float* h_out, uint8_t* h_valid, double* h_stats);
+
+/* ------------------------------------------------------------------------------------------
  * K2  Encoder + three heads, fused forward.
  * Replaces CombinedAnglePredictionModel.forward (NLML_HPE_Model_Builder.py:115-126), i.e.
  * LandmarkEncoder.forward (:55-68) and 3 x AnglePredictionNetwork.forward (:104-105), called

@@ -34,6 +34,9 @@ SYMBOLS = {
     "nlml_abi_version": (C.c_int, []),
     "nlml_last_error": (C.c_char_p, []),
     "nlml_normalize_ipd": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # raw, B, out, valid, stats[, stream]
+    "nlml_normalize_centroid": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlml_normalize_centroid_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_encoder_heads_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "nlml_encoder_heads_pack": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t]),

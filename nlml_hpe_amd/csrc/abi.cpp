@@ -8,6 +8,7 @@
 
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
+#include "centroid_ref.h"
 #include "layout.h"
 #include "powell.h"
 
@@ -38,6 +39,24 @@ int nlml_normalize_ipd(const float* raw, int64_t B, int normalize, float* out, u
   if ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(out)) & 15)
     return fail(NLML_E_BADARG, "normalize_ipd: raw/out must be 16-byte aligned");
   return launch_normalize_ipd(raw, B, normalize, out, valid, stream);
+}
+
+int nlml_normalize_centroid(const float* raw, int64_t B, float* out, uint8_t* valid, double* stats, void* stream) {
+  if (B < 0 || (B > 0 && (!raw || !out))) return fail(NLML_E_BADARG, "normalize_centroid: null buffer or negative B");
+  if ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(out)) & 15)
+    return fail(NLML_E_BADARG, "normalize_centroid: raw/out must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(stats) & 7) return fail(NLML_E_BADARG, "normalize_centroid: stats must be 8-byte aligned");
+  return launch_normalize_centroid(raw, B, out, valid, stats, stream);
+}
+
+// the same operation order (centroid_ref.h) on host buffers: plain C++, no HIP call
+int nlml_normalize_centroid_host(const float* h_raw, int64_t B, float* h_out, uint8_t* h_valid, double* h_stats) {
+  if (B < 0 || (B > 0 && (!h_raw || !h_out))) return fail(NLML_E_BADARG, "normalize_centroid_host: null buffer or negative B");
+  for (int64_t b = 0; b < B; ++b) {
+    const int v = cn_face_host(h_raw + b * NLML_F_REFERENCE, h_out + b * NLML_F_REFERENCE, h_stats ? h_stats + 4 * b : nullptr);
+    if (h_valid) h_valid[b] = (uint8_t)v;
+  }
+  return 0;
 }
 
 size_t nlml_encoder_heads_packed_bytes(int F, int mode) {

@@ -88,6 +88,8 @@ int launch_mode5_product(const float* core, const float* U, int Q, int R5, int M
 // normalize_ipd.hip
 int launch_normalize_ipd(const float* raw, int64_t B, int normalize, float* out, uint8_t* valid,
                          void* stream);
+// normalize_centroid.hip
+int launch_normalize_centroid(const float* raw, int64_t B, float* out, uint8_t* valid, double* stats, void* stream);
 // tucker_objective.hip
 int launch_tucker_objective(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index,
                             const double* params, const double* cos_params, int64_t N,

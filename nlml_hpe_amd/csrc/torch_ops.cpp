@@ -72,6 +72,19 @@ at::Tensor normalize_ipd(const at::Tensor& raw_, bool normalize) {
   return out;
 }
 
+// the reference's other normalisation (centroid and RMS radius): features only -- the face mask and the statistics come from the Python
+// wrapper, ops.normalize_centroid
+at::Tensor normalize_centroid(const at::Tensor& raw_) {
+  need(raw_, "raw", at::kFloat);
+  TORCH_CHECK(raw_.dim() == 3 && raw_.size(1) == 468 && raw_.size(2) == 3, "raw: expected [B,468,3], got ", raw_.sizes());
+  const at::Tensor raw = raw_.contiguous();
+  const int64_t B = raw.size(0);
+  at::Tensor out = at::empty({B, F_REF}, raw.options());
+  OnDevice dev(raw);
+  check(nlml_normalize_centroid(raw.data_ptr<float>(), B, out.data_ptr<float>(), nullptr, nullptr, dev.stream), "nlml_normalize_centroid");
+  return out;
+}
+
 // The K2 forwards: the checks, the allocation and the call behind the five forward ops and landmarks_to_pose_valid.  in_ is the raw
 // landmarks [B,468,3] (landmarks) or the feature rows [B,F]; ws given = the layer-per-launch path through that workspace, else the fused
 // launch; want_valid adds the "a face was found" mask u8[B] (row not all-zero).
@@ -285,6 +298,7 @@ std::tuple<at::Tensor, at::Tensor> pose_eval_merge(const at::Tensor& records_, i
 
 // ---- shapes only (Meta backend: tracing / fake tensors) -------------------------------------------------------------
 at::Tensor normalize_ipd_meta(const at::Tensor& raw, bool) { return at::empty({raw.size(0), F_REF}, raw.options()); }
+at::Tensor normalize_centroid_meta(const at::Tensor& raw) { return at::empty({raw.size(0), F_REF}, raw.options()); }
 template <class... Rest> at::Tensor pose_meta(const at::Tensor& x, const at::Tensor&, Rest...) { return at::empty({x.size(0), 3}, x.options()); }
 at::Tensor tucker_objective_meta(const at::Tensor&, const at::Tensor&, const at::Tensor& params, const at::Tensor&, std::string) {
   return at::empty({params.size(0)}, params.options());
@@ -316,6 +330,7 @@ std::tuple<at::Tensor, at::Tensor> pose_eval_merge_meta(const at::Tensor& record
 
 TORCH_LIBRARY(nlml_hpe, m) {
   m.def("normalize_ipd(Tensor raw, bool normalize) -> Tensor");
+  m.def("normalize_centroid(Tensor raw) -> Tensor");
   m.def("encoder_heads_fwd(Tensor x, Tensor packed_w, int F) -> Tensor");
   m.def("landmarks_to_pose(Tensor raw, Tensor packed_w, bool normalize) -> Tensor");
   m.def("encoder_heads_fwd_small(Tensor x, Tensor packed_w, int F, Tensor workspace) -> Tensor");
@@ -333,6 +348,7 @@ TORCH_LIBRARY(nlml_hpe, m) {
 
 TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CUDA key
   m.impl("normalize_ipd", &normalize_ipd);
+  m.impl("normalize_centroid", &normalize_centroid);
   m.impl("encoder_heads_fwd", &encoder_heads_fwd);
   m.impl("landmarks_to_pose", &landmarks_to_pose);
   m.impl("encoder_heads_fwd_small", &encoder_heads_fwd_small);
@@ -348,6 +364,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
 
 TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("normalize_ipd", &normalize_ipd_meta);
+  m.impl("normalize_centroid", &normalize_centroid_meta);
   m.impl("encoder_heads_fwd", &pose_meta<int64_t>);
   m.impl("landmarks_to_pose", &pose_meta<bool>);
   m.impl("encoder_heads_fwd_small", &pose_meta<int64_t, const at::Tensor&>);

@@ -15,6 +15,15 @@ import torch
 from . import _lib, ops, weights
 
 
+NORMALIZATIONS = ("ipd", "centroid")   # the reference's two landmark normalisations (FeatureExtractor.py:86-98)
+
+
+def check_normalization(name: str) -> str:
+    if name not in NORMALIZATIONS:
+        raise ValueError(f"unknown normalization {name!r}; expected one of {list(NORMALIZATIONS)}")
+    return name
+
+
 class HIPPoseModel:
     """CombinedAnglePredictionModel (Model_Builder.py:107-126) on the fused gfx950 kernel."""
 
@@ -92,10 +101,22 @@ class HIPPoseModel:
         return 0 < B <= self.small_batch_max(self.mode)
 
     def from_landmarks(self, raw: torch.Tensor, normalize: bool = True, return_latent: bool = False,
-                       return_valid: bool = False):
-        """raw FaceMesh landmarks f32[B,468,3] -> f32[B,3] radians, normalisation fused into the launch."""
+                       return_valid: bool = False, normalization: str = "ipd"):
+        """raw FaceMesh landmarks f32[B,468,3] -> f32[B,3] radians.  normalization: "ipd" (the default), fused into the launch, or
+        "centroid" (the reference's other normalisation, FeatureExtractor.py:17-28): its own kernel, then the features forward --
+        the same bits as self.forward_packed(ops.normalize_centroid(raw)); valid is then "the raw row is not all zero"."""
         if self.input_size != ops.F_REF:
             raise ValueError("from_landmarks needs the reference input width 1404")
+        normalization = check_normalization(normalization)
+        if normalization == "centroid":
+            if not normalize:
+                raise ValueError('normalization="centroid" with normalize=False: un-normalised landmarks are the "ipd" form\'s normalize=False')
+            res = ops.normalize_centroid(raw.to(self.device, torch.float32), return_valid=return_valid)
+            feats, valid = res if return_valid else (res, None)
+            out = self.forward_packed(feats, return_latent=return_latent)
+            if not return_valid:
+                return out
+            return (*out, valid) if return_latent else (out, valid)
         fwd = ops.landmarks_to_pose_small if self._small(raw.shape[0]) else ops.landmarks_to_pose
         return fwd(raw.to(self.device, torch.float32), self.blob, normalize,
                    return_latent=return_latent, return_valid=return_valid)

@@ -69,6 +69,29 @@ def normalize_ipd(raw: torch.Tensor, normalize: bool = True, return_valid: bool 
     return (out, valid.bool()) if return_valid else out
 
 
+def normalize_centroid(raw: torch.Tensor, return_valid: bool = False, return_stats: bool = False):
+    """raw f32[B,468,3] -> features f32[B,1404] normalised by centroid and RMS radius (FeatureExtractor.py:17-28,101), bit-exact
+    [, valid bool[B]: the raw row is not the all-zero "no face" sentinel (whose features are all zero)]
+    [, stats f64[B,4]: centroid x, y, z and the scale]."""
+    _need_cuda(raw, "raw", torch.float32)
+    raw = _raw_rows(raw)
+    B = raw.shape[0]
+    out = torch.empty((B, F_REF), dtype=torch.float32, device=raw.device)
+    valid = torch.empty((B,), dtype=torch.uint8, device=raw.device) if return_valid else None
+    stats = torch.empty((B, 4), dtype=torch.float64, device=raw.device) if return_stats else None
+    with _on_device_of(("raw", raw)) as stream:
+        _lib.check(_lib.lib().nlml_normalize_centroid(raw.data_ptr(), B, out.data_ptr(),
+                                                      valid.data_ptr() if valid is not None else None,
+                                                      stats.data_ptr() if stats is not None else None, stream),
+                   "nlml_normalize_centroid")
+    res = [out]
+    if return_valid:
+        res.append(valid.bool())
+    if return_stats:
+        res.append(stats)
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 # ---- the K2 forward (encoder + heads): one private forward behind the five public wrappers ---------------------------------------
 _k2_ws: dict = {}
 
@@ -226,7 +249,7 @@ def _load_torch_ops():
     _lib.lib()                                  # the C ABI library the shim links against, checked symbol by symbol first
     torch.ops.load_library(TORCH_OPS_PATH)
     # the registered ops; *_small take an explicit workspace, landmarks_to_pose_valid is the video tick's forward (pose + face mask)
-    for name in ("normalize_ipd", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
+    for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_powell", "video_post", "cosine_table", "pose_eval",
                  "pose_eval_merge"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it

@@ -24,10 +24,14 @@ import torch
 
 
 class HostPipeline:
-    def __init__(self, model, batch: int = 8192, normalize: bool = True, workers: int | None = None):
+    def __init__(self, model, batch: int = 8192, normalize: bool = True, workers: int | None = None, normalization: str = "ipd"):
         # (8,192 faces = 46 MB per batch: 0.8 ms of DMA against 0.15 ms of kernel, and a 65,536-face call already has eight batches to overlap:
         # 8.7 M faces/s where one 65,536-face batch -- nothing to overlap -- gives 5.6 M; tools/host_pipeline_sweep.py)
         self.model, self.batch, self.normalize = model, int(batch), normalize
+        from .model import check_normalization
+        self.normalization = check_normalization(normalization)    # "ipd" | "centroid", as HIPPoseModel.from_landmarks
+        if self.normalization == "centroid" and not normalize:
+            raise ValueError('normalization="centroid" with normalize=False')
         dev = model.device
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.out_stream = torch.cuda.Stream(device=dev)     # poses back to the host: not behind the next batch's landmarks
@@ -41,6 +45,8 @@ class HostPipeline:
         self.pool = ThreadPoolExecutor(self.workers)
         self.pin_in_np = None
         self.last_mode = None
+        # (a model object without the keyword -- anything with the old from_landmarks signature -- keeps working with the default)
+        self._norm_kw = {"normalization": "centroid"} if self.normalization == "centroid" else {}
 
     def _ensure_staging(self):
         if self.pin_in is None:
@@ -139,7 +145,7 @@ class HostPipeline:
             if i + 1 < len(starts):
                 stage(i + 1)                        # overlaps with the kernel of batch i
             compute.wait_event(h2d_done[i])
-            p, v = self.model.from_landmarks(self.dev_in[slot][:m], self.normalize, return_valid=True)
+            p, v = self.model.from_landmarks(self.dev_in[slot][:m], self.normalize, return_valid=True, **self._norm_kw)
             k_done[i].record(compute)
             outs[i] = (p, v)
             with torch.cuda.stream(self.out_stream):

@@ -17,7 +17,9 @@ AXIS_SIZE = 80.0         # :73
 
 class VideoPoseTracker:
     def __init__(self, model, streams: int, frame_w: int, frame_h: int, alpha: float = ALPHA,
-                 max_jump: float = MAX_CENTER_JUMP, size: float = AXIS_SIZE):
+                 max_jump: float = MAX_CENTER_JUMP, size: float = AXIS_SIZE, normalization: str = "ipd"):
+        from .model import check_normalization
+        self.normalization = check_normalization(normalization)   # "centroid": its own kernel, then the features forward (two launches)
         self.model, self.S = model, int(streams)
         self.frame_w, self.frame_h = float(frame_w), float(frame_h)
         self.alpha, self.max_jump, self.size = float(alpha), float(max_jump), float(size)
@@ -58,8 +60,12 @@ class VideoPoseTracker:
         ops._need_cuda(raw, "raw", torch.float32)
         if tuple(raw.shape) != (self.S, 468, 3):
             raise ValueError(f"expected landmarks [{self.S},468,3]")
-        ws = ops._small_workspace(self.S, ops.F_REF, m.device) if m._small(self.S) else None
-        pose, valid = torch.ops.nlml_hpe.landmarks_to_pose_valid(raw, m.blob, True, ws)
+        if self.normalization == "centroid":
+            pose, found = m.from_landmarks(raw, return_valid=True, normalization="centroid")
+            valid = found.view(torch.uint8)
+        else:
+            ws = ops._small_workspace(self.S, ops.F_REF, m.device) if m._small(self.S) else None
+            pose, valid = torch.ops.nlml_hpe.landmarks_to_pose_valid(raw, m.blob, True, ws)
         torch.ops.nlml_hpe.video_post(pose, raw, valid, self.frame_w, self.frame_h, self.alpha, self.max_jump, self.size,
                                       self.state, self.smoothed, self.centre, self.endpoints, self.updated)
         return self.smoothed, self.centre, self.endpoints, self.updated.bool()
