@@ -323,6 +323,11 @@ int nlml_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const dou
  *                           zero-initialise before the first tick
  *   smoothed  f64[S,3] degrees; centre f64[S,2] pixels; endpoints f64[S,3,2] pixels (x,y of the red,
  *             green, blue axis tips; the reference draws int() of them)
+ * Parity: every f64 operation is rounded on its own in the reference's Python order (no fma contraction), so smoothed, centre and
+ * state are the reference's values bit for bit -- for any S, every stream independent of the others -- given that round(x, 2) is
+ * rint(x*100)/100 (it is, unless x*100 lies within an ulp of a .5 tie).  The end points go through the device library's sin / cos
+ * instead of the host libm's and stay within eps * (26*size + |centre| + 2*size) of the reference's, eps = 2^-52
+ * (tests/test_video_post_gpu.py derives it); int() of them agrees unless the value lies that close to an integer.
  */
 int nlml_video_post(const float* pose_rad, const float* raw, const uint8_t* valid, int64_t S,
                     double frame_w, double frame_h, double alpha, double max_jump, double size,

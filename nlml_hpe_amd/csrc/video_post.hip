@@ -12,9 +12,16 @@
 // does not change and its outputs are left untouched; so is a stream whose pose is not finite.  `updated` (optional) tells the
 // caller which streams' ticks were applied, so a skipped stream is never reported with stale outputs as if they were new.
 //
-// One thread per stream, all f64 (the reference computes in Python floats).  round(x, 2) is
-// rint(x*100)/100 (half-to-even), which equals Python's correctly-rounded round() except when
-// x*100 lies within an ulp of a .5 tie.
+// One thread per stream, all f64 (the reference computes in Python floats), every operation rounded on its own in Python's order
+// (#pragma clang fp contract(off): left to itself hipcc fuses alpha*new + (1-alpha)*s and dx*dx + dy*dy into fma, and the smoothed
+// angle -- which feeds back into the state -- leaves the reference's bits by an ulp).  What that buys:
+//   smoothed, centre, state   bit for bit the reference's Python arithmetic: IEEE mul / div / add / sqrt / rint only
+//   end points                the same expression tree, but sin / cos are the device library's, not the host libm's: within
+//                             eps * (26 * size + |centre| + 2 * size), eps = 2^-52 (derived in tests/test_video_post_gpu.py from
+//                             <= 2 ulp device + <= 1 ulp host per trig factor); int() of them, which is what gets drawn, agrees
+//                             unless the value lies that close to an integer
+// round(x, 2) is rint(x*100)/100 (half-to-even), which equals Python's correctly-rounded round() except when x*100 lies within
+// an ulp of a .5 tie (not reachable from an f32 pose: tests/test_video_replay_host.py checks every pose the tests use).
 #include <hip/hip_runtime.h>
 
 #include "../../include/nlml_hpe.h"
@@ -27,6 +34,7 @@ __global__ void video_post_kernel(const float* __restrict__ pose_rad, const floa
                                   double alpha, double max_jump, double size, double* __restrict__ state,
                                   double* __restrict__ smoothed, double* __restrict__ centre,
                                   double* __restrict__ endpoints, uint8_t* __restrict__ updated) {
+#pragma clang fp contract(off)   // Python rounds alpha*new, (1-alpha)*s and their sum separately (:220-222); dx**2 + dy**2 (:98) too
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
   if (updated) updated[s] = 0;              // set to 1 below only if this stream's tick is applied
@@ -58,8 +66,8 @@ __global__ void video_post_kernel(const float* __restrict__ pose_rad, const floa
   st[3] = tdx; st[4] = tdy; st[5] += 1.0;
   if (updated) updated[s] = 1;
   centre[s * 2 + 0] = tdx; centre[s * 2 + 1] = tdy;
-  const double kRad = 3.141592653589793 / 180.0;
-  const double pitch = ang[1] * kRad, yaw = -(ang[0] * kRad), roll = ang[2] * kRad;   // :74-76
+  const double kPi = 3.141592653589793;     // np.pi; x * np.pi / 180 is two roundings (:74-76), not x * (pi/180)
+  const double pitch = ang[1] * kPi / 180.0, yaw = -(ang[0] * kPi / 180.0), roll = ang[2] * kPi / 180.0;
   double* ep = endpoints + s * 6;
   ep[0] = size * (cos(yaw) * cos(roll)) + tdx;                                        // :110-119
   ep[1] = size * (cos(pitch) * sin(roll) + cos(roll) * sin(pitch) * sin(yaw)) + tdy;

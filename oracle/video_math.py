@@ -18,13 +18,18 @@ MAX_CENTER_JUMP = 100       # :136
 AXIS_SIZE = 80              # :73 default
 
 
+def ema_step(s, pose_rad, alpha: float = ALPHA):
+    """One prediction: s = the smoothed [yaw, pitch, roll] so far (None before the first) -> the new one, Python floats."""
+    new = [round(float(np.degrees(float(v))), 2) for v in pose_rad]    # :211
+    return new if s is None else [alpha * n + (1 - alpha) * o for n, o in zip(new, s)]  # :215-222
+
+
 def ema_sequence(poses_rad: np.ndarray, alpha: float = ALPHA) -> np.ndarray:
     """poses_rad f32/f64[T,3] model outputs (radians) -> smoothed degrees f64[T,3]."""
     out = np.empty((len(poses_rad), 3), dtype=np.float64)
     s = None
     for t, pr in enumerate(poses_rad):
-        new = [round(float(np.degrees(float(v))), 2) for v in pr]    # :211
-        s = new if s is None else [alpha * n + (1 - alpha) * o for n, o in zip(new, s)]  # :215-222
+        s = ema_step(s, pr, alpha)
         out[t] = s
     return out
 
@@ -50,3 +55,34 @@ def axes_on_face(prev_tdx, prev_tdy, frame_w, frame_h, nose, left_eye, right_eye
     x3 = size * (sin(yaw)) + tdx
     y3 = size * (-cos(yaw) * sin(pitch)) + tdy
     return tdx, tdy, (x1, y1), (x2, y2), (x3, y3)
+
+
+def replay(poses_rad, landmarks, valid, frame_w, frame_h, alpha=ALPHA, max_jump=MAX_CENTER_JUMP, size=AXIS_SIZE):
+    """process_video's loop (:181-229) for S streams side by side, each with its own (smoothed, previous centre, count).
+
+    poses_rad f32[T,S,3], landmarks f32[T,S,468,3], valid bool[T,S] (False = no face, the `continue` of :193-196).  A tick whose
+    pose is not finite is skipped the same way (the reference raises there, :121; the device keeps the stream's state).
+    Returns a dict of f64 arrays: smoothed [T,S,3], centre [T,S,2], endpoints [T,S,3,2], state [T,S,6] = [sm_y, sm_p, sm_r, tdx, tdy,
+    count] as the kernel lays it out, and updated bool[T,S].  A skipped tick repeats the stream's previous values (zeros before its
+    first applied tick, like freshly allocated device buffers)."""
+    T, S = np.shape(poses_rad)[:2]
+    out = {"smoothed": np.zeros((T, S, 3)), "centre": np.zeros((T, S, 2)), "endpoints": np.zeros((T, S, 3, 2)),
+           "state": np.zeros((T, S, 6)), "updated": np.zeros((T, S), dtype=bool)}
+    for s in range(S):
+        sm, prev, count = None, (None, None), 0
+        for t in range(T):
+            if t:
+                for k in ("smoothed", "centre", "endpoints", "state"):
+                    out[k][t, s] = out[k][t - 1, s]
+            pr = poses_rad[t, s]
+            if not valid[t, s] or not all(math.isfinite(float(v)) for v in pr):
+                continue
+            sm = ema_step(sm, pr, alpha)
+            lm = landmarks[t, s]
+            tdx, tdy, p1, p2, p3 = axes_on_face(prev[0], prev[1], frame_w, frame_h, lm[1], lm[33], lm[263], *sm,
+                                                size=size, max_jump=max_jump)
+            prev, count = (tdx, tdy), count + 1
+            out["smoothed"][t, s], out["centre"][t, s], out["endpoints"][t, s] = sm, (tdx, tdy), (p1, p2, p3)
+            out["state"][t, s] = (*sm, tdx, tdy, count)
+            out["updated"][t, s] = True
+    return out

@@ -324,9 +324,9 @@ def test_fx7_video_post_on_device(head_sds, golden_dir, device):
         if t in no_face:
             continue
         fr = recs[t]
-        assert np.allclose(sm.cpu().numpy()[0], fr["smoothed"], rtol=0, atol=1e-9)
+        assert np.array_equal(sm.cpu().numpy()[0], fr["smoothed"])      # the reference's bits: K4 rounds every operation on its own
         cc = c.cpu().numpy()[0]
-        assert np.allclose(cc, fr["centre"], rtol=0, atol=1e-9)
+        assert np.array_equal(cc, fr["centre"])
         e = ep.cpu().numpy()[0]
         got = [[[int(cc[0]), int(cc[1])], [int(e[k, 0]), int(e[k, 1])]] for k in range(3)]
         assert got == fr["lines"], (t, got, fr["lines"])
