@@ -310,6 +310,29 @@ int nlml_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const dou
                          int32_t* status, int r_id, int order, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K3g -- objective value AND analytic gradient in one call (TD_Tester.py:60-102, compute_gradient: the jac= the reference hands to
+ * scipy.optimize.minimize, :194,253-256), in the reference's own operation order, for r_id = NLML_TUCKER_RANK_MIN..NLML_TUCKER_RANK_MAX:
+ *   err   f64[N] or NULL      the bits of nlml_tucker_objective_r(..., NLML_TD_ORDER_REFERENCE)
+ *   grad  f64[N, 3 + r_id]    (d/dw_y, d/dw_p, d/dw_r, d/du[r_id]); every component is the reference's, bit for bit:
+ *       df = float32(((-a) b) sin(b w + c)) with a correctly rounded sin; the four einsums 'ijklm,i,j,k,l->m' in numpy's generic loop
+ *       order; np.sum(r * e) by numpy's pairwise tree; the identity term as the reference writes it (:96-97: the inner einsum
+ *       'ijklm,j,k,l->m' runs in f32 and sums over i as well; the outer 'ijklm,m->i' in numpy's buffered two-lane order).
+ *       csrc/tucker_grad_ref.h states the order.
+ *   workspace   nlml_tucker_gradient_workspace_bytes(N, r_id) bytes of device memory, 8-byte aligned (the chains' rows and r * v; about
+ *       56 KB per evaluation); the call leaves nothing in it that a later call needs.
+ * Arguments, error codes and alignment otherwise as for nlml_tucker_objective_r in NLML_TD_ORDER_REFERENCE: r_id out of range ->
+ * NLML_E_SHAPE; negative N, a null buffer, ldx < 1404, a workspace that is too small -> NLML_E_BADARG.  Two launches on `stream`.
+ * nlml_tucker_gradient_host: the same arithmetic on HOST buffers in plain C++ (no GPU involved) -- the restatement the device kernels
+ * are held to; h_v f32[N,1404] or NULL receives the f32 einsum of the identity term (for tests). */
+size_t nlml_tucker_gradient_workspace_bytes(int64_t N, int r_id);   /* 0 for N <= 0 or an r_id out of range */
+int nlml_tucker_gradient_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index,
+                           const double* params, const double* cos_params, int64_t N,
+                           double* err, double* grad, int r_id, void* workspace, size_t workspace_bytes, void* stream);
+int nlml_tucker_gradient_host(const float* h_Wm, const float* h_x, int64_t ldx, const int32_t* h_x_index,
+                              const double* h_params, const double* h_cos_params, int64_t N,
+                              double* h_err, double* h_grad, int r_id, float* h_v);
+
+/* ------------------------------------------------------------------------------------------
  * K4  Video post-processing for S concurrent streams, one frame tick per call.
  * Replaces, per stream (generatePose_on_video.py): round(np.degrees(.), 2) (:211), the exponential
  * smoothing s = alpha*new + (1-alpha)*s seeded by the first prediction (:215-224, alpha 0.4 at :179),

@@ -5,7 +5,7 @@ Same names and argument meaning as /root/reference/TD_Tester.py for the function
   objective(params, W, x, params_y, params_p, params_r)   :31-58   -> float (one evaluation, K3 kernel)
   compute_gradient(params, W, x, params_y, params_p, params_r) :60-102 -> f64[8] (the jac= the reference hands to Powell)
   Test(W, x, u_id_shape, Py, Pp, Pr, u_id, f_y, f_p, f_r) :162-291 -> (yaw deg, pitch deg, roll deg, u_id)
-plus the batched forms this build adds: objective_batch, compute_gradient_batch, Test_batch.
+plus the batched forms this build adds: objective_batch, compute_gradient_batch, value_and_gradient_batch, Test_batch.
 The module-level debug lists of the reference (:18-22, appended on every call, unbounded) are not kept.
 """
 from __future__ import annotations
@@ -95,14 +95,36 @@ def objective(params, W, x, params_y, params_p, params_r, order=ORDER_REFERENCE)
     return float(objective_batch(np.asarray(params, dtype=np.float64)[None], W, x, params_y, params_p, params_r, order=order)[0])
 
 
-def compute_gradient_batch(params, W, X, params_y, params_p, params_r):
+def value_and_gradient_batch(params, W, X, params_y, params_p, params_r, x_index=None):
+    """Objective and analytic gradient (:31-58, :60-102) of N evaluations in one native call (K3g), both in the reference's own
+    operation order: err carries objective_batch's bits, every gradient component the reference's.  params f64[N,3+R]; X f32[M,1404]
+    (M == N, or rows selected by x_index i32[N]) -> (err f64[N], grad f64[N,3+R]) (numpy) -- what scipy's gradient methods (the
+    reference's L-BFGS-B alternative, :253-256) consume per step."""
+    Wm = _wm(W)
+    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3 + Wm.shape[0] // 27)).to(_dev())
+    xi = None if x_index is None else torch.from_numpy(np.ascontiguousarray(x_index, dtype=np.int32)).to(_dev())
+    err, grad = ops.tucker_gradient(Wm, _x(X), P, _cos(params_y, params_p, params_r), x_index=xi)
+    return err.cpu().numpy(), grad.cpu().numpy()
+
+
+IMPL_LIBRARY, IMPL_NATIVE = "library", "native"
+
+
+def compute_gradient_batch(params, W, X, params_y, params_p, params_r, impl=IMPL_LIBRARY):
     """Analytic gradient of the objective (:60-102) for N evaluations at once, on the device in f64.
+
+    impl="native": the K3g kernels (value_and_gradient_batch), the reference's gradient bit for bit.  impl="library" (the default,
+    unchanged): the regrouped form below -- angles within 1e-10 of scale, the identity part within f32 rounding.
 
     With c = u (x) f_y (x) f_p (x) f_r, r = x - c^T Wm (x_hat from the K3 kernel) and g = Wm r, the reference's four
     gradient einsums are dot products with g:  d/dw_a = -<dc/dw_a, g>, dc/dw_y = u (x) f_y' (x) f_p (x) f_r with
     f' = f32(-a b sin(b w + c)) (:80-95).  The identity-mode term is reproduced as the reference writes it (:96): its inner
     einsum also sums over i, so grad_u[i] = -sum_m S[i,m] r[m] v[m], v = (1 (x) f_y (x) f_p (x) f_r)^T Wm, S[i] = sum_jkl W[i,j,k,l].
     The three small GEMMs are library f64 matmuls (rocBLAS through torch).  -> f64[N,3+R] (numpy), R = W's identity rank."""
+    if impl == IMPL_NATIVE:
+        return value_and_gradient_batch(params, W, X, params_y, params_p, params_r)[1]
+    if impl != IMPL_LIBRARY:
+        raise ValueError(f"unknown impl {impl!r}; expected 'library' or 'native'")
     dev = _dev()
     Wm = _wm(W)
     R = Wm.shape[0] // 27
@@ -134,9 +156,9 @@ def compute_gradient_batch(params, W, X, params_y, params_p, params_r):
     return torch.cat([gy[:, None], gp[:, None], gr[:, None], gu], dim=1).cpu().numpy()
 
 
-def compute_gradient(params, W, x, params_y, params_p, params_r):
-    """Same signature as the reference (:60); x may be a torch tensor or an array.  -> f64[3+R]."""
-    return compute_gradient_batch(np.asarray(params, dtype=np.float64)[None], W, x, params_y, params_p, params_r)[0]
+def compute_gradient(params, W, x, params_y, params_p, params_r, impl=IMPL_LIBRARY):
+    """Same signature as the reference (:60); x may be a torch tensor or an array.  -> f64[3+R].  impl as in compute_gradient_batch."""
+    return compute_gradient_batch(np.asarray(params, dtype=np.float64)[None], W, x, params_y, params_p, params_r, impl=impl)[0]
 
 
 def Test_batch(W, X, u_id_shape, optimized_params_y, optimized_params_p, optimized_params_r, return_info=False,

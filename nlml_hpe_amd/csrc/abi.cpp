@@ -11,6 +11,7 @@
 #include "centroid_ref.h"
 #include "layout.h"
 #include "powell.h"
+#include "tucker_grad_ref.h"
 
 namespace nlml {
 static thread_local char g_err[256] = "";
@@ -383,6 +384,43 @@ int nlml_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const dou
   if (N > 0 && order == NLML_TD_ORDER_FAST)
     if (int rc = check_td_fast_alignment(Wm, x, ldx, "tucker_powell_r")) return rc;
   return launch_tucker_powell_r(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, r_id, order, stream);
+}
+
+// ---- K3g: objective value + analytic gradient, reference order ---------------------------------------------------------------
+size_t nlml_tucker_gradient_workspace_bytes(int64_t N, int r_id) { return rank_ok(r_id) ? tucker_gradient_workspace_bytes(N) : 0; }
+
+static int check_gradient_args(const char* who, const void* Wm, const void* x, int64_t ldx, const void* params, const void* cos_params,
+                               int64_t N, const void* grad, int r_id) {
+  static thread_local char msg[160];
+  if (!rank_ok(r_id)) return bad_rank(who, r_id);
+  const char* what = nullptr;
+  if (N < 0) what = "negative N";
+  else if (N > 0 && (!Wm || !x || !params || !cos_params || !grad)) what = "null buffer";
+  else if (N > 0 && ldx < NLML_F_REFERENCE) what = "ldx < 1404";
+  if (!what) return 0;
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return fail(NLML_E_BADARG, msg);
+}
+
+int nlml_tucker_gradient_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                           const double* cos_params, int64_t N, double* err, double* grad, int r_id, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  if (int rc = check_gradient_args("tucker_gradient_r", Wm, x, ldx, params, cos_params, N, grad, r_id)) return rc;
+  const size_t need = tucker_gradient_workspace_bytes(N);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(NLML_E_BADARG, "tucker_gradient_r: workspace too small");
+  if (misaligned8(workspace) || misaligned8(err) || misaligned8(grad) || misaligned8(params))
+    return fail(NLML_E_BADARG, "tucker_gradient_r: f64 buffers and the workspace must be 8-byte aligned");
+  return launch_tucker_gradient(Wm, x, ldx, x_index, params, cos_params, N, err, grad, r_id, workspace, stream);
+}
+
+// the same operation order (tucker_grad_ref.h) on host buffers: plain C++, no HIP call
+int nlml_tucker_gradient_host(const float* h_Wm, const float* h_x, int64_t ldx, const int32_t* h_x_index, const double* h_params,
+                              const double* h_cos_params, int64_t N, double* h_err, double* h_grad, int r_id, float* h_v) {
+  if (int rc = check_gradient_args("tucker_gradient_host", h_Wm, h_x, ldx, h_params, h_cos_params, N, h_grad, r_id)) return rc;
+  for (int64_t n = 0; n < N; ++n)
+    tg_gradient_host(h_Wm, h_x + (h_x_index ? (int64_t)h_x_index[n] : n) * ldx, h_params + n * (3 + r_id), h_cos_params, r_id,
+                     h_err ? h_err + n : nullptr, h_grad + n * (3 + r_id), h_v ? h_v + n * NLML_F_REFERENCE : nullptr);
+  return 0;
 }
 
 // host-side stepping for n = 3 + r_id parameters: the state the rank-aware device kernel runs

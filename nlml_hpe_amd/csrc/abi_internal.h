@@ -107,6 +107,11 @@ int launch_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const d
                            double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order,
                            void* stream);
 
+// tucker_gradient.hip (K3g): objective value and analytic gradient in the reference's operation order; workspace = the chains' rows + t
+size_t tucker_gradient_workspace_bytes(int64_t N);
+int launch_tucker_gradient(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                           const double* cos_params, int64_t N, double* err, double* grad, int r_id, void* workspace, void* stream);
+
 // video_post.hip
 int launch_video_post(const float* pose_rad, const float* raw, const uint8_t* valid, int64_t S, double frame_w,
                       double frame_h, double alpha, double max_jump, double size, double* state, double* smoothed,

@@ -14,6 +14,8 @@
 //   |x| <= 2^20: k = rint(x * 2/pi), r = x - k*pi/2 with pi/2 as four doubles (212 bits), cos/sin of r (|r| <= pi/4 + eps) by
 //                their Taylor series to r^30 / r^31 in double-double Horner form, quadrant fix-up;
 //   otherwise (never the case for the f-vectors: |b*w + c| < 10) the library cos.
+// cr_sin is the same evaluation read at the other column of the quadrant table: the derivative of the f-vectors in the analytic
+// gradient (df = float32(-a*b*sin(b*w + c)), TD_Tester.py:82,87,92; tucker_grad_ref.h); tests/test_td_gradient_host.py checks it.
 #pragma once
 #include <math.h>
 
@@ -106,9 +108,11 @@ constexpr double CR_SC[16][2] = {
     {0x1.434d2e783f5bcp-113, 0x1.0b87b91be9affp-167},
 };
 
-NLML_CR_HD double cr_cos(double x) {
+// cos(x) (SIN = false) or sin(x) (SIN = true): one reduction, the two series, and the quadrant table read at another column
+template <bool SIN>
+NLML_CR_HD double cr_trig(double x) {
   NLML_CR_STRICT
-  if (!(fabs(x) <= 1048576.0)) return cos(x);   // also NaN / Inf
+  if (!(fabs(x) <= 1048576.0)) return SIN ? sin(x) : cos(x);   // also NaN / Inf
   // argument reduction: r = x - k * pi/2, pi/2 = P1 + P2 + P3 + P4 (each exactly a double), |k| <= 2^20
   const double k = rint(x * 0x1.45f306dc9c883p-1);
   const double P1 = 0x1.921fb54442d18p+0, P2 = 0x1.1a62633145c07p-54, P3 = -0x1.f1976b7ed8fbcp-110, P4 = 0x1.4cf98e804177dp-164;
@@ -123,7 +127,7 @@ NLML_CR_HD double cr_cos(double x) {
   // +-cos(r) = sum (-1)^n r^(2n)/(2n)!;  +-sin(r) = r * sum (-1)^n r^(2n)/(2n+1)!
   // (one branch-free chain: the lanes of a wave hold different quadrants, so an if/else over the two series would run both;
   // the coefficients are immediates selected per lane)
-  const bool odd = (q & 1) != 0;
+  const bool odd = ((q & 1) != 0) != SIN;
   DD p = DD{odd ? -CR_SC[15][0] : -CR_CC[15][0], odd ? -CR_SC[15][1] : -CR_CC[15][1]};
 #pragma unroll
   for (int n = 14; n >= 0; --n) {
@@ -131,12 +135,15 @@ NLML_CR_HD double cr_cos(double x) {
     const double sg = (n & 1) ? -1.0 : 1.0;
     p = dd_add(DD{odd ? sg * CR_SC[n][0] : sg * CR_CC[n][0], odd ? sg * CR_SC[n][1] : sg * CR_CC[n][1]}, p);
   }
-  if ((q & 1) != 0) p = dd_mul(p, r);
-  // cos(x) by quadrant: q = 0: cos r, 1: -sin r, 2: -cos r, 3: sin r
-  const bool neg = (q == 1) || (q == 2);
+  if (odd) p = dd_mul(p, r);
+  // cos(x) by quadrant: q = 0: cos r, 1: -sin r, 2: -cos r, 3: sin r;  sin(x): q = 0: sin r, 1: cos r, 2: -sin r, 3: -cos r
+  const bool neg = SIN ? q >= 2 : (q == 1) || (q == 2);
   const double v = p.hi + p.lo;
   return neg ? -v : v;
 }
+NLML_CR_HD double cr_cos(double x) { return cr_trig<false>(x); }
+// The sin beside it (same scheme, same ~104 bits before the one rounding): the derivative of the f-vectors, TD_Tester.py:82,87,92.
+NLML_CR_HD double cr_sin(double x) { return cr_trig<true>(x); }
 
 // float32(a * cos(t) + d) with the cos correctly rounded -- the f-vector entry as the reference rounds it (TD_Tester.py:25-28,37) --
 // without paying for the double-double chain (~450 dependent operations, 2 us of every Powell round) unless it can matter.  The
@@ -151,6 +158,20 @@ NLML_CR_HD float cr_f32_a_cos_d(double a, double t, double d) {
   const float lo = (float)(v - delta), hi = (float)(v + delta);
   if (lo == hi) return lo;
   return (float)(a * cr_cos(t) + d);
+}
+
+// float32(((-a) * b) * sin(t)) with the sin correctly rounded -- the derivative entry df = -p[0] * p[1] * np.sin(...) as the reference
+// rounds it (TD_Tester.py:82,87,92: negation, product, product, each f64 operation on its own) -- by the same fast path / slow path
+// scheme: the library sin is within 2^-51 absolute of the correctly rounded one, so v is within |a b| * 2^-51 + one rounding of the
+// slow path's value, and delta = (|a b| + |v|) * 2^-46 is 32 times that.
+NLML_CR_HD float cr_f32_nab_sin(double a, double b, double t) {
+  NLML_CR_STRICT
+  const double nab = -a * b;
+  const double v = nab * sin(t);
+  const double delta = (fabs(nab) + fabs(v)) * 0x1p-46;
+  const float lo = (float)(v - delta), hi = (float)(v + delta);
+  if (lo == hi) return lo;
+  return (float)(nab * cr_sin(t));
 }
 
 }  // namespace nlml

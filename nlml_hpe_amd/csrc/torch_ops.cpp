@@ -183,6 +183,27 @@ at::Tensor tucker_objective(const at::Tensor& Wm_, const at::Tensor& x_, const a
   return err;
 }
 
+// K3g: objective value and analytic gradient in the reference's operation order -> (err f64[N], grad f64[N,3+R])
+std::tuple<at::Tensor, at::Tensor> tucker_gradient(const at::Tensor& Wm_, const at::Tensor& x_, const at::Tensor& params_,
+                                                   const at::Tensor& cosp_) {
+  const int r_id = check_td(Wm_, x_, cosp_);
+  need(params_, "params", at::kDouble);
+  same_device(x_, params_, "params");
+  TORCH_CHECK(params_.dim() == 2 && params_.size(1) == 3 + r_id, "params: expected [N,", 3 + r_id, "], got ", params_.sizes());
+  TORCH_CHECK(x_.size(0) == params_.size(0), "x has ", x_.size(0), " rows but params has ", params_.size(0));
+  const at::Tensor Wm = Wm_.contiguous(), x = x_.contiguous(), params = params_.contiguous(), cosp = cosp_.contiguous();
+  const int64_t N = params.size(0);
+  at::Tensor err = at::empty({N}, params.options()), grad = at::empty({N, 3 + r_id}, params.options());
+  const size_t ws_bytes = nlml_tucker_gradient_workspace_bytes(N, r_id);
+  at::Tensor ws = at::empty({(int64_t)(ws_bytes / sizeof(double))}, params.options());
+  OnDevice dev(x);
+  check(nlml_tucker_gradient_r(Wm.data_ptr<float>(), x.data_ptr<float>(), F_REF, nullptr, params.data_ptr<double>(),
+                               cosp.data_ptr<double>(), N, err.data_ptr<double>(), grad.data_ptr<double>(), r_id, ws.data_ptr(), ws_bytes,
+                               dev.stream),
+        "nlml_tucker_gradient_r");
+  return {err, grad};
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> tucker_powell(const at::Tensor& Wm_, const at::Tensor& x_,
                                                                                       const at::Tensor& cosp_, std::string order) {
   const int r_id = check_td(Wm_, x_, cosp_);
@@ -303,6 +324,9 @@ template <class... Rest> at::Tensor pose_meta(const at::Tensor& x, const at::Ten
 at::Tensor tucker_objective_meta(const at::Tensor&, const at::Tensor&, const at::Tensor& params, const at::Tensor&, std::string) {
   return at::empty({params.size(0)}, params.options());
 }
+std::tuple<at::Tensor, at::Tensor> tucker_gradient_meta(const at::Tensor&, const at::Tensor&, const at::Tensor& params, const at::Tensor&) {
+  return {at::empty({params.size(0)}, params.options()), at::empty({params.size(0), params.size(1)}, params.options())};
+}
 std::tuple<at::Tensor, at::Tensor> pose_valid_meta(const at::Tensor& raw, const at::Tensor&, bool, const std::optional<at::Tensor>&) {
   return {at::empty({raw.size(0), 3}, raw.options()), at::empty({raw.size(0)}, raw.options().dtype(at::kByte))};
 }
@@ -337,6 +361,7 @@ TORCH_LIBRARY(nlml_hpe, m) {
   m.def("landmarks_to_pose_small(Tensor raw, Tensor packed_w, bool normalize, Tensor workspace) -> Tensor");
   m.def("landmarks_to_pose_valid(Tensor raw, Tensor packed_w, bool normalize, Tensor? workspace) -> (Tensor, Tensor)");
   m.def("tucker_objective(Tensor Wm, Tensor x, Tensor params, Tensor cos_params, str order=\"reference\") -> Tensor");
+  m.def("tucker_gradient(Tensor Wm, Tensor x, Tensor params, Tensor cos_params) -> (Tensor, Tensor)");
   m.def("tucker_powell(Tensor Wm, Tensor x, Tensor cos_params, str order=\"reference\") -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("video_post(Tensor pose_rad, Tensor raw, Tensor? valid, float frame_w, float frame_h, float alpha, float max_jump, float size, "
         "Tensor(a!) state, Tensor(b!) smoothed, Tensor(c!) centre, Tensor(d!) endpoints, Tensor(e!) updated) -> ()");
@@ -355,6 +380,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
   m.impl("landmarks_to_pose_small", &landmarks_to_pose_small);
   m.impl("landmarks_to_pose_valid", &landmarks_to_pose_valid);
   m.impl("tucker_objective", &tucker_objective);
+  m.impl("tucker_gradient", &tucker_gradient);
   m.impl("tucker_powell", &tucker_powell);
   m.impl("video_post", &video_post);
   m.impl("cosine_table", &cosine_table);
@@ -371,6 +397,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("landmarks_to_pose_small", &pose_meta<bool, const at::Tensor&>);
   m.impl("tucker_objective", &tucker_objective_meta);
   m.impl("landmarks_to_pose_valid", &pose_valid_meta);
+  m.impl("tucker_gradient", &tucker_gradient_meta);
   m.impl("tucker_powell", &tucker_powell_meta);
   m.impl("video_post", &video_post_meta);
   m.impl("cosine_table", &cosine_table_meta);

@@ -232,6 +232,48 @@ def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, co
     return (err, xh) if return_xhat else err
 
 
+def tucker_gradient(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, cos_params: torch.Tensor,
+                    x_index: torch.Tensor | None = None, return_err: bool = True):
+    """K3g: objective value and analytic gradient (TD_Tester.py:60-102, the reference's ``jac=``) in one native call, in the reference's
+    own operation order: Wm f32[27R,1404], x f32[M,1404], params f64[N,3+R], cos_params f64[3,3,4] -> (err f64[N], grad f64[N,3+R]),
+    or grad alone with return_err=False.  err carries the bits of tucker_objective(order="reference"); every gradient component the
+    reference's own (csrc/tucker_grad_ref.h has the order).  R = 1..16."""
+    _need_cuda(Wm, "Wm", torch.float32)
+    _need_cuda(x, "x", torch.float32)
+    _need_cuda(params, "params", torch.float64)
+    _need_cuda(cos_params, "cos_params", torch.float64)
+    if Wm.dim() != 2 or Wm.shape[1] != F_REF:
+        raise ValueError(f"Wm: expected [27*R,1404], got {tuple(Wm.shape)}")
+    r_id = _lib.tucker_rank_of_rows(Wm.shape[0])
+    if x.dim() != 2 or x.shape[1] != F_REF:
+        raise ValueError(f"x: expected [M,1404], got {tuple(x.shape)}")
+    if params.dim() != 2 or params.shape[1] != 3 + r_id:
+        raise ValueError(f"params: expected [N,{3 + r_id}] for Wm of identity rank {r_id}, got {tuple(params.shape)}")
+    if tuple(cos_params.shape) != (3, 3, 4):
+        raise ValueError(f"cos_params: expected [3,3,4], got {tuple(cos_params.shape)}")
+    Wm, x, params, cos_params = Wm.contiguous(), x.contiguous(), params.contiguous(), cos_params.contiguous()
+    N = params.shape[0]
+    if x_index is not None:
+        _need_cuda(x_index, "x_index", torch.int32)
+        if x_index.shape != (N,):
+            raise ValueError("x_index: expected [N]")
+        x_index = x_index.contiguous()
+        if N and (int(x_index.min()) < 0 or int(x_index.max()) >= x.shape[0]):
+            raise IndexError("x_index out of range")
+    elif x.shape[0] != N:
+        raise ValueError(f"x has {x.shape[0]} rows but params has {N} (pass x_index to share rows)")
+    err = torch.empty((N,), dtype=torch.float64, device=x.device) if return_err else None
+    grad = torch.empty((N, 3 + r_id), dtype=torch.float64, device=x.device)
+    ws_bytes = _lib.lib().nlml_tucker_gradient_workspace_bytes(N, r_id)
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=x.device)
+    with _on_device_of(("x", x), ("Wm", Wm), ("params", params), ("cos_params", cos_params), ("x_index", x_index)) as stream:
+        _lib.check(_lib.lib().nlml_tucker_gradient_r(
+            Wm.data_ptr(), x.data_ptr(), F_REF, x_index.data_ptr() if x_index is not None else None,
+            params.data_ptr(), cos_params.data_ptr(), N, err.data_ptr() if err is not None else None, grad.data_ptr(), r_id,
+            ws.data_ptr(), ws_bytes, stream), "nlml_tucker_gradient_r")
+    return (err, grad) if return_err else grad
+
+
 # ---------------------------------------------------------------------------------------------
 # torch.ops.nlml_hpe.* (SURVEY.md 8b "Underlying op") come from COMPILED code: csrc/torch_ops.cpp, a TORCH_LIBRARY shim over the same
 # C ABI (shape / dtype checks, torch's allocator, the operand device's current stream), built next to this file as
@@ -250,7 +292,7 @@ def _load_torch_ops():
     torch.ops.load_library(TORCH_OPS_PATH)
     # the registered ops; *_small take an explicit workspace, landmarks_to_pose_valid is the video tick's forward (pose + face mask)
     for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
-                 "landmarks_to_pose_valid", "tucker_objective", "tucker_powell", "video_post", "cosine_table", "pose_eval",
+                 "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
                  "pose_eval_merge"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
