@@ -103,12 +103,13 @@ def _split(v):
 
 
 def _job_hx(blob, hdr, stage, job, x_in, k16, nb):
-    """x_in f32[32 faces, >= 16*k16] -> f64[nb*32 rows, 32 faces] = inv_scale * (bias' + sum of the three split products)."""
+    """x_in f32[n faces, >= 16*k16] -> f64[nb*32 rows, n faces] = inv_scale * (bias' + sum of the three split products)."""
     woff = int(hdr["w_off"][stage] + job * hdr["job_w16"][stage]) * 16
     w = blob[woff: woff + k16 * nb * 2 * 64 * 16].view(np.float16).reshape(k16, nb, 2, 64, 8).astype(np.float64)
     boff = int(hdr["b_off"][stage] + job * nb * 8) * 16
     b = blob[boff: boff + nb * 32 * 4].view(np.float32).reshape(nb, 2, 16).astype(np.float64)
-    acc = np.zeros((nb, 32, 32))
+    nf = len(x_in)
+    acc = np.zeros((nb, 32, nf))
     for n in range(nb):
         for h in range(2):
             for q in range(16):
@@ -121,39 +122,40 @@ def _job_hx(blob, hdr, stage, job, x_in, k16, nb):
                 whi = w[s, :, 0, 32 * h:32 * h + 32, j][:, :, None]
                 wlo = w[s, :, 1, 32 * h:32 * h + 32, j][:, :, None]
                 acc += wlo * xh[None, None, :, k] + whi * xl[None, None, :, k] + whi * xh[None, None, :, k]
-    return acc.reshape(nb * 32, 32) * hdr["inv_scale"][stage]
+    return acc.reshape(nb * 32, nf) * hdr["inv_scale"][stage]
 
 
 def forward_f16x2(blob: np.ndarray, x: np.ndarray) -> tuple:
-    """Split-f16 blob walk: x f32[32,F] (one face block) -> (out f64[32,3], latent f64[32,9]).
+    """Split-f16 blob walk: x f32[n,F] -> (out f64[n,3], latent f64[n,9]); every face is walked as a face block's column.
 
     Activations pass between layers as f32 (the kernel rounds accumulator*inv_scale to f32 before splitting)."""
     hdr = _header(blob)
     assert hdr["mode"] in (2, 3)      # NLML_MODE_F16X2 / NLML_MODE_F16X2S: one image
     F, k16 = hdr["F"], hdr["k8_e0"]
     f32 = lambda v: np.asarray(v, np.float32)
-    xin = np.zeros((32, 16 * k16), np.float32)
+    nf = len(x)
+    xin = np.zeros((nf, 16 * k16), np.float32)
     xin[:, :F] = x
     relu = lambda v: np.maximum(v, 0)
-    h1 = np.zeros((32, 1024), np.float32)
+    h1 = np.zeros((nf, 1024), np.float32)
     for job in range(8):
         h1[:, 128 * job:128 * job + 128] = f32(relu(_job_hx(blob, hdr, 0, job, xin, k16, 4)).T)
-    h2 = np.zeros((32, 512), np.float32)
+    h2 = np.zeros((nf, 512), np.float32)
     for wv in range(4):
         h2[:, 128 * wv:128 * wv + 128] = f32(relu(_job_hx(blob, hdr, 1, wv, h1, 64, 4)).T)
-    h3 = np.zeros((32, 256), np.float32)
+    h3 = np.zeros((nf, 256), np.float32)
     for wv in range(4):
         h3[:, 64 * wv:64 * wv + 64] = f32(relu(_job_hx(blob, hdr, 2, wv, h2, 32, 2)).T)
-    h4 = np.zeros((32, 128), np.float32)
+    h4 = np.zeros((nf, 128), np.float32)
     for wv in range(4):
         h4[:, 32 * wv:32 * wv + 32] = f32(relu(_job_hx(blob, hdr, 3, wv, h3, 16, 1)).T)
-    h5 = np.zeros((32, 64), np.float32)
+    h5 = np.zeros((nf, 64), np.float32)
     for wv in range(2):
         h5[:, 32 * wv:32 * wv + 32] = f32(np.tanh(_job_hx(blob, hdr, 4, wv, h4, 8, 1)).T)
     lat = f32(_job_hx(blob, hdr, 5, 0, h5, 4, 2).T)             # [32 faces, 64 cols]: head g at cols 16g..16g+2
     latent = np.stack([lat[:, 16 * (n // 3) + n % 3] for n in range(9)], axis=1).astype(np.float64)
-    ha = np.zeros((32, 384), np.float32); hb = np.zeros((32, 768), np.float32)
-    hc = np.zeros((32, 384), np.float32); hd = np.zeros((32, 192), np.float32)
+    ha = np.zeros((nf, 384), np.float32); hb = np.zeros((nf, 768), np.float32)
+    hc = np.zeros((nf, 384), np.float32); hd = np.zeros((nf, 192), np.float32)
     for job in range(12):
         g, nb = job >> 2, job & 3
         ha[:, 128 * g + 32 * nb: 128 * g + 32 * nb + 32] = f32(relu(_job_hx(blob, hdr, 6, job, lat[:, 16 * g:16 * g + 16], 1, 1)).T)
@@ -166,7 +168,7 @@ def forward_f16x2(blob: np.ndarray, x: np.ndarray) -> tuple:
     for job in range(6):
         g, nb = job >> 1, job & 1
         hd[:, 64 * g + 32 * nb: 64 * g + 32 * nb + 32] = f32(relu(_job_hx(blob, hdr, 9, job, hc[:, 128 * g:128 * g + 128], 8, 1)).T)
-    out = np.zeros((32, 3))
+    out = np.zeros((nf, 3))
     for g in range(3):
         out[:, g] = _job_hx(blob, hdr, 10, g, hd[:, 64 * g:64 * g + 64], 4, 1)[0, :]
     return out, latent

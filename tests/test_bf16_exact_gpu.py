@@ -2,8 +2,8 @@
 
 Every accumulator of these networks is an exact sum in f32 whatever the order (certified per face: sum|addends| + |bias| < 2^20 quanta),
 so the kernel has one correct answer per rounding point and oracle.encoder_heads.forward_bf16_emulated gives it.  Every comparison is
-np.array_equal on the f32 bits of pose and latent and on the validity mask.  The last section runs the same networks, with f32
-activations, through the parity modes.
+np.array_equal on the f32 bits of pose and latent and on the validity mask.  The parity modes (f32, f16x2, f16x2s) have their own file,
+tests/test_split_f16_exact_gpu.py.
 
 Live-Tanh form: the device's tanhf, measured against the f64 tanh on these networks' own E4 pre-activations: 1.27 f32 ulps at most
 (test_device_tanhf_error_is_inside_the_tie_margin measures it again on every run, reports it and asserts it stays <= margin / 8); the
@@ -13,54 +13,10 @@ import pytest
 import torch
 
 import exact_nets as XN
+from exact_gpu import _bits, _blob, _fwd, _report, _report_pool, _same, _tile
 from nlml_hpe_amd import _lib, ops, synth, weights
-from test_gpu_parity import _report          # the suite's one margins file: a JSON line per measured figure
 
 pytestmark = pytest.mark.gpu
-
-
-def _report_pool(name, p, **kv):
-    _report(name, worst_bits_needed=max(p["bits"].values()), excluded_share=p["excluded"], **{f"bits_{k}": v for k, v in p["bits"].items()}, **kv)
-
-
-_blobs: dict = {}
-
-
-def _blob(p, mode, device):
-    key = (id(p), mode)
-    if key not in _blobs:
-        _blobs[key] = torch.from_numpy(weights.pack_blob(p["enc"], p["heads"], _lib.mode_from_name(mode))).to(device)
-    return _blobs[key]
-
-
-def _tile(p, B, seed):
-    """B picks (with repeats, shuffled) out of the pool's certified faces; the "no face" row is among them when B > 2."""
-    idx = synth.rng(seed, 41).integers(0, len(p["x"]), size=B)
-    if B > 2:
-        idx[B // 2] = 0
-    return idx
-
-
-def _bits(t):
-    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, p, idx, tag):
-    """got = (pose, latent, valid) tensors; the model's bits for the pool rows idx."""
-    pose, lat, valid = got
-    bad = np.flatnonzero((_bits(pose) != _bits(p["pose"][idx])).any(axis=1) | (_bits(lat) != _bits(p["latent"][idx])).any(axis=1))
-    if len(bad):
-        r = int(bad[0])
-        lat_cols = np.flatnonzero(_bits(lat)[r] != _bits(p["latent"][idx])[r])
-        raise AssertionError(f"{tag}: {len(bad)} of {len(idx)} faces differ, first row {r} (tile row {r % 64}): latent columns {lat_cols.tolist()} "
-                             f"got {lat.cpu().numpy()[r].tolist()} want {p['latent'][idx][r].tolist()}; pose got {pose.cpu().numpy()[r].tolist()} "
-                             f"want {p['pose'][idx][r].tolist()}")
-    assert np.array_equal(valid.cpu().numpy(), p["valid"][idx]), tag
-
-
-def _fwd(xt, blob, F):
-    return ops.encoder_heads_fwd(xt, blob, F, return_latent=True, return_valid=True)
 
 
 def _live_cap(p):
@@ -240,27 +196,3 @@ def test_registered_ops_and_graph_replay(device):
     torch.cuda.synchronize()
     assert torch.equal(static_out, ops.encoder_heads_fwd(static_in, blob, 1404))
     assert np.array_equal(_bits(static_out), _bits(p["pose"][idx2]))
-
-
-# ---- the same nets, f32 activations, through the parity modes ----------------------------------------------------------------------
-@pytest.mark.parametrize("B", [65, 300])
-@pytest.mark.parametrize("mode", ["f32", "f16x2", "f16x2s"])
-def test_parity_modes_on_exact_nets(mode, B, device):
-    """Saturated Tanh, activations kept in f32 (certificate with rounded=False): the f64 value is the one right answer for the f32
-    kernel and for the split-f16 modes too -- an integer below 2^22 splits exactly into hi + lo f16 pieces, the weight pre-scale is a
-    power of two, and the split accumulators are exact sums again.  An absolute, order-independent answer instead of a tolerance or a
-    sibling implementation: fused kernel from features and from raw landmarks; strict-fast also on the layer-per-launch path and
-    the streamed-tail path."""
-    p = XN.pool(1404, "saturated", rounded=False)
-    assert p["excluded"] == 0.0
-    blob = _blob(p, mode, device)
-    idx = _tile(p, B, seed=100 + B)
-    xt = torch.from_numpy(p["x"][idx]).to(device)
-    rt = torch.from_numpy(XN.raw_landmarks(p["x"], seed=11)[idx]).to(device)
-    _same(_fwd(xt, blob, 1404), p, idx, f"{mode} fused, features")
-    _same(ops.landmarks_to_pose(rt, blob, True, return_latent=True, return_valid=True), p, idx, f"{mode} fused, raw landmarks")
-    if mode == "f16x2s":
-        _same(ops.encoder_heads_fwd_small(xt, blob, 1404, return_latent=True, return_valid=True), p, idx, "layer per launch")
-        _same(ops.landmarks_to_pose_small(rt, blob, True, return_latent=True, return_valid=True), p, idx, "layer per launch, raw")
-        _same(ops.landmarks_to_pose_streamed(rt, blob, True, return_latent=True, return_valid=True), p, idx, "streamed tail")
-    _report_pool(f"exact_unrounded_{mode}_B{B}", p)

@@ -168,3 +168,138 @@ def test_raw_landmarks_normalise_to_the_certified_integers():
     # un-normalised: the raw coordinates themselves are the features; they certify too (quantum 1/8)
     flat = raw.reshape(len(raw), 1404)
     assert XN.certify(flat, p["enc"], p["heads"])[0].mean() >= 0.9
+
+
+# ---- networks with live lo pieces (the split-f16 modes) -----------------------------------------------------------------------------
+MIN_KEPT = 128
+MIN_COVER = 0.10
+WIDTHS = [1404, 136, 64, 16, 13, 1407]
+LAYER0_POOLS = ("E0w", "E0x", "E0wx")
+SPLIT_CASES = [(n, 1404) for n in sorted(XN.SPLIT_POOLS)] + [(n, F) for n in LAYER0_POOLS for F in WIDTHS[1:]]
+
+
+@pytest.mark.parametrize("name,F", SPLIT_CASES)
+def test_split_pool_conditions(name, F):
+    """At most 15 % of the candidates left out, at least 128 faces kept, row 0 the all-zero "no face" row.  Pool E0wx: at least 10 %
+    of the certified E0 accumulators receive a non-zero product of EACH of the three kinds, a_lo w_lo is live there and the model's
+    bits differ from the f64 forward's.  The other pools: a_hi w_lo at every bumped stage (E0x: a_lo w_hi at E0); their a_lo w_hi
+    lies behind the bump, because a hidden stage with both lo pieces does not certify (tests/exact_nets.py has the measurement), and
+    test_split_pools_together_cover_every_stage_kind asserts the sum over the pools."""
+    p = XN.split_pool(name, F)
+    assert p["excluded"] <= XN.MAX_EXCLUDED_SHARE and len(p["x"]) >= MIN_KEPT, (p["excluded"], len(p["x"]))
+    assert not p["x"][0].any() and not p["valid"][0] and p["valid"][1:].all()
+    assert max(p["bits"].values()) < 20
+    for st in p["bump"]:
+        assert p["cover"][st]["hi_lo"] >= MIN_COVER and p["cover"][st]["hi_hi"] >= MIN_COVER, (st, p["cover"][st])
+    if name == "E0wx":
+        assert min(p["cover"]["E0"].values()) >= MIN_COVER, p["cover"]["E0"]
+        assert not XN.lo_lo_is_zero(XN._split_walk(p["x"], p["enc"], p["heads"])[:1], np.ones(len(p["x"]), bool))
+        f64 = EH.encoder_latent_numpy(p["x"], EH.Params(p["enc"], p["heads"]), np.float64)
+        differ = (f64 != p["latent"].astype(np.float64)).any(axis=1)
+        assert differ.sum() >= 8, "the dropped a_lo w_lo must show in the answer"
+        print(f"{name} F={F}: {differ.sum()} faces whose latent is not the f64 forward's")
+    elif name == "E0x":
+        assert p["cover"]["E0"]["lo_hi"] >= MIN_COVER and np.any(p["x"] * 2.0 ** 10 % 1 != 0)
+    else:
+        assert np.array_equal(p["x"], np.round(p["x"]))
+    assert len(np.unique(p["pose"], axis=0)) >= 0.9 * len(p["x"]), "the faces must tell each other apart"
+    print(f"{name} F={F}: kept {len(p['x'])} of {p['n_all']}, excluded {p['excluded']:.3f}, worst bits {max(p['bits'].values()):.1f}, "
+          + ", ".join(f"{st} lo_hi {c['lo_hi']:.2f} hi_lo {c['hi_lo']:.2f}" for st, c in p["cover"].items()))
+
+
+def test_split_pools_together_cover_every_stage_kind():
+    """Non-zero w_lo AND non-zero a_lo products under each of the eleven stage kinds, on >= 10 % of the accumulators of some pool.
+    The one exception is a_lo under E5: its input is the saturated Tanh (-1, 0, 1), whose lo piece is identically zero."""
+    pools = [XN.split_pool(n) for n in sorted(XN.SPLIT_POOLS)]
+    for st in ("E0", "E1", "E2", "E3", "E4", "E5", "H0", "H1", "H2", "H3", "H4"):
+        assert max(p["cover"][st]["hi_lo"] for p in pools) >= MIN_COVER, st
+        if st == "E5":
+            assert all(p["cover"][st]["lo_hi"] == 0.0 for p in pools)
+        else:
+            assert max(p["cover"][st]["lo_hi"] for p in pools) >= MIN_COVER, st
+
+
+@pytest.mark.parametrize("name,F", SPLIT_CASES)
+def test_reference_split_is_the_blob_walk_bit_for_bit(name, F):
+    """The dense piece model on the state dicts == pack.cpp's split-f16 image walked with the kernel's index arithmetic
+    (blob_emulator.forward_f16x2), pose and latent, every bit, on ALL certified faces of every pool and width the GPU tests run: ties
+    the packer (scale, hi/lo planes, fragment order, the padded K tail) to the model the GPU tests compare with.  The f16x2 blob is the
+    strict-fast blob's split image byte for byte (the header's mode and size apart), so one walk covers both."""
+    p = XN.split_pool(name, F)
+    blob = weights.pack_blob(p["enc"], p["heads"], _lib.MODE_F16X2S)
+    fast = weights.pack_blob(p["enc"], p["heads"], _lib.MODE_F16X2)
+    for b, mode in ((blob, _lib.MODE_F16X2S), (fast, _lib.MODE_F16X2)):
+        assert b.nbytes == _lib.lib().nlml_encoder_heads_packed_bytes(F, mode)
+    assert np.array_equal(fast[256:], blob[256:fast.nbytes])
+    differ = np.flatnonzero(fast[:256].view(np.uint32) != blob[:256].view(np.uint32))
+    assert differ.tolist() == [3, 5], "header words: mode and total size"
+    out, lat = BE.forward_f16x2(blob, p["x"])
+    assert np.array_equal(out, p["pose"].astype(np.float64)) and np.array_equal(lat, p["latent"].astype(np.float64))
+    hdr = BE._header(blob)
+    stages = XN._split_walk(p["x"][:2], p["enc"], p["heads"])
+    assert np.array_equal(hdr["inv_scale"], [1.0 / stages[i]["s"] for i in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10)])
+
+
+def test_rescue_pool_is_the_blob_walk_on_its_unrescued_faces():
+    p = XN.rescue_pool()
+    calm = ~p["rescued"]
+    out, lat = BE.forward_f16x2(weights.pack_blob(p["enc"], p["heads"], _lib.MODE_F16X2S), p["x"][calm])
+    assert np.array_equal(out, p["pose"][calm].astype(np.float64)) and np.array_equal(lat, p["latent"][calm].astype(np.float64))
+
+
+def test_reference_split_is_the_f64_forward_where_lo_lo_is_zero():
+    """The model drops a_lo w_lo and nothing else: where no accumulator has such a product (integer x under a bumped E0, +-1 weights
+    behind it; the old all-integer pool) it equals the plain f64 forward; where some have, it differs."""
+    for p in (XN.split_pool("E0w"), XN.pool(1404, "saturated", rounded=False), XN.rescue_pool()):
+        stages = XN._split_walk(p["x"], p["enc"], p["heads"])
+        rescued = p.get("rescued", np.zeros(len(p["x"]), bool))
+        assert XN.lo_lo_is_zero(stages, ~rescued)
+        pose, lat, valid, over = XN.reference_split(p["x"], p["enc"], p["heads"])
+        assert np.array_equal(over, rescued)
+        want_pose, want_lat, want_valid = XN.reference(p["x"], p["enc"], p["heads"], rounded=False)
+        assert np.array_equal(_bits(pose), _bits(want_pose)) and np.array_equal(_bits(lat), _bits(want_lat)) and np.array_equal(valid, want_valid)
+        assert np.array_equal(_bits(pose), _bits(p["pose"])) and np.array_equal(_bits(lat), _bits(p["latent"]))
+    # bumped at E0 AND E1: E1 meets a_lo with w_lo, the dropped product shows, and the certificate refuses the net (E1 needs
+    # 26.5 bits: E0's outputs such as 1 + 3 2^-11 have an 11-bit hi against w_lo's 2^-4)
+    enc, heads, x = XN.make_split(1404, 5, ("E0", "E1"), "int", XN.SPLIT_POOLS["E0w"]["nnz"], B=32)
+    stages = XN._split_walk(x, enc, heads)
+    assert not XN.lo_lo_is_zero(stages, np.ones(32, bool))
+    lat = XN.reference_split(x, enc, heads)[1]
+    assert (lat.astype(np.float64) != EH.encoder_latent_numpy(x, EH.Params(enc, heads), np.float64)).any()
+    ok, worst, _, _ = XN.certify_split(x, enc, heads)
+    assert not ok[1:].any() and XN.worst_bits(worst)["E1"] > 24
+
+
+def test_old_unrounded_pool_is_unchanged():
+    import hashlib
+    p = XN.pool(1404, "saturated", rounded=False)
+    h = hashlib.sha256()
+    for k in ("x", "pose", "latent"):
+        h.update(np.ascontiguousarray(p[k], np.float32).tobytes())
+    assert len(p["x"]) == 256 and p["excluded"] == 0.0
+    assert h.hexdigest() == "c135bc8e8c1ae2b9b0324ac11d02950e77f265aa0adc2ce271c71245fbbe4543"
+
+
+def test_rescue_pool():
+    """Rows times 2^k around f16's range: just inside (not rescued), over in a hidden layer only, over in the input; each with the
+    unscaled row's latent and pose bits, each certified for the arithmetic that evaluates it."""
+    p = XN.rescue_pool()
+    kind, x = p["kind"], p["x"]
+    assert p["excluded"] <= XN.MAX_EXCLUDED_SHARE and all((kind == i).sum() >= 64 for i in range(4))
+    assert np.array_equal(p["rescued"], kind >= 2) and not x[0].any() and kind[0] == 0
+    assert np.array_equal(_bits(p["pose"]), _bits(p["pose"][p["base"]])) and np.array_equal(_bits(p["latent"]), _bits(p["latent"][p["base"]]))
+    assert (np.abs(x[kind == 2]).max(axis=1) <= 32768).all() and (np.abs(x[kind == 3]).max(axis=1) >= XN.F16_OVER).all()
+    stages = XN._split_walk(x[kind == 1], p["enc"], p["heads"])
+    m = np.max([np.abs(st["a"]).max(axis=1) for st in stages], axis=0)
+    assert (m < XN.F16_MAX).all() and (m >= XN.F16_MAX / 2 - 1).all(), "just inside: one more doubling leaves f16's range"
+    assert XN.certify_split(x[~p["rescued"]], p["enc"], p["heads"])[0].all()
+    assert XN.certify(x[p["rescued"]], p["enc"], p["heads"], rounded=False)[0].all()
+    print(f"rescue pool: {np.bincount(kind).tolist()} rows (plain, inside, hidden, input), excluded {p['excluded']:.3f}")
+
+
+def test_raw_landmarks_normalise_to_the_fractional_features():
+    """x = k + j 2^-11 through raw_landmarks(): coordinates in 2^-14ths, still exact in f32, and the f64 normalisation gives x back."""
+    for name in ("E0x", "E0w"):
+        p = XN.split_pool(name)
+        raw = XN.raw_landmarks(p["x"], seed=11)
+        assert np.array_equal(FN.normalize_ipd(raw, True), p["x"]) and not raw[0].any()
