@@ -8,7 +8,10 @@
 // result: this cos is evaluated in double-double arithmetic (~104 bits) and rounded once, so it returns the correctly rounded
 // value (a wrong rounding needs the true value within 2^-100 of a tie), and differs from glibc's (< 0.55 ulp, correctly rounded
 // in all but ~1e-4 of the cases) only where glibc itself is not correctly rounded -- and then by one unit in the last place.
-// tests/test_abi_and_host.py checks it on the CPU against 60-digit decimal arithmetic; tests/test_gpu_parity.py sweeps 1e6
+// Checked against multi-precision arithmetic rounded once (tests/cr_reference.py), bit for bit: the host build on ~100,000 hard
+// arguments (next to every k pi/2 up to the reduction's limit, tiny, subnormal; tests/test_cr_reference_host.py, beside the 60-digit
+// checks of tests/test_abi_and_host.py), the DEVICE build on the same arguments and, at every compile site with a read-out, on
+// inputs whose float32 hangs on the last bits of the cos (tests/test_td_fvec_exact_gpu.py); tests/test_gpu_parity.py sweeps 1e6
 // angles on the device against numpy.
 //
 //   |x| <= 2^20: k = rint(x * 2/pi), r = x - k*pi/2 with pi/2 as four doubles (212 bits), cos/sin of r (|r| <= pi/4 + eps) by
@@ -113,6 +116,7 @@ template <bool SIN>
 NLML_CR_HD double cr_trig(double x) {
   NLML_CR_STRICT
   if (!(fabs(x) <= 1048576.0)) return SIN ? sin(x) : cos(x);   // also NaN / Inf
+  if (SIN && x == 0.0) return x;                                // sin(-0) = -0: the sums below would return +0
   // argument reduction: r = x - k * pi/2, pi/2 = P1 + P2 + P3 + P4 (each exactly a double), |k| <= 2^20
   const double k = rint(x * 0x1.45f306dc9c883p-1);
   const double P1 = 0x1.921fb54442d18p+0, P2 = 0x1.1a62633145c07p-54, P3 = -0x1.f1976b7ed8fbcp-110, P4 = 0x1.4cf98e804177dp-164;

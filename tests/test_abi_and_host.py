@@ -235,23 +235,8 @@ def test_cr_cos_is_correctly_rounded(tmp_path, repo_root):
     assert (np.abs(y - ref) <= np.spacing(np.abs(ref))).all()                       # never more than one ulp from libm
     differ = np.nonzero(y != ref)[0]
     assert len(differ) <= 5e-3 * len(ref)
+    from cr_reference import decimal_cos as exact_cos                               # the 70-digit series (tests/cr_reference.py)
     getcontext().prec = 70
-    pi = Decimal("3.14159265358979323846264338327950288419716939937510582097494459230781640628620899862803482534211706798")
-
-    def exact_cos(xf):
-        X = Decimal(xf)
-        k = (X / (pi / 2)).to_integral_value()
-        r = X - k * (pi / 2)
-
-        def series(start):
-            t = Decimal(1) if start == 0 else r
-            s, n = t, start
-            while abs(t) > Decimal(10) ** -65:
-                n += 2
-                t = -t * r * r / (n * (n - 1))
-                s += t
-            return s
-        return [series(0), -series(1), -series(0), series(1)][int(k) % 4]
 
     for i in differ[:100]:                                                         # where the two disagree, cr_cos is the closer one
         t = exact_cos(float(x[i]))

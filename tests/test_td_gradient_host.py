@@ -90,23 +90,8 @@ def test_cr_sin_is_correctly_rounded(tmp_path, repo_root):
     assert (np.abs(y - ref) <= np.spacing(np.abs(ref))).all()
     differ = np.nonzero(y != ref)[0]
     assert len(differ) <= 5e-3 * len(ref)
+    from cr_reference import decimal_sin as exact_sin                               # the 70-digit series (tests/cr_reference.py)
     getcontext().prec = 70
-    pi = Decimal("3.14159265358979323846264338327950288419716939937510582097494459230781640628620899862803482534211706798")
-
-    def exact_sin(xf):
-        X = Decimal(xf)
-        k = (X / (pi / 2)).to_integral_value()
-        r = X - k * (pi / 2)
-
-        def series(start):
-            t = Decimal(1) if start == 0 else r
-            s, n = t, start
-            while abs(t) > Decimal(10) ** -80:
-                n += 2
-                t = -t * r * r / (n * (n - 1))
-                s += t
-            return s
-        return [series(1), series(0), -series(1), -series(0)][int(k) % 4]
 
     for i in differ[:100]:
         t = exact_sin(float(x[i]))
