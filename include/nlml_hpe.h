@@ -248,6 +248,17 @@ int nlml_landmarks_to_pose_ws(const float* raw, int64_t B, int normalize,
  *       x_hat = c^T Wm with c = ((u*f_y)*f_p)*f_r as a GEMM on the f64 matrix cores, one fma chain per output; agrees with the
  *       reference's objective to <= 1e-12 relative (measured ~2e-16), ~5x the evaluations/s.
  *       Alignment: Wm and x 16-byte aligned and ldx % 4 == 0 (16-byte vector loads), else NLML_E_BADARG.
+ *
+ * TD ARGUMENT CHECKS.  Every TD entry point (objective, Powell and gradient, of every generation) checks its arguments in this order
+ * and returns at the first that fails, before any launch; a host may rely on which of two errors it gets:
+ *   1. r_id outside NLML_TUCKER_RANK_MIN..NLML_TUCKER_RANK_MAX -> NLML_E_SHAPE (the entry points that take a rank)
+ *   2. unknown order -> NLML_E_BADARG (the entry points that take an order)
+ *   3. N < 0 -> NLML_E_BADARG;  N == 0 -> 0: no launch, no buffer is looked at
+ *   4. a required buffer NULL -> NLML_E_BADARG (objective: Wm, x, params, cos_params, err; Powell: Wm, x, cos_params, result;
+ *      gradient: Wm, x, params, cos_params, grad)
+ *   5. ldx < 1404 -> NLML_E_BADARG
+ *   6. NLML_TD_ORDER_FAST and its alignment rule broken -> NLML_E_BADARG
+ * nlml_last_error() names the entry point family and the condition.
  */
 #define NLML_TD_ORDER_FAST      0
 #define NLML_TD_ORDER_REFERENCE 1
@@ -292,10 +303,11 @@ int nlml_tucker_powell_ex(const float* Wm, const float* x, int64_t ldx, const do
  * rank from the artefact (TD_Inference.py:51, u_id_shape = factors_data['U_id'][1].size) and runs objective() and Test() with
  * 3 + R parameters whatever it is (TD_Tester.py:31-58,162-199); slicing W to fewer identity components is its own advice
  * (TD_Inference.py:54-55).  The angle ranks stay 3.
- *   r_id       NLML_TUCKER_RANK_MIN..NLML_TUCKER_RANK_MAX, else NLML_E_SHAPE
+ *   r_id       NLML_TUCKER_RANK_MIN..NLML_TUCKER_RANK_MAX
  *   Wm         f32[27 r_id, 1404] = W.reshape(-1, 1404), W f32[r_id,3,3,3,1404]
  *   params, x0, result   f64[N, 3 + r_id]: (w_y, w_p, w_r, u_id[r_id])
- *   everything else, the two orders and their alignment rules: as for nlml_tucker_objective_ex / nlml_tucker_powell_ex.
+ *   everything else, the two orders, their alignment rules and the argument checks: as for nlml_tucker_objective_ex /
+ *   nlml_tucker_powell_ex ("TD argument checks" above).
  * scipy's defaults follow the number of parameters: maxiter = maxfev = 1000 (3 + r_id).
  * NLML_TD_ORDER_REFERENCE is bit-identical to the reference's objective and walks scipy's trajectory for every rank (FX10: ranks 1, 3
  * and 8); NLML_TD_ORDER_FAST keeps its <= 1e-12 relative.  r_id == 5 runs the kernels of the entry points above: the same bits.
@@ -320,8 +332,9 @@ int nlml_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const dou
  *       csrc/tucker_grad_ref.h states the order.
  *   workspace   nlml_tucker_gradient_workspace_bytes(N, r_id) bytes of device memory, 8-byte aligned (the chains' rows and r * v; about
  *       56 KB per evaluation); the call leaves nothing in it that a later call needs.
- * Arguments, error codes and alignment otherwise as for nlml_tucker_objective_r in NLML_TD_ORDER_REFERENCE: r_id out of range ->
- * NLML_E_SHAPE; negative N, a null buffer, ldx < 1404, a workspace that is too small -> NLML_E_BADARG.  Two launches on `stream`.
+ * Arguments, alignment and the argument checks ("TD argument checks" above) otherwise as for nlml_tucker_objective_r in
+ * NLML_TD_ORDER_REFERENCE; then a workspace that is too small, or an f64 buffer or workspace that is not 8-byte aligned ->
+ * NLML_E_BADARG.  Two launches on `stream`.
  * nlml_tucker_gradient_host: the same arithmetic on HOST buffers in plain C++ (no GPU involved) -- the restatement the device kernels
  * are held to; h_v f32[N,1404] or NULL receives the f32 einsum of the identity term (for tests). */
 size_t nlml_tucker_gradient_workspace_bytes(int64_t N, int r_id);   /* 0 for N <= 0 or an r_id out of range */

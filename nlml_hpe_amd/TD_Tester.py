@@ -64,6 +64,15 @@ def _x(x) -> torch.Tensor:
     return t.to(_dev()).contiguous()
 
 
+def _stage(params, W, X, params_y, params_p, params_r, x_index=None):
+    """The operands of the batched TD calls on the device -> (Wm f32[27R,1404], X f32[M,1404], P f64[N,3+R], cos f64[3,3,4],
+    x_index i32[N] or None)."""
+    Wm = _wm(W)
+    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3 + Wm.shape[0] // 27)).to(_dev())
+    xi = None if x_index is None else torch.from_numpy(np.ascontiguousarray(x_index, dtype=np.int32)).to(_dev())
+    return Wm, _x(X), P, _cos(params_y, params_p, params_r), xi
+
+
 def func(w, params):
     a, b, c, d = params
     return a * np.cos(b * w + c) + d
@@ -79,11 +88,8 @@ ORDER_REFERENCE, ORDER_FAST = "reference", "fast"
 
 def objective_batch(params, W, X, params_y, params_p, params_r, x_index=None, return_xhat=False, order=ORDER_REFERENCE):
     """params f64[N,3+R] (R = W's identity rank); X f32[M,1404] (M == N, or rows selected by x_index i32[N]) -> err f64[N] (numpy)."""
-    Wm = _wm(W)
-    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3 + Wm.shape[0] // 27)).to(_dev())
-    xi = None if x_index is None else torch.from_numpy(np.ascontiguousarray(x_index, dtype=np.int32)).to(_dev())
-    out = ops.tucker_objective(Wm, _x(X), P, _cos(params_y, params_p, params_r), x_index=xi, return_xhat=return_xhat,
-                               order=order)
+    Wm, Xd, P, cp, xi = _stage(params, W, X, params_y, params_p, params_r, x_index)
+    out = ops.tucker_objective(Wm, Xd, P, cp, x_index=xi, return_xhat=return_xhat, order=order)
     if return_xhat:
         return out[0].cpu().numpy(), out[1].cpu().numpy()
     return out.cpu().numpy()
@@ -100,10 +106,8 @@ def value_and_gradient_batch(params, W, X, params_y, params_p, params_r, x_index
     operation order: err carries objective_batch's bits, every gradient component the reference's.  params f64[N,3+R]; X f32[M,1404]
     (M == N, or rows selected by x_index i32[N]) -> (err f64[N], grad f64[N,3+R]) (numpy) -- what scipy's gradient methods (the
     reference's L-BFGS-B alternative, :253-256) consume per step."""
-    Wm = _wm(W)
-    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3 + Wm.shape[0] // 27)).to(_dev())
-    xi = None if x_index is None else torch.from_numpy(np.ascontiguousarray(x_index, dtype=np.int32)).to(_dev())
-    err, grad = ops.tucker_gradient(Wm, _x(X), P, _cos(params_y, params_p, params_r), x_index=xi)
+    Wm, Xd, P, cp, xi = _stage(params, W, X, params_y, params_p, params_r, x_index)
+    err, grad = ops.tucker_gradient(Wm, Xd, P, cp, x_index=xi)
     return err.cpu().numpy(), grad.cpu().numpy()
 
 
@@ -125,12 +129,8 @@ def compute_gradient_batch(params, W, X, params_y, params_p, params_r, impl=IMPL
         return value_and_gradient_batch(params, W, X, params_y, params_p, params_r)[1]
     if impl != IMPL_LIBRARY:
         raise ValueError(f"unknown impl {impl!r}; expected 'library' or 'native'")
-    dev = _dev()
-    Wm = _wm(W)
+    Wm, Xd, P, cp, _ = _stage(params, W, X, params_y, params_p, params_r)     # cp: [3 angles, 3 rows, (a,b,c,d)]
     R = Wm.shape[0] // 27
-    P = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3 + R)).to(dev)
-    cp = _cos(params_y, params_p, params_r)                                   # [3 angles, 3 rows, (a,b,c,d)]
-    Xd = _x(X)
     _, xh = ops.tucker_objective(Wm, Xd, P, cp, return_xhat=True)
     r = Xd.double() - xh                                                      # residuals, :77
     a, b, c, d = cp[..., 0], cp[..., 1], cp[..., 2], cp[..., 3]               # each [3,3]

@@ -29,8 +29,24 @@ def _k2_forwards():
         yield "nlml_landmarks_to_pose" + form, (C.c_int, _FWD_RAW + _FWD_OUT + ws + [C.c_void_p])
 
 
+# the TD entry points: Wm, x, ldx, x_index, params, cos_params, N, err, x_hat | grad (objective, gradient) or Wm, x, ldx, cos_params, N, x0,
+# result, fval, nfev, nit, status (Powell), + nothing | order | r_id, order (plain, _ex, _r) + stream
+_TD_EVAL = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+_TD_POWELL = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+
+
+def _td_entries():
+    for op, head in (("objective", _TD_EVAL), ("powell", _TD_POWELL)):
+        for form, tail in (("", []), ("_ex", [C.c_int]), ("_r", [C.c_int, C.c_int])):
+            yield f"nlml_tucker_{op}{form}", (C.c_int, head + tail + [C.c_void_p])
+    # K3g: ..., r_id, workspace, workspace_bytes, stream | ..., r_id, h_v
+    yield "nlml_tucker_gradient_r", (C.c_int, _TD_EVAL + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+    yield "nlml_tucker_gradient_host", (C.c_int, _TD_EVAL + [C.c_int, C.c_void_p])
+
+
 SYMBOLS = {
     **dict(_k2_forwards()),
+    **dict(_td_entries()),
     "nlml_abi_version": (C.c_int, []),
     "nlml_last_error": (C.c_char_p, []),
     "nlml_normalize_ipd": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -44,25 +60,7 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_encoder_heads_small_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "nlml_encoder_heads_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
-    "nlml_tucker_objective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nlml_tucker_powell": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nlml_tucker_objective_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "nlml_tucker_powell_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    # the TD path for any identity rank: ..., r_id, order, stream
-    "nlml_tucker_objective_r": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "nlml_tucker_powell_r": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    # K3g: Wm, x, ldx, x_index, params, cos_params, N, err, grad, r_id, workspace, workspace_bytes, stream | ..., r_id, h_v
     "nlml_tucker_gradient_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
-    "nlml_tucker_gradient_r": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "nlml_tucker_gradient_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nlml_video_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_video_post_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,

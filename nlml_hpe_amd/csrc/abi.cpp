@@ -190,34 +190,6 @@ int nlml_landmarks_to_pose_ws(const float* raw, int64_t B, int normalize, const 
   return k2_forward(K2_AUTO, true, nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
 }
 
-// The matrix-core order reads Wm and the x rows with 16-byte vector loads (tucker_common.h load11 / tucker_few)
-static int check_td_fast_alignment(const float* Wm, const float* x, int64_t ldx, const char* who) {
-  if ((reinterpret_cast<uintptr_t>(Wm) & 15) || (reinterpret_cast<uintptr_t>(x) & 15) || (ldx & 3)) {
-    static thread_local char msg[160];
-    snprintf(msg, sizeof msg, "%s: NLML_TD_ORDER_FAST needs Wm and x 16-byte aligned and ldx %% 4 == 0", who);
-    return fail(NLML_E_BADARG, msg);
-  }
-  return 0;
-}
-
-int nlml_tucker_objective_ex(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index,
-                             const double* params, const double* cos_params, int64_t N, double* err, double* x_hat,
-                             int order, void* stream) {
-  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) return fail(NLML_E_BADARG, "tucker_objective: unknown order");
-  if (N < 0) return fail(NLML_E_BADARG, "tucker_objective: negative N");
-  if (N > 0 && (!Wm || !x || !params || !cos_params || !err)) return fail(NLML_E_BADARG, "tucker_objective: null buffer");
-  if (N > 0 && ldx < NLML_F_REFERENCE) return fail(NLML_E_BADARG, "tucker_objective: ldx < 1404");
-  if (N > 0 && order == NLML_TD_ORDER_FAST)
-    if (int rc = check_td_fast_alignment(Wm, x, ldx, "tucker_objective")) return rc;
-  return launch_tucker_objective(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, order, stream);
-}
-
-int nlml_tucker_objective(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index,
-                          const double* params, const double* cos_params, int64_t N, double* err, double* x_hat,
-                          void* stream) {
-  return nlml_tucker_objective_ex(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, NLML_TD_ORDER_REFERENCE, stream);
-}
-
 int nlml_video_post_ex(const float* pose_rad, const float* raw, const uint8_t* valid, int64_t S, double frame_w,
                        double frame_h, double alpha, double max_jump, double size, double* state, double* smoothed,
                        double* centre, double* endpoints, uint8_t* updated, void* stream) {
@@ -303,109 +275,87 @@ int nlml_pose_eval_merge(const double* records, int64_t n, int n_intervals, doub
   return launch_pose_eval_merge(records, n, n_intervals, record_out, result_out, stream);
 }
 
-// ---- host-side stepping of the Powell state machine (powell.h) --------------------------------
-size_t nlml_powell_state_bytes(void) { return sizeof(PowellState); }
-
-int nlml_powell_init(void* h_state, const double* h_x0, double xtol, double ftol) {
-  if (!h_state || !h_x0) return fail(NLML_E_BADARG, "powell_init: null pointer");
-  powell_init(*static_cast<PowellState*>(h_state), h_x0, xtol, ftol);
-  return 0;
-}
-
-int nlml_powell_step(void* h_state, double fin, double* h_xeval) {
-  if (!h_state || !h_xeval) return fail(NLML_E_BADARG, "powell_step: null pointer");
-  PowellState& s = *static_cast<PowellState*>(h_state);
-  const bool need = powell_step(s, fin);
-  if (need) std::memcpy(h_xeval, s.xeval, sizeof s.xeval);
-  return need ? 1 : 0;
-}
-
-int nlml_powell_result(const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status) {
-  if (!h_state || !h_x) return fail(NLML_E_BADARG, "powell_result: null pointer");
-  const PowellState& s = *static_cast<const PowellState*>(h_state);
-  std::memcpy(h_x, s.x, sizeof s.x);
-  if (h_fval) *h_fval = s.fval;
-  if (h_nfev) *h_nfev = s.nfev;
-  if (h_nit) *h_nit = s.iter;
-  if (h_status) *h_status = s.status;
-  return 0;
-}
-
-int nlml_tucker_powell_ex(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N,
-                          const double* x0, double* result, double* fval, int32_t* nfev, int32_t* nit,
-                          int32_t* status, int order, void* stream) {
-  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) return fail(NLML_E_BADARG, "tucker_powell: unknown order");
-  if (N < 0) return fail(NLML_E_BADARG, "tucker_powell: negative N");
-  if (N > 0 && (!Wm || !x || !cos_params || !result)) return fail(NLML_E_BADARG, "tucker_powell: null buffer");
-  if (N > 0 && ldx < NLML_F_REFERENCE) return fail(NLML_E_BADARG, "tucker_powell: ldx < 1404");
-  if (N > 0 && order == NLML_TD_ORDER_FAST)
-    if (int rc = check_td_fast_alignment(Wm, x, ldx, "tucker_powell")) return rc;
-  return launch_tucker_powell(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, order, stream);
-}
-
-int nlml_tucker_powell(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N,
-                       const double* x0, double* result, double* fval, int32_t* nfev, int32_t* nit,
-                       int32_t* status, void* stream) {
-  return nlml_tucker_powell_ex(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, NLML_TD_ORDER_REFERENCE, stream);
-}
-
-// ---- the TD path for any identity rank -------------------------------------------------------------------------------------
+// ---- the TD path (K3 objective, device Powell, K3g gradient): one argument check, one core per operation -----------------------
 static_assert(PW_NMAX == 3 + NLML_TUCKER_RANK_MAX && PW_N == 3 + 5, "powell.h's state sizes follow the ranks");
 static bool rank_ok(int r_id) { return r_id >= NLML_TUCKER_RANK_MIN && r_id <= NLML_TUCKER_RANK_MAX; }
 static int bad_rank(const char* who, int r_id) {
-  static thread_local char msg[160];
+  char msg[160];
   snprintf(msg, sizeof msg, "%s: identity rank %d outside [%d, %d]", who, r_id, NLML_TUCKER_RANK_MIN, NLML_TUCKER_RANK_MAX);
   return fail(NLML_E_SHAPE, msg);
 }
 
+// The checks of every TD entry point, in the order include/nlml_hpe.h promises ("TD argument checks": hosts may match on which of two
+// errors they get).  who: the entry point family that was called.  An entry point without a rank passes the shipped artefacts' 5, one
+// without an order the reference order -- what they run.  null_buffer: one of the operation's required buffers is NULL.  N == 0 with
+// rank and order in range needs nothing else: the launchers return at once.
+static int check_td_args(const char* who, int r_id, int order, int64_t N, int64_t ldx, bool null_buffer, const float* Wm, const float* x) {
+  if (!rank_ok(r_id)) return bad_rank(who, r_id);
+  const char* what = nullptr;
+  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) what = "unknown order";
+  else if (N < 0) what = "negative N";
+  else if (N == 0) return 0;
+  else if (null_buffer) what = "null buffer";
+  else if (ldx < NLML_F_REFERENCE) what = "ldx < 1404";
+  // the matrix-core order reads Wm and the x rows with 16-byte vector loads (tucker_common.h load11 / tucker_few)
+  else if (order == NLML_TD_ORDER_FAST && (((reinterpret_cast<uintptr_t>(Wm) | reinterpret_cast<uintptr_t>(x)) & 15) || (ldx & 3)))
+    what = "NLML_TD_ORDER_FAST needs Wm and x 16-byte aligned and ldx % 4 == 0";
+  if (!what) return 0;
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return fail(NLML_E_BADARG, msg);
+}
+
+static int td_objective(const char* who, const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                        const double* cos_params, int64_t N, double* err, double* x_hat, int r_id, int order, void* stream) {
+  if (int rc = check_td_args(who, r_id, order, N, ldx, !Wm || !x || !params || !cos_params || !err, Wm, x)) return rc;
+  return launch_tucker_objective_r(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, r_id, order, stream);
+}
+
+int nlml_tucker_objective(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                          const double* cos_params, int64_t N, double* err, double* x_hat, void* stream) {
+  return td_objective("tucker_objective", Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, 5, NLML_TD_ORDER_REFERENCE, stream);
+}
+
+int nlml_tucker_objective_ex(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                             const double* cos_params, int64_t N, double* err, double* x_hat, int order, void* stream) {
+  return td_objective("tucker_objective", Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, 5, order, stream);
+}
+
 int nlml_tucker_objective_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
                             const double* cos_params, int64_t N, double* err, double* x_hat, int r_id, int order, void* stream) {
-  if (!rank_ok(r_id)) return bad_rank("tucker_objective_r", r_id);
-  // rank 5: the shipped artefacts' kernels (the same argument checks, in the same order)
-  if (r_id == 5) return nlml_tucker_objective_ex(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, order, stream);
-  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) return fail(NLML_E_BADARG, "tucker_objective_r: unknown order");
-  if (N < 0) return fail(NLML_E_BADARG, "tucker_objective_r: negative N");
-  if (N > 0 && (!Wm || !x || !params || !cos_params || !err)) return fail(NLML_E_BADARG, "tucker_objective_r: null buffer");
-  if (N > 0 && ldx < NLML_F_REFERENCE) return fail(NLML_E_BADARG, "tucker_objective_r: ldx < 1404");
-  if (N > 0 && order == NLML_TD_ORDER_FAST)
-    if (int rc = check_td_fast_alignment(Wm, x, ldx, "tucker_objective_r")) return rc;
-  return launch_tucker_objective_r(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, r_id, order, stream);
+  return td_objective("tucker_objective_r", Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, r_id, order, stream);
+}
+
+static int td_powell(const char* who, const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
+                     double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order, void* stream) {
+  if (int rc = check_td_args(who, r_id, order, N, ldx, !Wm || !x || !cos_params || !result, Wm, x)) return rc;
+  return launch_tucker_powell_r(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, r_id, order, stream);
+}
+
+int nlml_tucker_powell(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
+                       double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, void* stream) {
+  return td_powell("tucker_powell", Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, 5, NLML_TD_ORDER_REFERENCE, stream);
+}
+
+int nlml_tucker_powell_ex(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
+                          double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int order, void* stream) {
+  return td_powell("tucker_powell", Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, 5, order, stream);
 }
 
 int nlml_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
                          double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order,
                          void* stream) {
-  if (!rank_ok(r_id)) return bad_rank("tucker_powell_r", r_id);
-  if (r_id == 5) return nlml_tucker_powell_ex(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, order, stream);
-  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) return fail(NLML_E_BADARG, "tucker_powell_r: unknown order");
-  if (N < 0) return fail(NLML_E_BADARG, "tucker_powell_r: negative N");
-  if (N > 0 && (!Wm || !x || !cos_params || !result)) return fail(NLML_E_BADARG, "tucker_powell_r: null buffer");
-  if (N > 0 && ldx < NLML_F_REFERENCE) return fail(NLML_E_BADARG, "tucker_powell_r: ldx < 1404");
-  if (N > 0 && order == NLML_TD_ORDER_FAST)
-    if (int rc = check_td_fast_alignment(Wm, x, ldx, "tucker_powell_r")) return rc;
-  return launch_tucker_powell_r(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, r_id, order, stream);
+  return td_powell("tucker_powell_r", Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, r_id, order, stream);
 }
 
-// ---- K3g: objective value + analytic gradient, reference order ---------------------------------------------------------------
+// K3g: objective value + analytic gradient, reference order
 size_t nlml_tucker_gradient_workspace_bytes(int64_t N, int r_id) { return rank_ok(r_id) ? tucker_gradient_workspace_bytes(N) : 0; }
-
-static int check_gradient_args(const char* who, const void* Wm, const void* x, int64_t ldx, const void* params, const void* cos_params,
-                               int64_t N, const void* grad, int r_id) {
-  static thread_local char msg[160];
-  if (!rank_ok(r_id)) return bad_rank(who, r_id);
-  const char* what = nullptr;
-  if (N < 0) what = "negative N";
-  else if (N > 0 && (!Wm || !x || !params || !cos_params || !grad)) what = "null buffer";
-  else if (N > 0 && ldx < NLML_F_REFERENCE) what = "ldx < 1404";
-  if (!what) return 0;
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return fail(NLML_E_BADARG, msg);
-}
 
 int nlml_tucker_gradient_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
                            const double* cos_params, int64_t N, double* err, double* grad, int r_id, void* workspace,
                            size_t workspace_bytes, void* stream) {
-  if (int rc = check_gradient_args("tucker_gradient_r", Wm, x, ldx, params, cos_params, N, grad, r_id)) return rc;
+  if (int rc = check_td_args("tucker_gradient_r", r_id, NLML_TD_ORDER_REFERENCE, N, ldx, !Wm || !x || !params || !cos_params || !grad, Wm, x))
+    return rc;
   const size_t need = tucker_gradient_workspace_bytes(N);
   if (workspace_bytes < need || (need > 0 && !workspace)) return fail(NLML_E_BADARG, "tucker_gradient_r: workspace too small");
   if (misaligned8(workspace) || misaligned8(err) || misaligned8(grad) || misaligned8(params))
@@ -416,47 +366,75 @@ int nlml_tucker_gradient_r(const float* Wm, const float* x, int64_t ldx, const i
 // the same operation order (tucker_grad_ref.h) on host buffers: plain C++, no HIP call
 int nlml_tucker_gradient_host(const float* h_Wm, const float* h_x, int64_t ldx, const int32_t* h_x_index, const double* h_params,
                               const double* h_cos_params, int64_t N, double* h_err, double* h_grad, int r_id, float* h_v) {
-  if (int rc = check_gradient_args("tucker_gradient_host", h_Wm, h_x, ldx, h_params, h_cos_params, N, h_grad, r_id)) return rc;
+  if (int rc = check_td_args("tucker_gradient_host", r_id, NLML_TD_ORDER_REFERENCE, N, ldx,
+                             !h_Wm || !h_x || !h_params || !h_cos_params || !h_grad, h_Wm, h_x))
+    return rc;
   for (int64_t n = 0; n < N; ++n)
     tg_gradient_host(h_Wm, h_x + (h_x_index ? (int64_t)h_x_index[n] : n) * ldx, h_params + n * (3 + r_id), h_cos_params, r_id,
                      h_err ? h_err + n : nullptr, h_grad + n * (3 + r_id), h_v ? h_v + n * NLML_F_REFERENCE : nullptr);
   return 0;
 }
 
-// host-side stepping for n = 3 + r_id parameters: the state the rank-aware device kernel runs
+// ---- host-side stepping of the Powell state machine (powell.h) --------------------------------
+// S = PowellState (the shipped artefacts' 8 parameters, a constant of the type: nlml_powell_*) or PowellStateN (n = 3 + r_id
+// parameters, remembered in the state the rank-aware device kernel runs: nlml_powell_*_n)
 static bool dim_ok(int n) { return n >= 3 + NLML_TUCKER_RANK_MIN && n <= 3 + NLML_TUCKER_RANK_MAX; }
+static int null_pointer(const char* who) {
+  char msg[64];
+  snprintf(msg, sizeof msg, "%s: null pointer", who);
+  return fail(NLML_E_BADARG, msg);
+}
 
-size_t nlml_powell_state_bytes_n(int n) { return dim_ok(n) ? sizeof(PowellStateN) : 0; }
-
-int nlml_powell_init_n(void* h_state, int n, const double* h_x0, double xtol, double ftol) {
-  if (!dim_ok(n)) return bad_rank("powell_init_n", n - 3);
-  if (!h_state || !h_x0) return fail(NLML_E_BADARG, "powell_init_n: null pointer");
-  PowellStateN& s = *static_cast<PowellStateN*>(h_state);
-  std::memset(h_state, 0, sizeof(PowellStateN));
+extern "C++" {   // templates have no C linkage
+template <class S> static int powell_host_init(const char* who, void* h_state, int n, const double* h_x0, double xtol, double ftol) {
+  if (!dim_ok(n)) return bad_rank(who, n - 3);
+  if (!h_state || !h_x0) return null_pointer(who);
+  S& s = *static_cast<S*>(h_state);
+  if (S::kDyn) std::memset(h_state, 0, sizeof(S));
   s.set_dim(n);
   powell_init(s, h_x0, xtol, ftol);
   return 0;
 }
 
-int nlml_powell_step_n(void* h_state, double fin, double* h_xeval) {
-  if (!h_state || !h_xeval) return fail(NLML_E_BADARG, "powell_step_n: null pointer");
-  PowellStateN& s = *static_cast<PowellStateN*>(h_state);
-  if (!dim_ok(s.n)) return bad_rank("powell_step_n", s.n - 3);
+template <class S> static int powell_host_step(const char* who, void* h_state, double fin, double* h_xeval) {
+  if (!h_state || !h_xeval) return null_pointer(who);
+  S& s = *static_cast<S*>(h_state);
+  if (!dim_ok(s.dim())) return bad_rank(who, s.dim() - 3);
   const bool need = powell_step(s, fin);
-  if (need) std::memcpy(h_xeval, s.xeval, sizeof(double) * s.n);
+  if (need) std::memcpy(h_xeval, s.xeval, sizeof(double) * s.dim());
   return need ? 1 : 0;
 }
 
-int nlml_powell_result_n(const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status) {
-  if (!h_state || !h_x) return fail(NLML_E_BADARG, "powell_result_n: null pointer");
-  const PowellStateN& s = *static_cast<const PowellStateN*>(h_state);
-  if (!dim_ok(s.n)) return bad_rank("powell_result_n", s.n - 3);
-  std::memcpy(h_x, s.x, sizeof(double) * s.n);
+template <class S>
+static int powell_host_result(const char* who, const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status) {
+  if (!h_state || !h_x) return null_pointer(who);
+  const S& s = *static_cast<const S*>(h_state);
+  if (!dim_ok(s.dim())) return bad_rank(who, s.dim() - 3);
+  std::memcpy(h_x, s.x, sizeof(double) * s.dim());
   if (h_fval) *h_fval = s.fval;
   if (h_nfev) *h_nfev = s.nfev;
   if (h_nit) *h_nit = s.iter;
   if (h_status) *h_status = s.status;
   return 0;
+}
+}  // extern "C++"
+
+size_t nlml_powell_state_bytes(void) { return sizeof(PowellState); }
+int nlml_powell_init(void* h_state, const double* h_x0, double xtol, double ftol) {
+  return powell_host_init<PowellState>("powell_init", h_state, PW_N, h_x0, xtol, ftol);
+}
+int nlml_powell_step(void* h_state, double fin, double* h_xeval) { return powell_host_step<PowellState>("powell_step", h_state, fin, h_xeval); }
+int nlml_powell_result(const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status) {
+  return powell_host_result<PowellState>("powell_result", h_state, h_x, h_fval, h_nfev, h_nit, h_status);
+}
+
+size_t nlml_powell_state_bytes_n(int n) { return dim_ok(n) ? sizeof(PowellStateN) : 0; }
+int nlml_powell_init_n(void* h_state, int n, const double* h_x0, double xtol, double ftol) {
+  return powell_host_init<PowellStateN>("powell_init_n", h_state, n, h_x0, xtol, ftol);
+}
+int nlml_powell_step_n(void* h_state, double fin, double* h_xeval) { return powell_host_step<PowellStateN>("powell_step_n", h_state, fin, h_xeval); }
+int nlml_powell_result_n(const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status) {
+  return powell_host_result<PowellStateN>("powell_result_n", h_state, h_x, h_fval, h_nfev, h_nit, h_status);
 }
 
 }  // extern "C"

@@ -151,8 +151,8 @@ std::tuple<at::Tensor, at::Tensor> landmarks_to_pose_valid(const at::Tensor& raw
   return {r.pose, r.valid};
 }
 
-// -> the identity rank R of Wm [27 R, 1404]
-int check_td(const at::Tensor& Wm, const at::Tensor& x, const at::Tensor& cosp) {
+// -> the identity rank R of Wm [27 R, 1404]; params (objective, gradient): f64[N, 3 + R], one row of x per row of it
+int check_td(const at::Tensor& Wm, const at::Tensor& x, const at::Tensor& cosp, const at::Tensor* params = nullptr) {
   need(Wm, "Wm", at::kFloat);
   need(x, "x", at::kFloat);
   need(cosp, "cos_params", at::kDouble);
@@ -163,16 +163,19 @@ int check_td(const at::Tensor& Wm, const at::Tensor& x, const at::Tensor& cosp) 
               "Wm: expected [27*R,1404] for an identity rank R in [", NLML_TUCKER_RANK_MIN, ", ", NLML_TUCKER_RANK_MAX, "], got ", Wm.sizes());
   TORCH_CHECK(x.dim() == 2 && x.size(1) == F_REF, "x: expected [N,1404], got ", x.sizes());
   TORCH_CHECK(cosp.dim() == 3 && cosp.size(0) == 3 && cosp.size(1) == 3 && cosp.size(2) == 4, "cos_params: expected [3,3,4], got ", cosp.sizes());
-  return (int)(Wm.size(0) / 27);
+  const int r_id = (int)(Wm.size(0) / 27);
+  if (params) {
+    need(*params, "params", at::kDouble);
+    same_device(x, *params, "params");
+    TORCH_CHECK(params->dim() == 2 && params->size(1) == 3 + r_id, "params: expected [N,", 3 + r_id, "], got ", params->sizes());
+    TORCH_CHECK(x.size(0) == params->size(0), "x has ", x.size(0), " rows but params has ", params->size(0));
+  }
+  return r_id;
 }
 
 at::Tensor tucker_objective(const at::Tensor& Wm_, const at::Tensor& x_, const at::Tensor& params_, const at::Tensor& cosp_,
                             std::string order) {
-  const int r_id = check_td(Wm_, x_, cosp_);
-  need(params_, "params", at::kDouble);
-  same_device(x_, params_, "params");
-  TORCH_CHECK(params_.dim() == 2 && params_.size(1) == 3 + r_id, "params: expected [N,", 3 + r_id, "], got ", params_.sizes());
-  TORCH_CHECK(x_.size(0) == params_.size(0), "x has ", x_.size(0), " rows but params has ", params_.size(0));
+  const int r_id = check_td(Wm_, x_, cosp_, &params_);
   const at::Tensor Wm = Wm_.contiguous(), x = x_.contiguous(), params = params_.contiguous(), cosp = cosp_.contiguous();
   const int64_t N = params.size(0);
   at::Tensor err = at::empty({N}, params.options());
@@ -186,11 +189,7 @@ at::Tensor tucker_objective(const at::Tensor& Wm_, const at::Tensor& x_, const a
 // K3g: objective value and analytic gradient in the reference's operation order -> (err f64[N], grad f64[N,3+R])
 std::tuple<at::Tensor, at::Tensor> tucker_gradient(const at::Tensor& Wm_, const at::Tensor& x_, const at::Tensor& params_,
                                                    const at::Tensor& cosp_) {
-  const int r_id = check_td(Wm_, x_, cosp_);
-  need(params_, "params", at::kDouble);
-  same_device(x_, params_, "params");
-  TORCH_CHECK(params_.dim() == 2 && params_.size(1) == 3 + r_id, "params: expected [N,", 3 + r_id, "], got ", params_.sizes());
-  TORCH_CHECK(x_.size(0) == params_.size(0), "x has ", x_.size(0), " rows but params has ", params_.size(0));
+  const int r_id = check_td(Wm_, x_, cosp_, &params_);
   const at::Tensor Wm = Wm_.contiguous(), x = x_.contiguous(), params = params_.contiguous(), cosp = cosp_.contiguous();
   const int64_t N = params.size(0);
   at::Tensor err = at::empty({N}, params.options()), grad = at::empty({N, 3 + r_id}, params.options());

@@ -1,7 +1,7 @@
 // tucker_rank.hip -- K3 and the device-side Powell minimiser for any Tucker identity rank R = 1..16 (nlml_tucker_objective_r,
 // nlml_tucker_powell_r): Wm f32[27 R, 1404], 3 + R parameters per evaluation.  The arithmetic is tucker_ref.h's (reference order, the
-// parity mode) and tucker_common.h's (matrix cores) with the rank as a run-time value: tucker_rank.h.  R = 5 through these entry points
-// is dispatched to the kernels of tucker_objective.hip / tucker_powell.hip, so the shipped artefacts run the code they always ran.
+// parity mode) and tucker_common.h's (matrix cores) with the rank as a run-time value: tucker_rank.h.  R = 5 is handed on by the launchers
+// below to the kernels of tucker_objective.hip / tucker_powell.hip, so the shipped artefacts run the code they always ran.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -212,6 +212,7 @@ __global__ __launch_bounds__(ORDER == NLML_TD_ORDER_REFERENCE ? TR_NT : TNT, 1) 
 
 int launch_tucker_objective_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
                               const double* cos_params, int64_t N, double* err, double* x_hat, int r_id, int order, void* stream) {
+  if (r_id == 5) return launch_tucker_objective(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, order, stream);   // the shipped artefacts' kernels
   if (N == 0) return 0;
   const dim3 grid((unsigned)((N + EV - 1) / EV));
   if (order == NLML_TD_ORDER_REFERENCE)
@@ -226,6 +227,7 @@ int launch_tucker_objective_r(const float* Wm, const float* x, int64_t ldx, cons
 int launch_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
                            double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order,
                            void* stream) {
+  if (r_id == 5) return launch_tucker_powell(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, order, stream);
   if (N == 0) return 0;
   const dim3 grid((unsigned)((N + EV - 1) / EV));
   if (order == NLML_TD_ORDER_REFERENCE)

@@ -191,27 +191,35 @@ def landmarks_to_pose(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = T
     return _k2_forward("", None, raw, blob, F_REF, normalize, return_latent, return_valid)
 
 
-def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, cos_params: torch.Tensor,
-                     x_index: torch.Tensor | None = None, return_xhat: bool = False, order="reference"):
-    """Batched objective (TD_Tester.py:31-58): Wm f32[27R,1404], x f32[M,1404], params f64[N,3+R],
-    cos_params f64[3,3,4] -> err f64[N] (+ x_hat f64[N,1404]); R = the identity rank, 1..16 (5 for the shipped artefacts).  order: "reference" (the default and the parity mode: np.einsum's
-    operation order and numpy's pairwise sum -- the reference's bits) or "fast" (opt-in: a GEMM on the f64 matrix cores, <= 1e-12
-    relative, ~5x the evaluations/s)."""
-    order = _lib.td_order_from_name(order)
+# ---- the TD path (K3 objective, K3g gradient, device Powell): one operand preamble behind the three public wrappers ----------------
+def _td_operands(Wm, x, cos_params, params=None, x_index=None, x0=None):
+    """The operand checks of the TD wrappers -> (Wm, x, cos_params, params, x_index, x0, r_id, N), every tensor contiguous.  With params
+    (objective, gradient): N = its rows, evaluation n on row n of x, or on row x_index[n].  Without (Powell): one minimisation per row
+    of x, N of them, started at x0[n] if x0 is given."""
     _need_cuda(Wm, "Wm", torch.float32)
     _need_cuda(x, "x", torch.float32)
-    _need_cuda(params, "params", torch.float64)
+    if params is not None:
+        _need_cuda(params, "params", torch.float64)
     _need_cuda(cos_params, "cos_params", torch.float64)
     if Wm.dim() != 2 or Wm.shape[1] != F_REF:
         raise ValueError(f"Wm: expected [27*R,1404], got {tuple(Wm.shape)}")
     r_id = _lib.tucker_rank_of_rows(Wm.shape[0])
     if x.dim() != 2 or x.shape[1] != F_REF:
-        raise ValueError(f"x: expected [M,1404], got {tuple(x.shape)}")
-    if params.dim() != 2 or params.shape[1] != 3 + r_id:
+        raise ValueError(f"x: expected [{'N' if params is None else 'M'},1404], got {tuple(x.shape)}")
+    if params is not None and (params.dim() != 2 or params.shape[1] != 3 + r_id):
         raise ValueError(f"params: expected [N,{3 + r_id}] for Wm of identity rank {r_id}, got {tuple(params.shape)}")
     if tuple(cos_params.shape) != (3, 3, 4):
         raise ValueError(f"cos_params: expected [3,3,4], got {tuple(cos_params.shape)}")
-    Wm, x, params, cos_params = Wm.contiguous(), x.contiguous(), params.contiguous(), cos_params.contiguous()
+    Wm, x, cos_params = Wm.contiguous(), x.contiguous(), cos_params.contiguous()
+    if params is None:
+        N = x.shape[0]
+        if x0 is not None:
+            _need_cuda(x0, "x0", torch.float64)
+            if tuple(x0.shape) != (N, 3 + r_id):
+                raise ValueError(f"x0: expected [{N},{3 + r_id}], got {tuple(x0.shape)}")
+            x0 = x0.contiguous()
+        return Wm, x, cos_params, None, None, x0, r_id, N
+    params = params.contiguous()
     N = params.shape[0]
     if x_index is not None:
         _need_cuda(x_index, "x_index", torch.int32)
@@ -222,6 +230,17 @@ def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, co
             raise IndexError("x_index out of range")
     elif x.shape[0] != N:
         raise ValueError(f"x has {x.shape[0]} rows but params has {N} (pass x_index to share rows)")
+    return Wm, x, cos_params, params, x_index, None, r_id, N
+
+
+def tucker_objective(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, cos_params: torch.Tensor,
+                     x_index: torch.Tensor | None = None, return_xhat: bool = False, order="reference"):
+    """Batched objective (TD_Tester.py:31-58): Wm f32[27R,1404], x f32[M,1404], params f64[N,3+R],
+    cos_params f64[3,3,4] -> err f64[N] (+ x_hat f64[N,1404]); R = the identity rank, 1..16 (5 for the shipped artefacts).  order: "reference" (the default and the parity mode: np.einsum's
+    operation order and numpy's pairwise sum -- the reference's bits) or "fast" (opt-in: a GEMM on the f64 matrix cores, <= 1e-12
+    relative, ~5x the evaluations/s)."""
+    order = _lib.td_order_from_name(order)
+    Wm, x, cos_params, params, x_index, _, r_id, N = _td_operands(Wm, x, cos_params, params, x_index)
     err = torch.empty((N,), dtype=torch.float64, device=x.device)
     xh = torch.empty((N, F_REF), dtype=torch.float64, device=x.device) if return_xhat else None
     with _on_device_of(("x", x), ("Wm", Wm), ("params", params), ("cos_params", cos_params), ("x_index", x_index)) as stream:
@@ -238,30 +257,7 @@ def tucker_gradient(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, cos
     own operation order: Wm f32[27R,1404], x f32[M,1404], params f64[N,3+R], cos_params f64[3,3,4] -> (err f64[N], grad f64[N,3+R]),
     or grad alone with return_err=False.  err carries the bits of tucker_objective(order="reference"); every gradient component the
     reference's own (csrc/tucker_grad_ref.h has the order).  R = 1..16."""
-    _need_cuda(Wm, "Wm", torch.float32)
-    _need_cuda(x, "x", torch.float32)
-    _need_cuda(params, "params", torch.float64)
-    _need_cuda(cos_params, "cos_params", torch.float64)
-    if Wm.dim() != 2 or Wm.shape[1] != F_REF:
-        raise ValueError(f"Wm: expected [27*R,1404], got {tuple(Wm.shape)}")
-    r_id = _lib.tucker_rank_of_rows(Wm.shape[0])
-    if x.dim() != 2 or x.shape[1] != F_REF:
-        raise ValueError(f"x: expected [M,1404], got {tuple(x.shape)}")
-    if params.dim() != 2 or params.shape[1] != 3 + r_id:
-        raise ValueError(f"params: expected [N,{3 + r_id}] for Wm of identity rank {r_id}, got {tuple(params.shape)}")
-    if tuple(cos_params.shape) != (3, 3, 4):
-        raise ValueError(f"cos_params: expected [3,3,4], got {tuple(cos_params.shape)}")
-    Wm, x, params, cos_params = Wm.contiguous(), x.contiguous(), params.contiguous(), cos_params.contiguous()
-    N = params.shape[0]
-    if x_index is not None:
-        _need_cuda(x_index, "x_index", torch.int32)
-        if x_index.shape != (N,):
-            raise ValueError("x_index: expected [N]")
-        x_index = x_index.contiguous()
-        if N and (int(x_index.min()) < 0 or int(x_index.max()) >= x.shape[0]):
-            raise IndexError("x_index out of range")
-    elif x.shape[0] != N:
-        raise ValueError(f"x has {x.shape[0]} rows but params has {N} (pass x_index to share rows)")
+    Wm, x, cos_params, params, x_index, _, r_id, N = _td_operands(Wm, x, cos_params, params, x_index)
     err = torch.empty((N,), dtype=torch.float64, device=x.device) if return_err else None
     grad = torch.empty((N, 3 + r_id), dtype=torch.float64, device=x.device)
     ws_bytes = _lib.lib().nlml_tucker_gradient_workspace_bytes(N, r_id)
@@ -312,24 +308,8 @@ def tucker_powell(Wm: torch.Tensor, x: torch.Tensor, cos_params: torch.Tensor, x
 
     Returns dict(x=f64[N,3+R] (w_y,w_p,w_r radians + u_id), fun=f64[N], nfev=i32[N], nit=i32[N], status=i32[N]).
     """
-    _need_cuda(Wm, "Wm", torch.float32)
-    _need_cuda(x, "x", torch.float32)
-    _need_cuda(cos_params, "cos_params", torch.float64)
-    if Wm.dim() != 2 or Wm.shape[1] != F_REF:
-        raise ValueError(f"Wm: expected [27*R,1404], got {tuple(Wm.shape)}")
-    r_id = _lib.tucker_rank_of_rows(Wm.shape[0])
+    Wm, x, cos_params, _, _, x0, r_id, N = _td_operands(Wm, x, cos_params, x0=x0)
     n_par = 3 + r_id
-    if x.dim() != 2 or x.shape[1] != F_REF:
-        raise ValueError(f"x: expected [N,1404], got {tuple(x.shape)}")
-    if tuple(cos_params.shape) != (3, 3, 4):
-        raise ValueError(f"cos_params: expected [3,3,4], got {tuple(cos_params.shape)}")
-    Wm, x, cos_params = Wm.contiguous(), x.contiguous(), cos_params.contiguous()
-    N = x.shape[0]
-    if x0 is not None:
-        _need_cuda(x0, "x0", torch.float64)
-        if tuple(x0.shape) != (N, n_par):
-            raise ValueError(f"x0: expected [{N},{n_par}], got {tuple(x0.shape)}")
-        x0 = x0.contiguous()
     order = _lib.td_order_from_name(order)
     dev = x.device
     res = torch.empty((N, n_par), dtype=torch.float64, device=dev)
