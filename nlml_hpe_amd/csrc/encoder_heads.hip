@@ -366,8 +366,8 @@ __device__ __forceinline__ void job_store(const Ctx& c, const f32x16 (&acc)[NB][
 // of a ~35-instruction IEEE division sequence, and the value is rounded to f32 afterwards anyway.
 __device__ __forceinline__ double div_ipd(double n, double d, double y) {
   const double q = n * y;
-  const double r = fma(-q, d, n);
-  return fma(r, y, q);
+  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
+  return fma(-r, y, q);
 }
 
 // ipd = ||lm[33] - lm[263]||_2 in f64 (== np.linalg.norm: sqrt of an fma-chained ddot), 1e-6 if exactly 0

@@ -180,8 +180,8 @@ __device__ __forceinline__ __bf16* img(const Ctx& c, int off_bytes) { return rei
 
 __device__ __forceinline__ double div_ipd(double n, double d, double y) {   // == IEEE n / d for these operands (K1)
   const double q = n * y;
-  const double r = fma(-q, d, n);
-  return fma(r, y, q);
+  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
+  return fma(-r, y, q);
 }
 
 // the heads' images for BOTH 32-face blocks side by side (byte offsets): HA / HC per block, then HB / HD per block, below the latent

@@ -41,8 +41,8 @@ namespace hx {
 
 __device__ __forceinline__ double div_ipd(double n, double d, double y) {
   const double q = n * y;
-  const double r = fma(-q, d, n);
-  return fma(r, y, q);
+  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
+  return fma(-r, y, q);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -124,8 +124,8 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
     if (link == 0) { nA = (double)st.v[e0]; nB = (double)st.v[e1]; asm volatile("" : "+v"(nA), "+v"(nB)); }
     if (link == 1) { nA = nA - r0; nB = nB - r1; asm volatile("" : "+v"(nA), "+v"(nB)); }
     if (link == 2) { qA = nA * rcp; qB = nB * rcp; asm volatile("" : "+v"(qA), "+v"(qB)); }
-    if (link == 3) { nA = fma(-qA, ipd, nA); nB = fma(-qB, ipd, nB); asm volatile("" : "+v"(nA), "+v"(nB)); }
-    if (link == 4) { qA = fma(nA, rcp, qA); qB = fma(nB, rcp, qB); asm volatile("" : "+v"(qA), "+v"(qB)); }
+    if (link == 3) { nA = fma(qA, ipd, -nA); nB = fma(qB, ipd, -nB); asm volatile("" : "+v"(nA), "+v"(nB)); }   // negated residual, as div_ipd
+    if (link == 4) { qA = fma(-nA, rcp, qA); qB = fma(-nB, rcp, qB); asm volatile("" : "+v"(qA), "+v"(qB)); }
     if (link == 5) { st.v[e0] = (float)qA; st.v[e1] = (float)qB; asm volatile("" : "+v"(st.v[e0]), "+v"(st.v[e1])); }
   };
   auto lw_rotate = [&]() {   // next slab: columns + 32 => phase + 2

@@ -31,8 +31,8 @@ struct RescueIn {
 
 __device__ __forceinline__ double rescue_div(double n, double d, double y) {   // == IEEE n / d for these operands (K1)
   const double q = n * y;
-  const double r = fma(-q, d, n);
-  return fma(r, y, q);
+  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
+  return fma(-r, y, q);
 }
 
 __device__ __forceinline__ void rescue_load8(const RescueIn& in, int g, int k0, float (&v)[8]) {

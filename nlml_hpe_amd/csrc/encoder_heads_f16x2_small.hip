@@ -45,8 +45,8 @@ __device__ __forceinline__ float activate(int act, float v) {
 
 __device__ __forceinline__ double div_ipd(double n, double d, double y) {
   const double q = n * y;
-  const double r = fma(-q, d, n);
-  return fma(r, y, q);
+  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
+  return fma(-r, y, q);
 }
 
 // ---- pre-pass: x (f32 rows, or raw landmarks with optional IPD normalisation) -> hi/lo fragments of layer 0's input.

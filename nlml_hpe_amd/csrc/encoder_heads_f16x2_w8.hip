@@ -37,8 +37,8 @@ namespace hx {
 
 __device__ __forceinline__ double div_ipd_w8(double n, double d, double y) {   // == IEEE n / d for these operands (K1)
   const double q = n * y;
-  const double r = fma(-q, d, n);
-  return fma(r, y, q);
+  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
+  return fma(-r, y, q);
 }
 
 // One K step of a layer-0 pass (two neuron blocks x two face blocks, split accumulators): step_fine's products in step_fine's order

@@ -21,8 +21,10 @@ namespace nlml {
 // path are bit-identical; 3 multiply-adds per element instead of an IEEE division sequence.
 __device__ __forceinline__ double div_ipd(double n, double d, double y) {
   const double q = n * y;
-  const double r = fma(-q, d, n);
-  return fma(r, y, q);
+  // the residual is taken NEGATED, r = -(n - q d), and subtracted: same value, same instructions, but a zero numerator keeps its
+  // sign -- fma(-q, d, n) is +0 for n = -0 and fma(+0, y, -0) = +0, where IEEE division gives -0 (tests/test_ipd_exact_gpu.py, family E)
+  const double r = fma(q, d, -n);
+  return fma(-r, y, q);
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

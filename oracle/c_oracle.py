@@ -37,6 +37,14 @@ def normalize_ipd(raw: np.ndarray, normalize: bool = True) -> np.ndarray:
     return out
 
 
+def ipd(raw: np.ndarray) -> np.ndarray:
+    """f64[B]: the divisor of normalize_ipd per face."""
+    raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(-1, 1404)
+    out = np.empty(raw.shape[0], np.float64)
+    lib().oracle_ipd(_p(raw), C.c_int64(raw.shape[0]), _p(out))
+    return out
+
+
 def encoder_heads(x: np.ndarray, params, order: int = 2, want_latent=False, want_pre_tanh=False):
     """params: oracle.encoder_heads.Params.  order 0 = k ascending, 1 = one MFMA-order chain per output, 2 (default) = the f32
     HIP kernel's order: MFMA-order chains with layers 0 to 3 summed in blocks of 128 k (encoder_heads.hip fold_block)."""

@@ -13,6 +13,18 @@
 #include <string.h>
 
 /* ---- helpers/FeatureExtractor.py:30-66 + the .float() at :101 ---------------------------- */
+/* ipd[b] of raw [B,1404] as oracle_normalize_ipd below computes it (the 1e-6 branch included) */
+void oracle_ipd(const float* raw, int64_t B, double* ipd_out) {
+  for (int64_t b = 0; b < B; ++b) {
+    const float* p = raw + b * 1404;
+    const double dx = (double)p[99] - (double)p[789];
+    const double dy = (double)p[100] - (double)p[790];
+    const double dz = (double)p[101] - (double)p[791];
+    const double ipd = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
+    ipd_out[b] = ipd == 0.0 ? 1e-6 : ipd;
+  }
+}
+
 void oracle_normalize_ipd(const float* raw, int64_t B, int normalize, float* out) {
   for (int64_t b = 0; b < B; ++b) {
     const float* p = raw + b * 1404;
