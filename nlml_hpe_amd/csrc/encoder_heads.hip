@@ -39,14 +39,13 @@
 
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
+#include "encoder_heads_common.h"
+#include "ipd_norm.h"
 #include "layout.h"
 
 namespace nlml {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+// f32 vector types, ACT_*, activate<ACT> and load_bias<NB, NFB>: encoder_heads_common.h
 
 struct EncArgs {
   const float* x;       // [B, ldx] features, or raw landmarks [B,1404] when norm != 0
@@ -63,33 +62,6 @@ struct EncArgs {
   int reeval_over;      // >= 0: RE-EVALUATION launch behind a split-f16 launch (NLML_MODE_F16X2S): a tile is computed only if more
                         // than this many of its faces hold a non-finite pose in `out`, and only those faces are written; -1: off
 };
-
-template <int ACT>
-__device__ __forceinline__ float activate(float v) {
-  if (ACT == ACT_RELU) return v < 0.0f ? 0.0f : v;   // NaN propagates like torch.relu (fmaxf would swallow it)
-  if (ACT == ACT_TANH) return tanhf(v);
-  return v;
-}
-
-// acc[nb][fb]: neuron block nb x face block fb.  The bias depends on the neuron only.
-template <int NB, int NFB>
-__device__ __forceinline__ void load_bias(f32x16 (&acc)[NB][NFB], const f32x4* __restrict__ b, int h) {
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const f32x4* p = b + (nb * 2 + h) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 v = p[q];
-#pragma unroll
-      for (int fb = 0; fb < NFB; ++fb) {
-        acc[nb][fb][4 * q + 0] = v[0];
-        acc[nb][fb][4 * q + 1] = v[1];
-        acc[nb][fb][4 * q + 2] = v[2];
-        acc[nb][fb][4 * q + 3] = v[3];
-      }
-    }
-  }
-}
 
 template <int NB, int NFB>
 __device__ __forceinline__ void mfma_step(f32x16 (&acc)[NB][NFB], const f32x4 (&w)[NB], const f32x4 (&x)[NFB]) {
@@ -361,26 +333,7 @@ __device__ __forceinline__ void job_store(const Ctx& c, const f32x16 (&acc)[NB][
 // ------------------------------------------------------------------------------------------
 // Layer 0, one pass: x[64,F] streamed through LDS slabs of 32 columns; this wave computes the 128
 // neurons of job `job` (4 blocks) for both face blocks.
-// n / ipd for the IPD normalisation, correctly rounded in f64 from a once-per-row reciprocal (Markstein:
-// q = n*y, r = n - q*d exactly by fma, q' = q + r*y with y = RN(1/d)): 3 multiply-adds per element instead
-// of a ~35-instruction IEEE division sequence, and the value is rounded to f32 afterwards anyway.
-__device__ __forceinline__ double div_ipd(double n, double d, double y) {
-  const double q = n * y;
-  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
-  return fma(-r, y, q);
-}
-
-// ipd = ||lm[33] - lm[263]||_2 in f64 (== np.linalg.norm: sqrt of an fma-chained ddot), 1e-6 if exactly 0
-__device__ __forceinline__ void ipd_of_row(const float* p, double& ipd, double& rcp) {
-  const double dx = (double)p[99] - (double)p[789];
-  const double dy = (double)p[100] - (double)p[790];
-  const double dz = (double)p[101] - (double)p[791];
-  double d = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
-  if (d == 0.0) d = 1e-6;
-  ipd = d;
-  rcp = 1.0 / d;
-}
-
+// The IPD normalisation on the way in is ipd_norm.h's: the rows' ipd and reciprocal once per tile, div_ipd per element.
 struct E0Stager {
   const float *p0, *p1;       // this thread's two rows (srow, srow + 32)
   // scalar members only: arrays inside this struct end up in scratch memory (private stack) on hipcc 7.2,
@@ -410,8 +363,12 @@ __device__ __forceinline__ void e0_stager_init(E0Stager& g, const EncArgs& a, in
   g.rcp0 = g.rcp1 = 1.0;
   g.r0a = g.r0b = g.r0c = g.r1a = g.r1b = g.r1c = 0.0;
   if (NORM) {  // IPD normalisation constants of the two rows (FeatureExtractor.py:38-48,85-86), f64
-    ipd_of_row(g.p0, g.ipd0, g.rcp0);
-    if (NFB == 2) ipd_of_row(g.p1, g.ipd1, g.rcp1);
+    g.ipd0 = ipd_length(g.p0);
+    g.rcp0 = ipd_reciprocal(g.ipd0);
+    if (NFB == 2) {
+      g.ipd1 = ipd_length(g.p1);
+      g.rcp1 = ipd_reciprocal(g.ipd1);
+    }
   }
 }
 
@@ -515,15 +472,11 @@ __device__ __forceinline__ void stage_e0_pass(const Ctx& c, const EncArgs& a, E0
 
   if (NORM) {  // phase of slab 0: this thread's first column is scol, element e is column scol + e;
                // landmark 1 (columns 3,4,5) is the reference point (FeatureExtractor.py:85-86)
-    const double x0 = (double)g.p0[3], y0 = (double)g.p0[4], z0 = (double)g.p0[5];
-    const double x1 = NFB == 2 ? (double)g.p1[3] : 0.0, y1 = NFB == 2 ? (double)g.p1[4] : 0.0, z1 = NFB == 2 ? (double)g.p1[5] : 0.0;
+    const double x0 = ipd_origin(g.p0, 0), y0 = ipd_origin(g.p0, 1), z0 = ipd_origin(g.p0, 2);
+    const double x1 = NFB == 2 ? ipd_origin(g.p1, 0) : 0.0, y1 = NFB == 2 ? ipd_origin(g.p1, 1) : 0.0, z1 = NFB == 2 ? ipd_origin(g.p1, 2) : 0.0;
     const int ph = g.scol % 3;   // coordinate (0 x, 1 y, 2 z) of this thread's first column
-    g.r0a = ph == 0 ? x0 : (ph == 1 ? y0 : z0);
-    g.r0b = ph == 0 ? y0 : (ph == 1 ? z0 : x0);
-    g.r0c = ph == 0 ? z0 : (ph == 1 ? x0 : y0);
-    g.r1a = ph == 0 ? x1 : (ph == 1 ? y1 : z1);
-    g.r1b = ph == 0 ? y1 : (ph == 1 ? z1 : x1);
-    g.r1c = ph == 0 ? z1 : (ph == 1 ? x1 : y1);
+    ipd_phase(ph, x0, y0, z0, g.r0a, g.r0b, g.r0c);
+    ipd_phase(ph, x1, y1, z1, g.r1a, g.r1b, g.r1c);
   }
   f32x4 setA[2], setB[2];
   gload(0, setA);

@@ -6,18 +6,16 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nlml_hpe.h"
+#include "encoder_heads_common.h"
 #include "layout.h"
 
 namespace nlml {
 namespace bf {   // (stage table, strides and LDS offsets of the bf16 mode: layout.h)
 namespace w8 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// f32 vector types, ACT_*, activate<ACT> and load_bias<NB, NFB>: encoder_heads_common.h
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 
 struct Args {
   const float* x;
@@ -28,32 +26,6 @@ struct Args {
   float* latent;
   uint8_t* valid;
 };
-
-template <int ACT>
-__device__ __forceinline__ float activate(float v) {
-  if (ACT == ACT_RELU) return v < 0.0f ? 0.0f : v;
-  if (ACT == ACT_TANH) return tanhf(v);
-  return v;
-}
-
-template <int NB, int NFB>
-__device__ __forceinline__ void load_bias(f32x16 (&acc)[NB][NFB], const f32x4* __restrict__ b, int h) {
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const f32x4* p = b + (nb * 2 + h) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 v = p[q];
-#pragma unroll
-      for (int fb = 0; fb < NFB; ++fb) {
-        acc[nb][fb][4 * q + 0] = v[0];
-        acc[nb][fb][4 * q + 1] = v[1];
-        acc[nb][fb][4 * q + 2] = v[2];
-        acc[nb][fb][4 * q + 3] = v[3];
-      }
-    }
-  }
-}
 
 // One K step, one load per MFMA slot: MFMA m (nb-major over the face blocks, the order the four-wave kernel gives every accumulator) is
 // followed by item m of the step's fetches -- the NFB LDS reads of the next step's x operands, then the NB weight fragments D steps ahead
@@ -177,12 +149,6 @@ struct Ctx {
 };
 
 __device__ __forceinline__ __bf16* img(const Ctx& c, int off_bytes) { return reinterpret_cast<__bf16*>(c.lds + off_bytes); }
-
-__device__ __forceinline__ double div_ipd(double n, double d, double y) {   // == IEEE n / d for these operands (K1)
-  const double q = n * y;
-  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
-  return fma(-r, y, q);
-}
 
 // the heads' images for BOTH 32-face blocks side by side (byte offsets): HA / HC per block, then HB / HD per block, below the latent
 constexpr int P_HA = 32 * S_HA * 2, P_HB = 32 * S_HB * 2;

@@ -19,6 +19,7 @@
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
 #include "encoder_heads_bf16_dev.h"
+#include "ipd_norm.h"
 #include "layout.h"
 
 namespace nlml {
@@ -43,15 +44,9 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
   const float* p = a.x + r * a.ldx;
   double ipd = 1.0, rcp = 1.0, ra = 0.0, rb = 0.0, rc = 0.0;
   if (NORM) {
-    const double dx = (double)p[99] - (double)p[789], dy = (double)p[100] - (double)p[790], dz = (double)p[101] - (double)p[791];
-    ipd = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
-    if (ipd == 0.0) ipd = 1e-6;
-    rcp = 1.0 / ipd;
-    const double x0 = (double)p[3], y0 = (double)p[4], z0 = (double)p[5];
-    const int ph = scol % 3;   // coordinate of this thread's first column; a slab later the phase is + 64 % 3 = + 1
-    ra = ph == 0 ? x0 : (ph == 1 ? y0 : z0);
-    rb = ph == 0 ? y0 : (ph == 1 ? z0 : x0);
-    rc = ph == 0 ? z0 : (ph == 1 ? x0 : y0);
+    double x0, y0, z0;
+    ipd_setup(p, ipd, rcp, x0, y0, z0);
+    ipd_phase(scol % 3, x0, y0, z0, ra, rb, rc);   // coordinate of this thread's first column; a slab later the phase is + 64 % 3 = + 1
   }
   unsigned nzbits = 0u;
 

@@ -31,19 +31,14 @@
 
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
+#include "ipd_norm.h"
 #include "encoder_heads_f16x2_dev.h"
 #include "layout.h"
 
 namespace nlml {
 namespace hx {
 
-// operand types, MFMA steps, K loops, stores and the network's tail: encoder_heads_f16x2_dev.h
-
-__device__ __forceinline__ double div_ipd(double n, double d, double y) {
-  const double q = n * y;
-  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
-  return fma(-r, y, q);
-}
+// operand types, MFMA steps, K loops, stores and the network's tail: encoder_heads_f16x2_dev.h; the IPD normalisation: ipd_norm.h
 
 // ------------------------------------------------------------------------------------------
 // Layer 0 in ONE pass over x: x[64,F] f32 -> (optional IPD normalisation in f64) -> hi/lo f16 -> three rotating LDS slabs of
@@ -73,15 +68,9 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
   // 3e-4 degree (65,536 random faces), so it is not used.
   double ipd = 1.0, rcp = 1.0, ra = 0.0, rb = 0.0, rc = 0.0;
   if (NORM) {
-    const double dx = (double)p[99] - (double)p[789], dy = (double)p[100] - (double)p[790], dz = (double)p[101] - (double)p[791];
-    ipd = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
-    if (ipd == 0.0) ipd = 1e-6;
-    rcp = 1.0 / ipd;
-    const double x0 = (double)p[3], y0 = (double)p[4], z0 = (double)p[5];
-    const int ph = scol % 3;   // coordinate of this thread's first column; a slab later the phase is + 32 % 3 = + 2
-    ra = ph == 0 ? x0 : (ph == 1 ? y0 : z0);
-    rb = ph == 0 ? y0 : (ph == 1 ? z0 : x0);
-    rc = ph == 0 ? z0 : (ph == 1 ? x0 : y0);
+    double x0, y0, z0;
+    ipd_setup(p, ipd, rcp, x0, y0, z0);
+    ipd_phase(scol % 3, x0, y0, z0, ra, rb, rc);   // coordinate of this thread's first column; a slab later the phase is + 32 % 3 = + 2
   }
   unsigned nzbits = 0u;
 
@@ -123,9 +112,9 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
     // (the empty asm pins each link to its slot: pure arithmetic is otherwise sunk towards its use, back into one cluster)
     if (link == 0) { nA = (double)st.v[e0]; nB = (double)st.v[e1]; asm volatile("" : "+v"(nA), "+v"(nB)); }
     if (link == 1) { nA = nA - r0; nB = nB - r1; asm volatile("" : "+v"(nA), "+v"(nB)); }
-    if (link == 2) { qA = nA * rcp; qB = nB * rcp; asm volatile("" : "+v"(qA), "+v"(qB)); }
-    if (link == 3) { nA = fma(qA, ipd, -nA); nB = fma(qB, ipd, -nB); asm volatile("" : "+v"(nA), "+v"(nB)); }   // negated residual, as div_ipd
-    if (link == 4) { qA = fma(-nA, rcp, qA); qB = fma(-nB, rcp, qB); asm volatile("" : "+v"(qA), "+v"(qB)); }
+    if (link == 2) { qA = div_ipd_quotient(nA, rcp); qB = div_ipd_quotient(nB, rcp); asm volatile("" : "+v"(qA), "+v"(qB)); }
+    if (link == 3) { nA = div_ipd_residual(qA, ipd, nA); nB = div_ipd_residual(qB, ipd, nB); asm volatile("" : "+v"(nA), "+v"(nB)); }
+    if (link == 4) { qA = div_ipd_correct(qA, nA, rcp); qB = div_ipd_correct(qB, nB, rcp); asm volatile("" : "+v"(qA), "+v"(qB)); }
     if (link == 5) { st.v[e0] = (float)qA; st.v[e1] = (float)qB; asm volatile("" : "+v"(st.v[e0]), "+v"(st.v[e1])); }
   };
   auto lw_rotate = [&]() {   // next slab: columns + 32 => phase + 2

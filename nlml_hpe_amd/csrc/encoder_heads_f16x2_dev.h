@@ -8,17 +8,15 @@
 #include <type_traits>
 
 #include "../../include/nlml_hpe.h"
+#include "encoder_heads_common.h"
 #include "layout.h"
 
 namespace nlml {
 namespace hx {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// f32 vector types, ACT_*, activate<ACT> and load_bias<NB, NFB>: encoder_heads_common.h
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 
 struct Args {
   const float* x;
@@ -31,13 +29,6 @@ struct Args {
   void* h3ws = nullptr;   // trunk-only launch (encoder_heads_f16x2_w8.hip, TRUNK = true): E2's output as MFMA operand fragments, read by
                           // the streamed tail (encoder_heads_f16x2_tailws.hip)
 };
-
-template <int ACT>
-__device__ __forceinline__ float activate(float v) {
-  if (ACT == ACT_RELU) return v < 0.0f ? 0.0f : v;   // NaN-propagating like torch.relu
-  if (ACT == ACT_TANH) return tanhf(v);
-  return v;
-}
 
 // (v0, v1) -> packed f16 pairs hi = f16(v), lo = f16(v - hi) in THREE instructions: v_cvt_pk_f16_f32, then one mixed-precision
 // fma per element (-hi * 1.0 + v evaluated in f32 -- exact -- and rounded once to f16 into the low / high half).  Bit-identical
@@ -88,25 +79,6 @@ __device__ __forceinline__ void frags_from_acc(const f32x16& acc, float inv, h8 
     swap_halves(lo[1], lo[3]);
     frag[p][0] = __builtin_bit_cast(h8, u4_{hi[0], hi[1], hi[2], hi[3]});
     frag[p][1] = __builtin_bit_cast(h8, u4_{lo[0], lo[1], lo[2], lo[3]});
-  }
-}
-
-template <int NB, int NFB>
-__device__ __forceinline__ void load_bias(f32x16 (&acc)[NB][NFB], const f32x4* __restrict__ b, int h) {
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const f32x4* p = b + (nb * 2 + h) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 v = p[q];
-#pragma unroll
-      for (int fb = 0; fb < NFB; ++fb) {
-        acc[nb][fb][4 * q + 0] = v[0];
-        acc[nb][fb][4 * q + 1] = v[1];
-        acc[nb][fb][4 * q + 2] = v[2];
-        acc[nb][fb][4 * q + 3] = v[3];
-      }
-    }
   }
 }
 

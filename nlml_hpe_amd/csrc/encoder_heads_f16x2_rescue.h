@@ -1,7 +1,7 @@
 // encoder_heads_f16x2_rescue.h -- the split-f16 kernels' slow path for faces whose activations leave f16's range.
 //
 // The f16 pieces of the split-f16 mode hold |v| < 65520.  A face with a larger activation anywhere in the network -- the
-// reference's own ipd == 0 -> 1e-6 branch (helpers/FeatureExtractor.py:47-48) makes features of ~1e6; un-normalised
+// reference's own ipd == 0 branch (helpers/FeatureExtractor.py:47-48) makes features of ~1e6; un-normalised
 // pixel coordinates do it too -- comes out of the MFMA path as NaN (hi = inf, lo = -inf), never as a wrong number.  The
 // reference (f32 ATen) returns a finite pose for such a face, so the tile that produced a non-finite pose re-evaluates
 // THAT face here: the same blob (weight = hi + lo pieces, the stage's power-of-two scale undone), the same stages and
@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nlml_hpe.h"
+#include "ipd_norm.h"
 #include "layout.h"
 
 namespace nlml {
@@ -29,12 +30,6 @@ struct RescueIn {
   int mode;                          // 0: LDS f32 vector; 1: global x row; 2: global raw landmarks, IPD-normalised on the fly
 };
 
-__device__ __forceinline__ double rescue_div(double n, double d, double y) {   // == IEEE n / d for these operands (K1)
-  const double q = n * y;
-  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
-  return fma(-r, y, q);
-}
-
 __device__ __forceinline__ void rescue_load8(const RescueIn& in, int g, int k0, float (&v)[8]) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -45,7 +40,7 @@ __device__ __forceinline__ void rescue_load8(const RescueIn& in, int g, int k0, 
       if (in.mode == 2) {
         const int ph = k % 3;
         const double rr = ph == 0 ? in.ref[g][0] : (ph == 1 ? in.ref[g][1] : in.ref[g][2]);
-        t = (float)rescue_div((double)t - rr, in.ipd[g], in.rcp[g]);
+        t = (float)div_ipd((double)t - rr, in.ipd[g], in.rcp[g]);
       }
     }
     v[e] = t;
@@ -129,13 +124,7 @@ __device__ __forceinline__ void rescue_tile(const float* __restrict__ x, int64_t
       const float* p = x + row[g] * ldx;
       in.base[g] = p;
       in.ipd[g] = 1.0; in.rcp[g] = 1.0; in.ref[g][0] = in.ref[g][1] = in.ref[g][2] = 0.0;
-      if (norm) {   // FeatureExtractor.py:30-66, exactly as K1 and the fused staging do it
-        const double dx = (double)p[99] - (double)p[789], dy = (double)p[100] - (double)p[790], dz = (double)p[101] - (double)p[791];
-        double ipd = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
-        if (ipd == 0.0) ipd = 1e-6;
-        in.ipd[g] = ipd; in.rcp[g] = 1.0 / ipd;
-        in.ref[g][0] = (double)p[3]; in.ref[g][1] = (double)p[4]; in.ref[g][2] = (double)p[5];
-      }
+      if (norm) ipd_setup(p, in.ipd[g], in.rcp[g], in.ref[g][0], in.ref[g][1], in.ref[g][2]);   // FeatureExtractor.py:30-66, as K1 does it
     }
     // trunk: E0 (x from global) .. E4, ping-pong through bufA / bufB
     for (int job = wv; job < 8; job += 4)

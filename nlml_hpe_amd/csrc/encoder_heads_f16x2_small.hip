@@ -22,31 +22,21 @@
 
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
+#include "ipd_norm.h"
 #include "encoder_heads_f16x2_dev.h"
 #include "layout.h"
 
 namespace nlml {
 namespace hxs {
 
-using hx::f32x16;
-using hx::f32x4;
 using hx::h4;
 using hx::h8;
-using hx::ACT_NONE;
-using hx::ACT_RELU;
-using hx::ACT_TANH;
 constexpr int STEP_UNITS = 2 * 2 * 64;   // h8 units per (tile, K step): 2 face blocks x 2 pieces x 64 lanes = 4 KiB
 
 __device__ __forceinline__ float activate(int act, float v) {
   if (act == ACT_RELU) return v < 0.0f ? 0.0f : v;
   if (act == ACT_TANH) return tanhf(v);
   return v;
-}
-
-__device__ __forceinline__ double div_ipd(double n, double d, double y) {
-  const double q = n * y;
-  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
-  return fma(-r, y, q);
 }
 
 // ---- pre-pass: x (f32 rows, or raw landmarks with optional IPD normalisation) -> hi/lo fragments of layer 0's input.
@@ -74,12 +64,10 @@ __global__ __launch_bounds__(256) void prepass_kernel(const float* __restrict__ 
   };
   if (VEC4) loadq(lane);   // before the reference points: in flight while the reciprocal is formed
   double ipd = 1.0, rcp = 1.0, ref0 = 0.0, ref1 = 0.0, ref2 = 0.0;
-  if (norm) {   // FeatureExtractor.py:30-66, exactly as K1 and the fused kernels do it
-    const double dx = (double)p[99] - (double)p[789], dy = (double)p[100] - (double)p[790], dz = (double)p[101] - (double)p[791];
-    ipd = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
-    if (ipd == 0.0) ipd = 1e-6;
-    rcp = 1.0 / ipd;
-    ref0 = (double)p[3]; ref1 = (double)p[4]; ref2 = (double)p[5];
+  if (norm) {   // FeatureExtractor.py:30-66, the arithmetic K1 and the fused kernels run: ipd_setup()'s pieces
+    ipd = ipd_length(p);
+    rcp = ipd_reciprocal(ipd);
+    ref0 = ipd_origin(p, 0); ref1 = ipd_origin(p, 1); ref2 = ipd_origin(p, 2);
   }
   unsigned nz = 0u;
   // Three chunks per lane and trip (layer 0 of the shipped encoder: 176 chunks = one trip): their 24 loads are issued together with the
@@ -519,7 +507,7 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
   for (int s = 0; s < 3; ++s) {
     LayerArgs a{};
     a.blob = blob; a.xin = in; a.xout = outb; a.B = B; a.stage = stages[s].stage; a.K16 = stages[s].K16;
-    a.nb_stage = stages[s].nb; a.jobs = stages[s].jobs; a.ntiles = ntiles; a.buf_steps = buf_steps; a.act = hx::ACT_RELU;
+    a.nb_stage = stages[s].nb; a.jobs = stages[s].jobs; a.ntiles = ntiles; a.buf_steps = buf_steps; a.act = ACT_RELU;
     // which K steps run on split accumulators, exactly as the fused kernel of the blob's mode (encoder_heads_f16x2.hip):
     //   NLML_MODE_F16X2S: all of layers 0, 1, 2, layer 1's small sums added at its K midpoint as well as at its end;
     //   NLML_MODE_F16X2:  layer 1 from its K midpoint on, layer 2; layer 0 never (kernel without the second set)

@@ -22,6 +22,7 @@
 
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
+#include "ipd_norm.h"
 #include "encoder_heads_f16x2_dev.h"
 #include "layout.h"
 
@@ -34,12 +35,6 @@
 
 namespace nlml {
 namespace hx {
-
-__device__ __forceinline__ double div_ipd_w8(double n, double d, double y) {   // == IEEE n / d for these operands (K1)
-  const double q = n * y;
-  const double r = fma(q, d, -n);   // the NEGATED residual: -0 / d stays -0 (normalize_ipd.hip)
-  return fma(-r, y, q);
-}
 
 // One K step of a layer-0 pass (two neuron blocks x two face blocks, split accumulators): step_fine's products in step_fine's order
 // -- (w_lo, x_hi) and (w_hi, x_lo) into accS, (w_hi, x_hi) into acc, one MFMA per slot -- with the x operands in registers of their
@@ -89,15 +84,9 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   const float* p = a.x + r * a.ldx;
   double ipd = 1.0, rcp = 1.0, ra = 0.0, rb = 0.0, rc = 0.0;
   if (NORM) {   // exactly K1's arithmetic: the f32 value the reference feeds the network, bit for bit
-    const double dx = (double)p[99] - (double)p[789], dy = (double)p[100] - (double)p[790], dz = (double)p[101] - (double)p[791];
-    ipd = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
-    if (ipd == 0.0) ipd = 1e-6;
-    rcp = 1.0 / ipd;
-    const double x0 = (double)p[3], y0 = (double)p[4], z0 = (double)p[5];
-    const int ph = scol % 3;   // coordinate of this thread's first column; a slab later the phase is + 32 % 3 = + 2
-    ra = ph == 0 ? x0 : (ph == 1 ? y0 : z0);
-    rb = ph == 0 ? y0 : (ph == 1 ? z0 : x0);
-    rc = ph == 0 ? z0 : (ph == 1 ? x0 : y0);
+    double x0, y0, z0;
+    ipd_setup(p, ipd, rcp, x0, y0, z0);
+    ipd_phase(scol % 3, x0, y0, z0, ra, rb, rc);   // coordinate of this thread's first column; a slab later the phase is + 32 % 3 = + 2
   }
   unsigned nzbits = 0u;
 
@@ -157,7 +146,7 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   auto lw_norm = [&](Set& st, int q) {   // element q (static): the plain chain (prologue)
     const int t = q % 3;
     const double rr = t == 0 ? ra : (t == 1 ? rb : rc);
-    st.v[q] = (float)div_ipd_w8((double)st.v[q] - rr, ipd, rcp);
+    st.v[q] = (float)div_ipd((double)st.v[q] - rr, ipd, rcp);
   };
   auto lw_rotate = [&]() {   // next slab: columns + 32 => phase + 2
     const double t0 = rc; rc = rb; rb = ra; ra = t0;

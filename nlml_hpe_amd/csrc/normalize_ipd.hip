@@ -2,8 +2,8 @@
 //
 // Replaces Read_Landmarks_and_Normalizing_using_IPD (helpers/FeatureExtractor.py:30-66) and the
 // f32 cast of its callers (:101): out = f32((f64(v) - f64(lm[1][c])) / ipd), with
-// ipd = ||lm[33] - lm[263]||_2 in f64 (np.linalg.norm == sqrt of an fma-chained dot on the
-// reference's BLAS; reproduced explicitly below), 1e-6 when exactly 0 (:47-48).
+// ipd = ||lm[33] - lm[263]||_2 in f64 and its ipd == 0 branch (:47-48): the arithmetic is ipd_norm.h's,
+// the one statement that the fused kernels' staging runs too, so K1 -> K2 and the fused paths are bit-identical.
 //
 // One wave per face: a face is 1404 f32 = 351 float4, read and written as fully coalesced
 // 16-B-per-lane accesses (6 wave-instructions each way).  Algorithmic bytes per face:
@@ -13,19 +13,9 @@
 
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
+#include "ipd_norm.h"
 
 namespace nlml {
-
-// n / d correctly rounded in f64 from y = RN(1/d) (Markstein): q = n*y, r = n - q*d exactly by fma,
-// q' = q + r*y.  Same routine as the fused kernel's staging (encoder_heads.hip), so K1 -> K2 and the fused
-// path are bit-identical; 3 multiply-adds per element instead of an IEEE division sequence.
-__device__ __forceinline__ double div_ipd(double n, double d, double y) {
-  const double q = n * y;
-  // the residual is taken NEGATED, r = -(n - q d), and subtracted: same value, same instructions, but a zero numerator keeps its
-  // sign -- fma(-q, d, n) is +0 for n = -0 and fma(+0, y, -0) = +0, where IEEE division gives -0 (tests/test_ipd_exact_gpu.py, family E)
-  const double r = fma(q, d, -n);
-  return fma(-r, y, q);
-}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -49,19 +39,15 @@ __global__ __launch_bounds__(256) void normalize_ipd_kernel(const float* __restr
     v[it] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + (i < F4 ? i : F4 - 1));
   }
   double rx = 0.0, ry = 0.0, rz = 0.0, ipd = 1.0;
-  if (normalize) {
-    rx = (double)p[3]; ry = (double)p[4]; rz = (double)p[5];                // nose tip, landmark 1
-    const double dx = (double)p[99] - (double)p[789];                        // landmark 33 - 263
-    const double dy = (double)p[100] - (double)p[790];
-    const double dz = (double)p[101] - (double)p[791];
-    ipd = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
-    if (ipd == 0.0) ipd = 1e-6;
+  if (normalize) {   // ipd_setup()'s pieces, the reciprocal behind the branch
+    rx = ipd_origin(p, 0); ry = ipd_origin(p, 1); rz = ipd_origin(p, 2);   // nose tip
+    ipd = ipd_length(p);
   }
-  const double rcp = 1.0 / ipd;
+  const double rcp = ipd_reciprocal(ipd);
   // element e of float4 i is column 4i+e, coordinate (4i+e) % 3; i = 64*it + lane and 256 % 3 == 1, so the phase
   // of a lane advances by one per iteration: rotate (a, b, c) instead of taking a modulo per element
-  const int ph = (4 * lane) % 3;
-  double a = ph == 0 ? rx : (ph == 1 ? ry : rz), b = ph == 0 ? ry : (ph == 1 ? rz : rx), c = ph == 0 ? rz : (ph == 1 ? rx : ry);
+  double a, b, c;
+  ipd_phase((4 * lane) % 3, rx, ry, rz, a, b, c);
   unsigned nzbits = 0u;
 #pragma unroll
   for (int it = 0; it < 6; ++it) {

@@ -22,7 +22,12 @@ arithmetic, so a variant that errs by less than the element's distance from its 
 sees, and a copy of the prologue meets 3 (a column of one family) to 8,370 (all of them) such elements.
 READ-OUT CERTIFICATE: ipd_cases.readout_net through the C oracle's f32 chain (order 2, the f32 kernel's) returns the engineered x itself
 (shift 60) and moves with a one-ulp nudge of x on at least half of the probe family's engineered elements (shift 60: all; shift 0, the
-live Tanh: measured below)."""
+live Tanh: measured below).
+THE SHIPPED STATEMENT: nlml_hpe_amd/csrc/ipd_norm.h -- the header every kernel compiles: reciprocal, two fma corrections, negated
+residual -- built for the host (tests/native/ipd_norm_host.cpp) gives the reference's bits and ipds on every family, the comparison the
+GPU test makes of K1; with the residual the way it stood before the sign fix it does not, on family E."""
+import os
+import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -71,8 +76,38 @@ def test_three_host_statements_agree(name):
           f"{int(np.isinf(ref).sum())} infinite and {int(((_bits(ref) & 0x7F800000) == 0).sum() - (ref == 0).sum())} subnormal results")
 
 
+def _ipd_norm_host(repo_root, tmp_path, raw, *defines):
+    """(normalised f32[B,1404], ipd f64[B]) from a host build of the shipped header."""
+    exe = tmp_path / "ipd_norm_host"
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", *defines, "-o", str(exe),
+                    os.path.join(repo_root, "tests", "native", "ipd_norm_host.cpp")], check=True, capture_output=True, text=True)
+    raw = np.ascontiguousarray(raw, np.float32).reshape(len(raw), -1)
+    raw.tofile(tmp_path / "raw.f32")
+    subprocess.run([str(exe), str(tmp_path / "raw.f32"), str(tmp_path / "out.f32"), str(tmp_path / "ipd.f64")], check=True)
+    return np.fromfile(tmp_path / "out.f32", np.float32).reshape(raw.shape), np.fromfile(tmp_path / "ipd.f64", np.float64)
+
+
+@pytest.mark.parametrize("name", FAMILIES)
+def test_shipped_header_on_the_host(name, repo_root, tmp_path):
+    fam = IC.family(name)
+    out, ipd = _ipd_norm_host(repo_root, tmp_path, fam["raw"])
+    ref, _ = IC.reference(name)
+    assert out.shape == ref.shape and np.array_equal(_bits(out), _bits(ref))
+    assert np.array_equal(ipd, fam["ipd"])
+
+
+def test_old_residual_fails_on_the_signs_family(repo_root, tmp_path):
+    """fma(-q, d, n) / fma(r, y, q) turns -0.0 / ipd into +0.0: family E shows it."""
+    fam = IC.family("E")
+    out, ipd = _ipd_norm_host(repo_root, tmp_path, fam["raw"], "-DIPD_NORM_OLD_RESIDUAL")
+    ref, _ = IC.reference("E")
+    assert np.array_equal(ipd, fam["ipd"])
+    differ = _bits(out) != _bits(ref)
+    assert differ.any() and (_bits(ref)[differ] == 0x80000000).all() and not (_bits(out)[differ] != 0).any()
+    print(f"old residual: {int(differ.sum())} elements of family E come out +0.0 where the reference has -0.0")
+
+
 def test_fx1_agrees_with_the_rational_reference(golden_dir):
-    import os
     g = np.load(os.path.join(golden_dir, "fx1_normalise.npz"))
     raw = g["landmarks"]
     fam = {"raw": raw, "ipd_q": [IC.ref_ipd(f[IC.EYE_L], f[IC.EYE_R]) for f in raw]}
