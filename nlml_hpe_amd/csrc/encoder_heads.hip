@@ -519,9 +519,6 @@ __device__ __forceinline__ void stage_e0_pass(const Ctx& c, const EncArgs& a, E0
                                          : *reinterpret_cast<const f32x4*>(xnext + fb * (32 * S_XS));
           },
           [&](int j) {   // (kk, j) are static: slab s+2's staging, one piece per gap
-#ifdef EXP_NO_STAGE
-            return;
-#endif
             if (kk == 0 && j == 2) gload(s + 3, ld);          // its own gap: address arithmetic + 2 loads
             if (kk == 1 && j == 0) lw_begin(wrset);
             if (NORM && kk == 1) lw_norm(wrset, 0, j);
@@ -531,9 +528,7 @@ __device__ __forceinline__ void stage_e0_pass(const Ctx& c, const EncArgs& a, E0
             if (kk == 3 && j == 2) lw_store(o_wr, wrset);
           });
     }
-#ifndef EXP_NO_BAR
     __syncthreads();
-#endif
   };
   // nslab is even (pack.cpp pads K to whole PAIRS of slabs): the two register sets alternate statically
   int o0 = 0, o1 = SLAB, o2 = 2 * SLAB;   // buffers of slabs s, s+1, s+2

@@ -50,16 +50,12 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
   }
   unsigned nzbits = 0u;
 
-  // ONE L2 request per 128-byte line of x (the strict-fast kernel's scheme, encoder_heads_f16x2_w8.hip): a row is 16-byte but not
+  // ONE L2 request per 128-byte line of x (+0.8 % here; the strict-fast kernel lacks the registers, DESIGN_APPENDIX.md A.10): a row is 16-byte but not
   // 128-byte aligned, so the 256 bytes it contributes to a slab touch three lines and the one shared with the next slab used to be
   // requested twice, a slab apart.  The 16-byte units that lie in a slab's FIRST line (`adv[i]`) are loaded one slab ahead -- one load
   // instruction then asks for whole lines only -- and wait one slab in `carry`.  Same values into the same LDS bytes.
-#ifdef BF8_NO_XLINE
-  const bool adv[2] = {false, false};
-#else
   const int xphase = (int)((reinterpret_cast<uintptr_t>(p) >> 4) & 7);   // the row's first 16-byte unit within its line
   const bool adv[2] = {VEC4 && xphase != 0 && xphase + 2 * (tid & 7) < 8, VEC4 && xphase != 0 && xphase + 2 * (tid & 7) + 1 < 8};
-#endif
   f32x4 set[2];   // ONE staging register set (8 floats per thread), refilled as soon as it has been written to LDS
   f32x4 carry[2];
   auto gload_at = [&](int s0, f32x4 (&dst)[2], bool ahead) {
@@ -83,7 +79,6 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
     if (piece == 0) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(set[i]));
-#ifndef BF8_NO_XLINE
       if (VEC4) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {   // a unit that is loaded a slab ahead stages what it loaded a slab ago
@@ -93,7 +88,6 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
           carry[i] = t;
         }
       }
-#endif
     }
     if (piece < 8) {
       if (NORM) {
@@ -135,9 +129,7 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
   bf16x8 wr[R0][NB];
   // prologue: slabs 0 and 1 in LDS, slab 2 in the registers; the ring and the bias are requested LAST (so that at the loop's entry no
   // load is younger than the loop's own steady state: hipcc merges the two entries' pending-load states conservatively)
-#ifndef BF8_NO_XLINE
   if (VEC4) gload_at(0, carry, false);   // slab 0 for the units that run a slab ahead
-#endif
   gload(0);
   lwrite(0, true);
   gload(1);

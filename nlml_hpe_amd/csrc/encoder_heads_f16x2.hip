@@ -205,20 +205,12 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
                                                  : *reinterpret_cast<const h8*>(xnext + pp * P_XS + fb * FB);
                 },
                 [&](int m) {   // slab s+2's staging in the free (odd) slots of the slab's four half-steps
-#ifdef HX_ABL_NOSTAGE
-                  return;      // timing-only ablation (wrong results)
-#endif
                   if ((m & 1) == 0) return;
                   const int j = 12 * slot + (m >> 1);          // free slot 0..47 of this slab
                   // 48 free slots per slab: 24 normalisation links (4 pairs x 6), rotate, 4 splits, 2 LDS stores, 2 reloads
                   if (j == 0) lw_begin(set[PAR]);
-#ifdef HX_NORM_CHAIN   // the first form, kept for A/B timing: one whole element per slot
-                  if (NORM && j >= 2 && j < 18 && (j & 1) == 0) lw_norm(set[PAR], (j - 2) >> 1);
-                  if (NORM && j == 18) lw_rotate();
-#else
                   if (NORM && j < 24) lw_norm2(set[PAR], j / 6, j % 6);
                   if (NORM && j == 24) lw_rotate();
-#endif
                   if (j >= 26 && j < 34 && (j & 1) == 0) lw_split(set[PAR], (j - 26) >> 1, real);
                   if (j == 34) lw_store(o2, 0);
                   if (j == 36) lw_store(o2, 1);
@@ -227,9 +219,7 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
                 });
       }
     }
-#ifndef HX_ABL_NOBAR
     __syncthreads();
-#endif
     const int t0 = o0;   // rotate: (o0, o1, o2) <- (o1, o2, o0)
     o0 = o1; o1 = o2; o2 = t0;
   };

@@ -35,15 +35,6 @@ struct Args {
 // to the plain C form (five conversions, two subtractions, a pack) on 4 M values incl. subnormal, overflowing and non-finite ones
 // (tools/probes/split_probe.hip); the epilogues run on the vector ALU with the matrix pipe idle, so their length is wall time.
 __device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo) {
-#ifdef HX_SPLIT_C
-  typedef _Float16 h2_ __attribute__((ext_vector_type(2)));
-  asm volatile("" : "+v"(v0), "+v"(v1));
-  h2_ a, b;
-  a[0] = (_Float16)v0; a[1] = (_Float16)v1;
-  b[0] = (_Float16)(v0 - (float)a[0]); b[1] = (_Float16)(v1 - (float)a[1]);
-  hi = __builtin_bit_cast(unsigned, a); lo = __builtin_bit_cast(unsigned, b);
-  return;
-#endif
   asm volatile("v_cvt_pk_f16_f32 %0, %2, %3\n\t"
                "v_fma_mixlo_f16 %1, -%0, 1.0, %2 op_sel_hi:[1,0,0]\n\t"
                "v_fma_mixhi_f16 %1, -%0, 1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
@@ -281,11 +272,9 @@ __device__ __forceinline__ void gloop_run(f32x16 (&acc)[NJ][NB][1], h8 (&wr)[4][
 
 // accumulators * inv -> activation -> hi/lo f16 -> LDS image [piece][face][neuron].  `out`: the lane's hi-plane address of
 // (its face row, the job's first column); columns at or beyond MAXCOL are not written (latent image).
-// A lane holds rows 8q + 4h .. + 3 (q < 4) of its face column: 8-byte pieces, and as ds_write_b64 they were 2-way bank
-// conflicted (26 % of all LDS cycles, profiles/r01_pmc_summary.md).  Register q = 2p of the upper half-wave is exchanged with
-// register q = 2p + 1 of the lower one, after which lanes 0-31 hold rows 16p .. 16p+7 and lanes 32-63 rows 16p+8 .. 16p+15:
-// one conflict-free 16-byte store per plane (row strides are 4 mod 32 dwords: the 8 lanes of a ds_write_b128 group tile all
-// 32 banks).  `hook(i)` runs after group i of NB * NFB * 2 groups: the NEXT stage's global fetches are dropped in there one or
+// A lane holds rows 8q + 4h .. + 3 (q < 4) of its face column: 8-byte pieces, written as ds_write_b64 (2-way bank conflicted).
+// (Conflict-free 16-byte stores after a half-wave exchange lost to them, 5.2 k against 4.7 k cycles: DESIGN_APPENDIX.md A.3, A.10.)
+// `hook(i)` runs after group i of NB * NFB * 2 groups: the NEXT stage's global fetches are dropped in there one or
 // two at a time, because a 1-KiB load costs ~64 cycles of issue when all four waves of the CU are fetching (the CU takes in
 // 64 B/clk) and the epilogue's ~130 VALU cycles per group hide it.
 struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
@@ -307,7 +296,6 @@ __device__ __forceinline__ void store_lds(const f32x16 (&acc)[NB][NFB], char* ou
           unsigned hi[4], lo[4];      // [0,1] = register q = 2p (rows 4h .. +3), [2,3] = register q = 2p + 1 (rows 8 + 4h .. +3)
 #pragma unroll
           for (int j = 0; j < 4; ++j) split2(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-#ifndef HX_STORE_B128
           typedef unsigned u2 __attribute__((ext_vector_type(2)));
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq) {
@@ -318,19 +306,6 @@ __device__ __forceinline__ void store_lds(const f32x16 (&acc)[NB][NFB], char* ou
               *reinterpret_cast<u2*>(d + plane) = u2{lo[2 * qq], lo[2 * qq + 1]};
             }
           }
-#else
-          swap_halves(hi[0], hi[2]);
-          swap_halves(hi[1], hi[3]);
-          swap_halves(lo[0], lo[2]);
-          swap_halves(lo[1], lo[3]);
-          const int col = 32 * nb + 16 * p + 8 * h;
-          if (MAXCOL >= 32 * NB || col < MAXCOL) {
-            char* d = out + fb * fb_stride + col * 2;
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<u4*>(d) = u4{hi[0], hi[1], hi[2], hi[3]};
-            *reinterpret_cast<u4*>(d + plane) = u4{lo[0], lo[1], lo[2], lo[3]};
-          }
-#endif
         }
         if constexpr (!std::is_same<Hook, NoHook>::value) {   // pin the fetches between the groups; without a hook the
           __builtin_amdgcn_sched_barrier(0);                 // scheduler is free to overlap the groups' dependency chains

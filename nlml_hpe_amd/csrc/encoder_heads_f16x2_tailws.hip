@@ -45,11 +45,7 @@ namespace nlml {
 namespace hx {
 
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
-#ifdef TW_NO_PRIO
-#define TW_PRIO(p) do { } while (0)
-#else
 #define TW_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#endif
 typedef __attribute__((address_space(3))) const char LdsC;
 typedef __attribute__((address_space(3))) char LdsW;
 

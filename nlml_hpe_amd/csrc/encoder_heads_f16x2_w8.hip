@@ -13,11 +13,9 @@
 //   * two waves per SIMD hide each other's dependent chains: the x staging (f64 normalisation, hi/lo split, LDS writes) and the
 //     epilogues of one wave run under the other's MFMAs without hand-placing every link.
 // The tail (E3, E4, E5, the three heads; 10 % of the FLOPs, stream-bound short stages) is the four-wave code of
-// encoder_heads_f16x2_dev.h run by waves 0-3.  Round 4 let waves 4-7 END after layer 2's store (S_BARRIER waits only for the waves of
-// the workgroup that have not terminated: gfx9 ISA, not the HIP programming model); since round 5 they STAY and take blocks 4..7 of every
-// head's H1 stage (tail_helper_w8: the same number of barriers as the main path), so nothing relies on that rule any more.  The gain is
-// small -- 0.918 against 0.921 ms per 65,536 faces, same box, five alternating runs: H1 is bound by its weight stream, not by its
-// MFMAs -- and the bits are unchanged (-DW8_TAIL_EXIT builds round 4's form for A/B).
+// encoder_heads_f16x2_dev.h run by waves 0-3.  Waves 4-7 STAY after layer 2's store and take blocks 4..7 of every head's H1 stage
+// (tail_helper_w8: the same number of barriers as the main path), so every wave of the workgroup passes every barrier, as the HIP
+// programming model asks.  (Round 4 let them end there instead; that form and its measurement: DESIGN_APPENDIX.md A.10.)
 #include <hip/hip_runtime.h>
 
 #include "../../include/nlml_hpe.h"
@@ -25,13 +23,6 @@
 #include "ipd_norm.h"
 #include "encoder_heads_f16x2_dev.h"
 #include "layout.h"
-
-// -DW8_TAIL_EXIT (round 4's form, A/B only): waves 4-7 of a workgroup end while waves 0-3 go on through barriers.  That is defined by
-// the gfx9 ISA's S_BARRIER (terminated waves are not waited for), not by the HIP programming model -- so that form builds for the
-// targets where the rule was read and tested, and nowhere else (an architecture with split or named barriers would hang instead of failing).
-#if defined(W8_TAIL_EXIT) && defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
-#error "-DW8_TAIL_EXIT relies on S_BARRIER ignoring terminated waves (gfx942 / gfx950)"
-#endif
 
 namespace nlml {
 namespace hx {
@@ -90,37 +81,15 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   }
   unsigned nzbits = 0u;
 
-  // ONE L2 request per 128-byte line of x -- built, bit-identical, measured SLOWER here, kept behind -DW8_XLINE.  A row is 16-byte but not
-  // 128-byte aligned (1,404 floats = 43.9 lines), so the 128 bytes a row contributes to a slab straddle two lines, and the line between
-  // slabs q and q+1 is requested twice, a slab apart (by then the weight stream -- 64 KB per slab -- has pushed it out of the 32-KB L1):
-  // 88 requests per row and pass for 45 lines, 6 % of all the kernel's L2 requests (profiles/r05l1_summary.md).  With -DW8_XLINE the
-  // threads whose 16 bytes lie in a slab's FIRST line (`adv`) load one slab ahead: one load instruction then asks, per row, for exactly
-  // one whole line, and an `adv` thread's value waits one slab in `carry`.  Same values into the same LDS bytes.  Measured on one box,
-  // alternating: 0.880 against 0.844 ms with the weight ring three steps ahead (the four carry registers push the spills from 30 to 52),
-  // 0.834 against 0.826 ms with the ring two steps ahead (21 against 15 spills): the saved requests do not pay for the registers.  The
-  // bf16 kernel, which has the registers, keeps the scheme (+0.8 %).
-#ifndef W8_XLINE
-  const bool adv = false;
-#else
-  const int xphase = (int)((reinterpret_cast<uintptr_t>(p) >> 4) & 7);   // the row's first 16-byte unit within its line
-  const bool adv = VEC4 && xphase != 0 && xphase + (tid & 7) < 8;
-#endif
-
+  // (One L2 request per 128-byte line of x, the bf16 kernel's scheme, was built here too, bit-identical, and measured slower: the saved
+  // requests do not pay for its four carry registers.  Record: DESIGN_APPENDIX.md A.10.)
   struct Set { float v[4]; };
-  [[maybe_unused]] Set carry;
-  auto gload_at = [&](int s, Set& st) {   // columns scol .. scol+3 of slab s
+  auto gload = [&](int s, Set& st) {   // columns scol .. scol+3 of slab s
     s = s < nslab ? s : nslab - 1;
-#ifdef W8_ABL_XHOT   // timing-only ablation (wrong results): every slab's x comes from the row's first 128 bytes (L1 / L2 hot)
-    s = 0;
-#endif
     const int k = s * XS_COLS + scol;
     if (VEC4) {
       const int kc = k < F ? k : (NORM ? k - 12 * ((k - F + 15) / 12) : F - 4);   // phase-preserving clamp (zero weights there)
-#ifdef W8_X_NT   // x lines are used once per pass: ask L2 not to keep them in the weights' way (experiment)
-      const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + kc));
-#else
       const f32x4 t = *reinterpret_cast<const f32x4*>(p + kc);
-#endif
 #pragma unroll
       for (int e = 0; e < 4; ++e) st.v[e] = t[e];
     } else {
@@ -128,20 +97,9 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
       for (int e = 0; e < 4; ++e) st.v[e] = p[k + e < F ? k + e : F - 1];
     }
   };
-  auto gload = [&](int s, Set& st) { gload_at(s + (adv ? 1 : 0), st); };   // (slab s+1 in the threads that run a slab ahead)
   auto lw_begin = [&](Set& st) {   // the set's loads must have landed: everything below consumes them
 #pragma unroll
     for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(st.v[e]));
-#ifdef W8_XLINE
-    if (VEC4) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {   // a thread that loads a slab ahead stages what it loaded a slab ago
-        const float t = st.v[e];
-        st.v[e] = adv ? carry.v[e] : t;
-        carry.v[e] = t;
-      }
-    }
-#endif
   };
   auto lw_norm = [&](Set& st, int q) {   // element q (static): the plain chain (prologue)
     const int t = q % 3;
@@ -165,7 +123,7 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   // the h1 / h2 images reach into that range are never live together with a slab (barriers on both sides of every layer-0 pass).
   // The slabs form TWO buffers of 64 columns: an iteration of the main loop reads one (four K steps) while the other is being
   // written for the next iteration -- ONE barrier per four K steps instead of per two (the slab barrier cost 14-16 k of a pass's
-  // 96-109 k cycles: every wave waits for the slowest of eight each time; -DW8_ABL_NOBAR stamps).
+  // 96-109 k cycles: every wave waits for the slowest of eight each time; measured with a build without the barrier).
   constexpr int XW_PLANE = 64 * 64, XW_SLAB = 2 * XW_PLANE, XW_BUF = 2 * XW_SLAB, O_XW = LDS_BYTES - 2 * XW_BUF;
   static_assert(O_XW >= 16 * 512 * 16, "slabs behind the parked accumulators");
   const int wr_off = srow * 64 + ((((tid & 7) >> 1) ^ ((srow >> 2) & 3)) << 4) + 8 * (tid & 1);   // this thread's 8 bytes of a plane
@@ -191,13 +149,7 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   load_bias<NB, NFB>(acc, c.blob4 + c.hdr.b_off(ST_E0) + job * (4 * 8) + (2 * nbh) * 8, c.h);
   zero_acc<NB, NFB>(accS);
   const h8* w = c.blob8 + c.hdr.w_off(ST_E0) + (size_t)job * c.hdr.job_w16(ST_E0) + (2 * nbh * 2) * 64 + c.lane;
-#ifdef W8_ABL_WHOT   // timing-only ablation (wrong results): every K step reads the weights of steps 0..3 -- always L2-resident, all CUs the same lines
-  auto wfrag = [&](int ks) { return w + (size_t)(ks & 3) * WSTEP; };
-#elif defined(W8_ABL_WL2)   // timing-only ablation (wrong results): a small L2-resident region per CU (no shared hot lines)
-  auto wfrag = [&](int ks) { return w + (size_t)((ks & 3) + 4 * (blockIdx.x % 20)) * WSTEP; };
-#else
   auto wfrag = [&](int ks) { return w + (size_t)ks * WSTEP; };   // K step ks of this wave's two blocks
-#endif
 
   // TWO staging register sets (4 floats per thread each), slab q in set[q & 1]: a slab's global loads are issued one iteration (four K
   // steps) before it is written to LDS.  In pass 0 x comes from HBM, and a load that has not returned holds back every weight load
@@ -214,9 +166,6 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   // weight ring: K step ks in slot ks % 4 = its step within the iteration, its hi / lo pieces requested DH / DL steps ahead
   constexpr int R0 = 4, DH = W8_D0_HI, DL = W8_D0_LO;
   h8 wr[R0][NB][2];
-#ifdef W8_XLINE
-  if (VEC4) gload_at(0, carry);   // slab 0 for the threads that run a slab ahead (their first regular load is slab 1's)
-#endif
   gload(0, set[0]);
   gload(1, set[1]);
   lwrite(0, set[0], true);
@@ -248,26 +197,8 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
     xh[0][fb] = xread(xb0, 0, fb, 0);
     xl[fb] = xread(xb0, 0, fb, 1);
   }
-#ifdef W8_XTOUCH
-  // EXPERIMENT (-DW8_XTOUCH; bit-identical, measured 2.8 % SLOWER: 0.890 against 0.866 ms on one box): x lines pulled into L2 through the
-  // SCALAR cache, two iterations before the vector loads ask for them.  Why it loses: scalar loads count in lgkmcnt with the LDS reads, so
-  // every `s_waitcnt lgkmcnt(k)` for an x operand of the next MFMAs also waits until all but k of the 16 touches -- each 300-500 cycles
-  // away -- have come back.  The idea as it was:  A vector load of
-  // a line that is still in HBM (pass A) or the Infinity Cache (pass B) sits 300-500 cycles at the head of the L1's in-order return queue
-  // with every younger weight line behind it (-DW8_ABL_XHOT: 23 k cycles per tile); a touch through the vector path costs the same.
-  // s_load_dword goes CU -> scalar cache -> L2 on a path of its own.  One touch per row and slab: the slab's last dword, i.e. the line
-  // it shares with the next slab.  The destination register is never read; it is kept live (`+s`) across the iteration's barrier, whose
-  // lgkmcnt(0) all touches have passed before the next ones are issued.
-  unsigned xt_sink = 0;
-  auto xtouch = [&](int k, int slab0) {   // touch k of 16: row k & 7 of this wave's eight rows, slab slab0 + (k >> 3)
-    int64_t rr = row0 + 8 * c.wv + (k & 7);
-    rr = rr < a.B ? rr : a.B - 1;
-    int col = (slab0 + (k >> 3)) * XS_COLS + XS_COLS - 1;
-    col = col < F ? col : F - 1;
-    const float* q = a.x + rr * a.ldx + col;
-    asm volatile("s_load_dword %0, %1, 0x0" : "+s"(xt_sink) : "s"(q) : "memory");
-  };
-#endif
+  // (x lines touched through the scalar cache two iterations ahead of the vector loads: bit-identical, 2.8 % slower -- scalar loads share
+  // lgkmcnt with the LDS reads.  Record: DESIGN_APPENDIX.md A.10.)
   int cur = 0, nxt = XW_BUF;   // byte offsets of the buffer being read / written
   for (int it = 0; it < niter; ++it) {
     const int s = 2 * it;
@@ -281,25 +212,11 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
       // step 0, slab s+3 during step 1) and the buffer being read has been read to its end (step 3's operands were fetched during
       // step 2) -- so step 3 fetches the next iteration's first operands from the new buffer under its own MFMAs, and the next
       // iteration may overwrite the old one from its first slot on.
-#ifndef W8_ABL_NOBAR
       if (t == 3) __syncthreads();
-#endif
-#ifdef W8_XTOUCH
-      if (t == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(xt_sink));   // (free behind the barrier: the last iteration's touches have landed)
-#endif
       step_w8(acc, accS, wr[t], xh[t & 1], xl, wr[(t + DH) % R0], wfrag(ks + DH), wr[(t + DL) % R0], wfrag(ks + DL),
               [&](int fb) { xh[(t + 1) & 1][fb] = t < 3 ? xread(xc[(t + 1) & 1], t + 1, fb, 0) : xread(xn, 0, fb, 0); },
               [&](int fb) { xl[fb] = t < 3 ? xread(xc[(t + 1) & 1], t + 1, fb, 1) : xread(xn, 0, fb, 1); },
               [&](int m) {   // the staging of slab s+2 (step 0) and s+3 (step 1), one piece behind an MFMA
-#ifdef W8_ABL_NOSTAGE
-                return;      // timing-only ablation (wrong results)
-#endif
-#ifdef W8_XTOUCH
-                if (t == 3) {   // slabs s+6 and s+7: their vector loads are issued in the next iteration
-                  if (m < 4) { xtouch(2 * m, s + 6); xtouch(2 * m + 1, s + 6); }
-                  else xtouch(4 + m, s + 6);
-                }
-#endif
                 if (t >= 2) return;
                 Set& st = set[t & 1];
                 const int j = m;
@@ -318,9 +235,6 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
     }
     const int t0 = cur; cur = nxt; nxt = t0;
   }
-#ifdef W8_XTOUCH
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(xt_sink));
-#endif
   if (pass == 0 && a.valid) {  // all-zero feature row == "no face" (FeatureExtractor.py:105-106); 8 lanes share a row
     const unsigned long long m = __ballot(nzbits != 0u);
     if ((tid & 7) == 0 && live) a.valid[row0 + srow] = ((m >> (c.lane & 56)) & 0xFFull) ? 1 : 0;
@@ -427,7 +341,7 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
   W8S(9);
   // E2: 512 -> 256, ReLU, split accumulators; job jw's block nbh.  h3 overwrites h2 => barrier between the K loop and the store
   Ctx ct = c;
-  ct.wv = c.wv & 3;                                       // the tail's wave index (waves 4-7 only fetch with it, then end)
+  ct.wv = c.wv & 3;                                       // the tail's wave index (waves 4-7 fetch with it, then help in H1)
   f32x16 acc3[1][2];
   h8 wr3[ring_slots(1, 2)][1][2];
   {
@@ -461,13 +375,9 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
   __syncthreads();
   W8S(11);
   W8S_WALL(15);
-#ifdef W8_TAIL_EXIT   // round 4's form (A/B): waves 4-7 end here; the tail's barriers wait only for the surviving waves (see the header)
-  if (c.wv >= 4) return;
-  constexpr bool H1W8 = false;
-#else                  // round 5: waves 4-7 stay for the heads' H1 stage (blocks 4..7 of each head's eight), tail_helper_w8
+  // waves 4-7 stay for the heads' H1 stage (blocks 4..7 of each head's eight), tail_helper_w8
   ct.helper = c.wv >= 4 ? 1 : 0;
   constexpr bool H1W8 = true;
-#endif
   // (Measured and dropped: on their way out these waves TOUCHED the input rows of the tile that starts one tile time later -- one dword
   // per line, so that its pass 0 finds x in the Infinity Cache instead of HBM: 0.852 ms against 0.834 without, same box.)
 #ifdef HX_STAMPS

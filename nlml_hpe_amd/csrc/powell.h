@@ -337,13 +337,11 @@ NLML_HD bool powell_step(S& s, double fin) {
     }                                                                         \
   } while (0)
 
-#ifndef NLML_POWELL_NO_FAST_PATH
   if (s.ls_pc == 10 && (s.pc == 2 || s.pc == 4) && brent_resume_fast(s, fin, s.xtol * 100)) {
     if (s.nfev >= s.maxfun) { s.status = PW_MAXFEV; s.pc = -1; return false; }   // as PW_LINESEARCH does after a suspension
     s.nfev += 1;
     return true;
   }
-#endif
   switch (s.pc) {
     case 0:
       for (int k = 0; k < N; ++k) s.xeval[k] = s.x[k];

@@ -180,8 +180,8 @@ __device__ __forceinline__ void tucker_xhat(TuckerShared& sh, const float* __res
 // for 16, and either way a round cannot be shorter than streaming Wm (758 KB) through one CU.
 //   x_hat[m]  the same q-ascending fma chain from +0.0 that one MFMA output accumulates (the padded q = 135
 //             step adds 0 * w and is skipped);
-//   columns   lane L of wave w takes the three consecutive columns tcol0(w) + 3L .. + 2 (lanes 0..58): one 12-byte load per
-//             row, 704 contiguous bytes per wave -- a third of the load instructions of the one-dword-per-block form;
+//   columns   lane L of wave w takes the four consecutive columns tcol0(w) + 4L .. + 3 (lanes 0..43): one 16-byte load per
+//             row, 704 contiguous bytes per wave -- a quarter of the load instructions of the one-dword-per-block form;
 //   residual  the differences go through `few` (LDS) so that lane c < 16 can square-and-sum the eleven columns
 //             tcol0(w) + tlcol(c, mb), mb ascending, exactly as the MFMA path's lane c does, then the same xor butterfly.
 struct TuckerFewShared {
@@ -191,17 +191,14 @@ struct TuckerFewShared {
 #ifndef K3_TRING4
 #define K3_TRING4 3          // ring depth of the 4x4x4 pass (tucker_mfma4)
 #endif
-#ifndef K3_FEW_CPL
-#define K3_FEW_CPL 4
-#endif
 template <int NE>
 __device__ __attribute__((noinline)) void tucker_few(TuckerShared& sh, TuckerFewShared& few, const float* __restrict__ Wm,
                                                      const float* (&xe)[NE], const int (&ev)[NE], int tid) {
   const int lane = tid & 63, wv = tid >> 6;
-  // CPL consecutive columns per lane: with 4, lanes 0..43 own columns 4L .. 4L+3 and every load is an ALIGNED 16-byte load (rows
-  // are 5,616 B = 351 x 16, the wave bases 704 w and 4,912 B too); with 3, lanes 0..58 and 12-byte loads at 12-byte strides.
-  constexpr int CPL = K3_FEW_CPL;
-  static_assert(TWC % CPL == 0 || CPL == 3, "columns per lane");
+  // CPL consecutive columns per lane: lanes 0..43 own columns 4L .. 4L+3 and every load is an ALIGNED 16-byte load (rows
+  // are 5,616 B = 351 x 16, the wave bases 704 w and 4,912 B too).  (Three columns and 12-byte loads: DESIGN_APPENDIX.md A.10.)
+  constexpr int CPL = 4;
+  static_assert(TWC % CPL == 0, "columns per lane");
   const int c0 = CPL * lane < TWC - CPL ? CPL * lane : TWC - CPL;   // lanes beyond the last owner repeat its loads
   const int own0 = CPL * lane < TWC ? CPL * lane : TWC;              // first column this lane writes
   const float* wb = Wm + tcol0(wv) + c0;
@@ -218,13 +215,8 @@ __device__ __attribute__((noinline)) void tucker_few(TuckerShared& sh, TuckerFew
   static_assert(TQ % QB == 0, "135 = 9 x 15 = 5 x 27 = 3 x 45");
   float w[2][QB][CPL];
   auto loadc = [&](int q, float (&dst)[CPL]) {
-    if constexpr (CPL == 4) {
-      const f32x4_t t = gload<f32x4_t>(wb + (size_t)q * TM);
-      dst[0] = t[0]; dst[1] = t[1]; dst[2] = t[2]; dst[3] = t[3];
-    } else {
-      const f32x3_t t = gload<f32x3_t>(wb + (size_t)q * TM);
-      dst[0] = t[0]; dst[1] = t[1]; dst[2] = t[2];
-    }
+    const f32x4_t t = gload<f32x4_t>(wb + (size_t)q * TM);
+    dst[0] = t[0]; dst[1] = t[1]; dst[2] = t[2]; dst[3] = t[3];
   };
 #pragma unroll
   for (int qq = 0; qq < QB; ++qq) loadc(qq, w[0][qq]);

@@ -34,6 +34,7 @@ __device__ __attribute__((noinline)) bool powell_step_call(LdsPowellState* s, do
 #define PW_FEW_N 4
 #endif
 constexpr int PW_FEW = PW_FEW_N;
+static_assert(PW_FEW >= 1 && PW_FEW <= 4, "the few-machine passes take one to four evaluations");
 
 // A round with many live machines: all 16 evaluations on the 16x16x4 matrix cores, exactly K3's body.  Not inlined, like the
 // few-machine passes: its 150 registers are then allocated on their own instead of across the state-machine code (inlined, the
@@ -164,11 +165,11 @@ __global__ __launch_bounds__(ORDER == NLML_TD_ORDER_REFERENCE ? TR_NT : TNT, ORD
     PWS(0);
     tucker_coef(sh, lp, cp4, tid);
     PWS(1);
-    if (PW_FEW > 0 && __popc(live_mask) <= PW_FEW) {
+    if (__popc(live_mask) <= PW_FEW) {
       // the tail of a workgroup's run: one to a few machines left (a face that needs 6,000 evaluations next to fifteen
       // that needed 1,500).  Their evaluations share ONE pass over Wm on the vector ALUs, bit-identical to the MFMA pass.
-      int ev[PW_FEW > 0 ? PW_FEW : 1];
-      const float* xe[PW_FEW > 0 ? PW_FEW : 1];
+      int ev[PW_FEW];
+      const float* xe[PW_FEW];
       int ne = 0;
       for (int mleft = live_mask; mleft; mleft &= mleft - 1) {
         const int e = __ffs(mleft) - 1;

@@ -201,7 +201,6 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
   __builtin_amdgcn_sched_barrier(0);
   wload(0, wr[0]);
   wload(1, wr[1]);
-#ifndef TR_NO_XPREFETCH
   // this thread's x values ride with the prologue's loads and wait in the d2 slots they will be subtracted in (as f32 in the low
   // half of the slot: written and read by the same thread) -- at the end of the main loop they used to be one exposed round trip
   // to global memory for the wave that finishes last
@@ -220,7 +219,6 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
       for (int c = 0; c < TR_COLS; ++c)
         if (livec[c] && (c == 0 || (n >= c1_lo && n < c1_hi))) *(__attribute__((address_space(3))) float*)&rl->d2[n][mc[c]] = xv[c][n];
   }
-#endif
   __builtin_amdgcn_sched_barrier(0);
   if (tid < NE * NFAC) rl->fac[tid / NFAC][tid % NFAC] = facv;
   __syncthreads();
@@ -244,13 +242,6 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
 #pragma unroll
     for (int n = 0; n < NE; ++n) acc[c][n] = 0.0;
 
-#ifdef TR_FP_RESIDENT
-  double fpr[3][NE];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int n = 0; n < NE; ++n) fpr[k][n] = facf[n * FS + 3 + k];
-#endif
   TRS(1);
 
   // (i, j, k, l) in the einsum's nesting order.  VAR (compile time inside, chosen per wave): which evaluations column 1 takes
@@ -269,10 +260,9 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
 #pragma unroll
       for (int n = 0; n < NE; ++n) fy[n] = facf[n * FS + j];
       const int b0 = (i * 3 + j) * 3;
-#ifndef TR_NO_PRIO
       {  // Issue priority falls with progress (s_setprio takes an immediate: four levels).  The arbiter serves the OLDEST wave of a SIMD
          // first, so its three waves finished one after the other and the last ran alone, at the 4.8 cycles per instruction one wave
-         // sustains, for a third of the pass (main loop by wave: 59.7 k / 101.8 k / 131.5 k ticks; -DTR_NO_PRIO).  A wave that is
+         // sustains, for a third of the pass (main loop by wave: 59.7 k / 101.8 k / 131.5 k ticks without the priorities).  A wave that is
          // ahead now has the lower priority: it still fills the slots its siblings leave, but cannot run away -- only the last
          // segment's imbalance is left, hence segments of 8, 4, 2 and 1 of the 15 (i, j) steps: 119.8 k / 122.6 k / 121.6 k ticks
          // against 118.8 k of pure issue (135 rows x 44 chains x 5 operations x 4 cycles), the pass 143.3 k -> 132.5 k.
@@ -283,19 +273,12 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
         else if (ij == NIJ - 3) __builtin_amdgcn_s_setprio(1);
         else if (ij == NIJ - 1) __builtin_amdgcn_s_setprio(0);
       }
-#endif
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-#ifndef TR_ABL_NOLOAD
         wload(b0 + k + 2, wr[(k + 2) % 3]);
-#endif
         double fp[NE];
 #pragma unroll
-#ifdef TR_FP_RESIDENT
-        for (int n = 0; n < NE; ++n) fp[n] = fpr[k][n];
-#else
         for (int n = 0; n < NE; ++n) fp[n] = facf[n * FS + 3 + k];
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int l = 0; l < 3; ++l) {
@@ -346,9 +329,6 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
 #pragma unroll
   for (int n = 0; n < NE; ++n) {
     const int slot = (slots >> (4 * n)) & 15;
-#ifdef TR_NO_XPREFETCH
-    const float* xr = xrow(slot);
-#endif
 #ifdef TR_STAMPS
     double* xh = nullptr;
 #else
@@ -357,11 +337,7 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
 #pragma unroll
     for (int c = 0; c < TR_COLS; ++c)
       if (livec[c] && (c == 0 || (n >= c1_lo && n < c1_hi))) {
-#ifndef TR_NO_XPREFETCH
         const double d = (double)*(const __attribute__((address_space(3))) float*)&rl->d2[n][mc[c]] - acc[c][n];
-#else
-        const double d = (double)gload<float>(xr + mc[c]) - acc[c][n];
-#endif
         rl->d2[n][mc[c]] = d * d;
         if (xh) xh[mc[c]] = acc[c][n];
       }

@@ -520,8 +520,8 @@ def test_bf16_fused_landmarks(head_sds, device):
 
 @pytest.mark.parametrize("mode_name", ["bf16", "f16x2s", "f16x2", "f32"])
 def test_result_does_not_depend_on_where_a_row_starts_in_its_cache_line(mode_name, head_sds, device):
-    """The kernels stage x in 16-byte units and (bf16: always; strict-fast: with -DW8_XLINE) let the units of a slab's first 128-byte line
-    be loaded one slab ahead, by the row's phase within its line.  Same features behind every phase (base offsets of 0 / 16 / 48 / 112
+    """The kernels stage x in 16-byte units, and the bf16 kernel lets the units of a slab's first 128-byte line be loaded one slab
+    ahead, by the row's phase within its line.  Same features behind every phase (base offsets of 0 / 16 / 48 / 112
     bytes in line-aligned rows, and the packed 5,616-byte rows whose phase changes from row to row) must give the same bits."""
     from nlml_hpe_amd import _lib
     sd = synth.encoder_state_dict(1404, seed=0)
