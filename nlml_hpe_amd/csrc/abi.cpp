@@ -308,7 +308,7 @@ static int check_td_args(const char* who, int r_id, int order, int64_t N, int64_
 static int td_objective(const char* who, const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
                         const double* cos_params, int64_t N, double* err, double* x_hat, int r_id, int order, void* stream) {
   if (int rc = check_td_args(who, r_id, order, N, ldx, !Wm || !x || !params || !cos_params || !err, Wm, x)) return rc;
-  return launch_tucker_objective_r(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, r_id, order, stream);
+  return launch_tucker_objective(Wm, x, ldx, x_index, params, cos_params, N, err, x_hat, r_id, order, stream);
 }
 
 int nlml_tucker_objective(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
@@ -329,7 +329,7 @@ int nlml_tucker_objective_r(const float* Wm, const float* x, int64_t ldx, const 
 static int td_powell(const char* who, const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
                      double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order, void* stream) {
   if (int rc = check_td_args(who, r_id, order, N, ldx, !Wm || !x || !cos_params || !result, Wm, x)) return rc;
-  return launch_tucker_powell_r(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, r_id, order, stream);
+  return launch_tucker_powell(Wm, x, ldx, cos_params, N, x0, result, fval, nfev, nit, status, r_id, order, stream);
 }
 
 int nlml_tucker_powell(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,

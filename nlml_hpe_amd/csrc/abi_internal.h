@@ -90,23 +90,13 @@ int launch_normalize_ipd(const float* raw, int64_t B, int normalize, float* out,
                          void* stream);
 // normalize_centroid.hip
 int launch_normalize_centroid(const float* raw, int64_t B, float* out, uint8_t* valid, double* stats, void* stream);
-// tucker_objective.hip
-int launch_tucker_objective(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index,
-                            const double* params, const double* cos_params, int64_t N,
-                            double* err, double* x_hat, int order, void* stream);
-
-// tucker_powell.hip
-int launch_tucker_powell(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N,
-                         const double* x0, double* result, double* fval, int32_t* nfev, int32_t* nit,
-                         int32_t* status, int order, void* stream);
-
-// tucker_rank.hip: both of the above for an identity rank r_id = 1..NLML_TUCKER_RANK_MAX (Wm [27 r_id, 1404], 3 + r_id parameters);
-// r_id == 5 is handed on to the two launchers above -- what abi.cpp calls for every TD entry point
-int launch_tucker_objective_r(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
-                              const double* cos_params, int64_t N, double* err, double* x_hat, int r_id, int order, void* stream);
-int launch_tucker_powell_r(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
-                           double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order,
-                           void* stream);
+// tucker_objective.hip, tucker_powell.hip: K3 and the device-side Powell minimiser for an identity rank r_id = 1..NLML_TUCKER_RANK_MAX
+// (Wm [27 r_id, 1404], 3 + r_id parameters).  r_id == 5 runs the kernels with the rank as a constant, the shipped artefacts' code.
+int launch_tucker_objective(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                            const double* cos_params, int64_t N, double* err, double* x_hat, int r_id, int order, void* stream);
+int launch_tucker_powell(const float* Wm, const float* x, int64_t ldx, const double* cos_params, int64_t N, const double* x0,
+                         double* result, double* fval, int32_t* nfev, int32_t* nit, int32_t* status, int r_id, int order,
+                         void* stream);
 
 // tucker_gradient.hip (K3g): objective value and analytic gradient in the reference's operation order; workspace = the chains' rows + t
 size_t tucker_gradient_workspace_bytes(int64_t N);

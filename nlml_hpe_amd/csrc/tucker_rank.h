@@ -2,17 +2,20 @@
 //
 // The identity rank is a knob of the reference's model (configs/config_TD_main.yaml tensor_decom_ranks.R_identity; the reference
 // reads it from the artefact, TD_Inference.py:51, and runs objective / Test with 3 + R parameters whatever it is).  The kernels of
-// tucker_common.h / tucker_ref.h / tucker_powell.hip are tuned for the shipped artefacts' R = 5 and stay the code they are; the
-// pieces here take R at run time and share their arithmetic:
+// tucker_common.h / tucker_ref.h are tuned for the shipped artefacts' R = 5 and stay the code they are; the pieces here take R at
+// run time and share their arithmetic:
 //   reference order  tucker_ref_pass itself (tucker_ref.h) with a run-time rank: np.einsum keeps its operation order when only the
 //                    first extent changes, and the pairwise sum over the 1,404 residuals does not depend on R.  Bit-correct for every
 //                    R; its shape (768 threads x 2 columns, three-slot ring) is the one tuned for 135 rows;
 //   matrix cores     tucker_coef_r / tucker_mfma_r: x_hat = c^T Wm on v_mfma_f64_16x16x4_f64 with K = 27 R padded to a multiple of 4
 //                    by zero coefficient rows, the same columns per lane and the same q-ascending chains as tucker_mfma (at R = 5 the
 //                    same bits); no few-machine passes: every round of the Powell kernel is a 16-wide pass.
-// The largest tables bound the workgroup: see the LDS budget at tucker_powell_r_kernel (tucker_rank.hip).
+// The largest tables bound the workgroup: see the LDS budget at tucker_powell_kernel (tucker_powell.hip).
+// Below them: the rank traits and the functors over which tucker_objective.hip and tucker_powell.hip write every kernel once.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "powell.h"
 #include "tucker_common.h"
@@ -85,32 +88,89 @@ __device__ __forceinline__ void tucker_mfma_r(TuckerSharedR& sh, const float* __
   }
 }
 
-// tucker_ref_eval for a run-time rank and a table of RS::kMaxE evaluations per pass: the live machines go as the fewest passes that
-// hold them, of about the same size (16 live, 7 per pass: 6 + 5 + 5).
-template <typename SH, typename RS, typename ParT, typename XRow, typename XhRow>
-__device__ __forceinline__ void tucker_ref_eval_r(const SH& sh, RS& rs, const float* __restrict__ Wm, const ParT par, int mask,
-                                                  const XRow xrow, const XhRow xhrow, int tid, int rid) {
-  const TrDynRank rank{rid};
-  while (mask) {
-    const int cnt = __popc(mask);
-    const int passes = (cnt + RS::kMaxE - 1) / RS::kMaxE;
-    const int take = (cnt + passes - 1) / passes;
-    unsigned slots = 0;
-    for (int i = 0; i < take; ++i) {
-      slots |= (unsigned)(__ffs(mask) - 1) << (4 * i);
-      mask &= mask - 1;
-    }
-#define NLML_RANK_PASS(K)                                                                                 \
-  case K:                                                                                                 \
-    if constexpr (K <= RS::kMaxE) tucker_ref_pass<K>(sh, rs, Wm, par, slots, xrow, xhrow, tid, rank);     \
-    break;
-    switch (take) {
-      NLML_RANK_PASS(8) NLML_RANK_PASS(7) NLML_RANK_PASS(6) NLML_RANK_PASS(5)
-      NLML_RANK_PASS(4) NLML_RANK_PASS(3) NLML_RANK_PASS(2) NLML_RANK_PASS(1)
-      default: break;
-    }
-#undef NLML_RANK_PASS
+// ---- rank traits: what the TD kernels (tucker_objective.hip, tucker_powell.hip) let the rank choose -------------------------------
+// TdRank5: the shipped artefacts' identity rank, a constant of the type -- the tuned code above and below it is instantiated as it
+// always was.  TdRankDyn: a run-time rank 1..16.  Each names its Powell state, its LDS tables and its matrix-core bodies.
+template <bool INDEXED, bool CLAMPED>
+struct XRow;   // (below)
+struct TdRank5 {
+  static constexpr bool kFixed = true;          // matrix cores: tucker_coef + tucker_mfma, and the Powell kernel's few-machine passes
+  static constexpr int kFastWorkgroups = 2;     // __launch_bounds__ of the matrix-core Powell kernel: two workgroups per CU
+  typedef PowellState State;
+  typedef TuckerShared Shared;                  // matrix-core order
+  typedef TuckerShared FvecShared;              // reference order: only fvec is used; the type stays (LDS offsets inside the tuned pass)
+  typedef TuckerRefShared ObjRefShared;
+  typedef TuckerRefShared PowellRefShared;
+  typedef XRow<false, true> FaceRow;            // the Powell kernel's x rows: one per face, no index
+  static __device__ __forceinline__ TdRank5 make(int) { return {}; }
+  typedef std::integral_constant<int, PW_N> NPar;   // parameters per evaluation: a constant (reads as an int)
+  __device__ __forceinline__ constexpr NPar npar() const { return {}; }
+  __device__ __forceinline__ TrFixedRank<5> pass_rank() const { return {}; }
+};
+struct TdRankDyn {
+  static constexpr bool kFixed = false;         // matrix cores: tucker_coef_r + tucker_mfma_r, every round of the Powell kernel 16 wide
+  static constexpr int kFastWorkgroups = 1;
+  typedef PowellStateN State;
+  typedef TuckerSharedR Shared;
+  typedef TuckerFvecShared FvecShared;
+  typedef TuckerRefSharedR<8> ObjRefShared;
+  typedef TuckerRefSharedR<7> PowellRefShared;  // next to 16 machines of 19 parameters eight evaluations do not fit: tucker_powell_kernel
+  typedef XRow<true, true> FaceRow;             // with the (null) index member: the registers the run-time-rank passes were allocated with; without it passes of 6 and 7 spill
+  int rid;
+  static __device__ __forceinline__ TdRankDyn make(int rid) { return {rid}; }
+  typedef int NPar;
+  __device__ __forceinline__ int npar() const { return 3 + rid; }
+  __device__ __forceinline__ TrDynRank pass_rank() const { return {rid}; }
+};
+
+// this thread's cosine row (a,b,c,d), TD_Tester.py:26 (threads < 144; zeros beyond)
+__device__ __forceinline__ void load_cos_rows(const double* __restrict__ cosp, int tid, double (&cp4)[4]) {
+  cp4[0] = cp4[1] = cp4[2] = cp4[3] = 0.0;
+  if (tid < EV * 9) {
+    const double* c4 = cosp + ((tid % 9) / 3 * 3 + tid % 3) * 4;
+    cp4[0] = c4[0]; cp4[1] = c4[1]; cp4[2] = c4[2]; cp4[3] = c4[3];
   }
 }
+
+// par(e, k) from global memory: evaluations beyond the batch repeat the last one
+template <typename Rank>
+struct GlobalPar {
+  const double* p;   // params of this block's first evaluation
+  int64_t left;      // evaluations available from there (>= 1)
+  [[no_unique_address]] typename Rank::NPar n;   // parameters per evaluation
+  __device__ __forceinline__ double operator()(int e, int k) const {
+    return gload<double>(p + (e < left ? e : left - 1) * n + k);
+  }
+};
+
+// Row functors of the reference-order pass (passed by value into the non-inlined pass).  A member a variant does not use is Absent:
+// each instantiation carries the members, and evaluates the expression, it needs -- a run-time test here lands in the tuned pass.
+struct Absent {
+  template <typename T>
+  constexpr Absent(T) {}   // (takes and drops what the member would have held: one brace list builds every variant)
+};
+// x row of machine slot `slot`.  INDEXED: through x_index where given; CLAMPED: slots beyond N read the last row
+template <bool INDEXED, bool CLAMPED>
+struct XRow {
+  const float* x;
+  [[no_unique_address]] std::conditional_t<INDEXED, const int32_t*, Absent> x_index;
+  int64_t ldx, e0;
+  [[no_unique_address]] std::conditional_t<CLAMPED, int64_t, Absent> N;
+  __device__ __forceinline__ const float* operator()(int slot) const {
+    int64_t n = e0 + slot;
+    if constexpr (CLAMPED) n = n < N ? n : N - 1;
+    if constexpr (INDEXED) return x + (x_index ? (int64_t)x_index[n] : n) * ldx;
+    else return x + n * ldx;
+  }
+};
+struct XhRow {
+  double* x_hat;
+  int64_t e0;
+  __device__ __forceinline__ double* operator()(int slot) const { return x_hat ? x_hat + (e0 + slot) * TM : (double*)nullptr; }
+};
+struct NoXhRow {
+  static constexpr double* x_hat = nullptr;   // (the stamp build of the pass looks for this member)
+  __device__ __forceinline__ double* operator()(int) const { return nullptr; }
+};
 
 }  // namespace nlml

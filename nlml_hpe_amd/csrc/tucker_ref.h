@@ -411,32 +411,50 @@ __device__ __forceinline__ void tucker_fvec(SH& sh, const ParT& par, const doubl
   __syncthreads();
 }
 
-// The evaluations whose bit is set in `mask` (machine slots), up to eight per pass over Wm.  A pass costs what its evaluations
-// cost on the vector ALUs (~6 us each at the issue rate) but never less than streaming Wm through the CU (~10 us), so nine or
-// more live machines go as two passes of about the same size.  xrow(slot) -> that slot's x row; xhrow(slot) -> its x_hat output
-// row or nullptr.
-template <typename ParT, typename XRow, typename XhRow>
-__device__ __forceinline__ void tucker_ref_eval(const TuckerShared& sh, TuckerRefShared& rs, const float* __restrict__ Wm,
-                                                const ParT par, int mask, const XRow xrow, const XhRow xhrow, int tid) {
+// How many of `cnt` live machines the next pass takes when a pass holds up to `maxe`: the fewest passes that hold them, of about the
+// same size.  A pass costs what its evaluations cost on the vector ALUs (~6 us each at the issue rate) but never less than streaming
+// Wm through the CU (~10 us), so nine or more live machines at eight per pass go as two passes of about the same size.
+constexpr int tr_take(int cnt, int maxe) {
+  const int passes = (cnt + maxe - 1) / maxe;
+  return (cnt + passes - 1) / passes;
+}
+constexpr bool tr_take_splits(int maxe) {   // every count of live machines goes as passes of 1..maxe that sum to it
+  for (int cnt = 1; cnt <= EV; ++cnt)
+    for (int left = cnt; left > 0; left -= tr_take(left, maxe))
+      if (tr_take(left, maxe) < 1 || tr_take(left, maxe) > maxe || tr_take(left, maxe) > left) return false;
+  return true;
+}
+constexpr bool tr_take_is_rank5s() {        // at eight per pass: the split the rank-5 kernels have always made
+  for (int cnt = 1; cnt <= EV; ++cnt)
+    if (tr_take(cnt, TR_MAXE) != (cnt <= TR_MAXE ? cnt : (cnt + 1) / 2)) return false;
+  return true;
+}
+static_assert(tr_take_is_rank5s() && tr_take_splits(TR_MAXE) && tr_take_splits(7), "the split of the live machines into passes");
+static_assert(tr_take(16, 7) == 6 && tr_take(10, 7) == 5 && tr_take(5, 7) == 5, "16 live machines at seven per pass: 6 + 5 + 5");
+
+// The evaluations whose bit is set in `mask` (machine slots), up to RS::kMaxE per pass over Wm (tr_take).  xrow(slot) -> that slot's
+// x row; xhrow(slot) -> its x_hat output row or nullptr; rank: TrFixedRank<5> or TrDynRank.
+template <typename SH, typename RS, typename ParT, typename XRow, typename XhRow, typename Rank>
+__device__ __forceinline__ void tucker_ref_eval(const SH& sh, RS& rs, const float* __restrict__ Wm, const ParT par, int mask,
+                                                const XRow xrow, const XhRow xhrow, int tid, const Rank rank) {
+  static_assert(RS::kMaxE <= TR_MAXE, "the passes are instantiated for up to eight evaluations");
   while (mask) {
-    const int cnt = __popc(mask);
-    const int take = cnt <= TR_MAXE ? cnt : (cnt + 1) / 2;   // cnt <= EV = 16
+    const int take = tr_take(__popc(mask), RS::kMaxE);   // cnt <= EV = 16
     unsigned slots = 0;
     for (int i = 0; i < take; ++i) {
       slots |= (unsigned)(__ffs(mask) - 1) << (4 * i);
       mask &= mask - 1;
     }
+#define NLML_REF_PASS(K)                                                                                  \
+  case K:                                                                                                 \
+    if constexpr (K <= RS::kMaxE) tucker_ref_pass<K>(sh, rs, Wm, par, slots, xrow, xhrow, tid, rank);     \
+    break;
     switch (take) {
-      case 8: tucker_ref_pass<8>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
-      case 7: tucker_ref_pass<7>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
-      case 6: tucker_ref_pass<6>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
-      case 5: tucker_ref_pass<5>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
-      case 4: tucker_ref_pass<4>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
-      case 3: tucker_ref_pass<3>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
-      case 2: tucker_ref_pass<2>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
-      case 1: tucker_ref_pass<1>(sh, rs, Wm, par, slots, xrow, xhrow, tid); break;
+      NLML_REF_PASS(8) NLML_REF_PASS(7) NLML_REF_PASS(6) NLML_REF_PASS(5)
+      NLML_REF_PASS(4) NLML_REF_PASS(3) NLML_REF_PASS(2) NLML_REF_PASS(1)
       default: break;
     }
+#undef NLML_REF_PASS
   }
 }
 

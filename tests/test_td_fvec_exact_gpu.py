@@ -4,15 +4,15 @@ cos / sin, rounded once; tests/test_cr_reference_host.py ties it to the host bui
 result, and with no tolerance:
 
   * the bare cr_cos through the cosine table on ~100,000 hard arguments (artefacts.hip);
-  * the f entry at every compile site that has a read-out -- the reference order at rank 5 (tucker_objective.hip) and at ranks 1 and 16
-    (tucker_rank.hip), the matrix-core order at ranks 5 and 1 (tucker_common.h, tucker_rank.h), the gradient at ranks 5 and 1
+  * the f entry at every compile site that has a read-out -- the reference order at rank 5 and at ranks 1 and 16 (the two
+    instantiations of tucker_objective.hip's kernel), the matrix-core order at ranks 5 and 1 (tucker_common.h, tucker_rank.h), the gradient at ranks 5 and 1
     (tucker_gradient.hip) -- on inputs built so that the float32 depends on the last bits of the cos: every one of them takes the
     header's double-double path, and a cos one ulp off would change 7 to 30 % of the results;
   * the df entry (the only read-out of cr_sin) the same way;
   * objective and gradient on the points scipy's Powell really visits (|w| to 2.6, |u_id| beyond 1.5: far outside the draws of the
     other bit-exact tests), where a handful of entries take the slow path in every run.
 
-NOT covered here: the Powell kernel's own instantiation of the f-vectors (tucker_powell.hip, tucker_rank.hip's Powell kernel) has
+NOT covered here: the Powell kernel's own instantiation of the f-vectors (the instantiations of tucker_powell.hip's kernel) has
 no read-out -- one flipped evaluation need not move nfev -- and stays covered by the trajectory tests of tests/test_gpu_parity.py and
 tests/test_td_rank_gpu.py only."""
 import os
