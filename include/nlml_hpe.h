@@ -85,6 +85,61 @@ int nlml_normalize_centroid(const float* raw, int64_t B, float* out, uint8_t* va
 int nlml_normalize_centroid_host(const float* h_raw, int64_t B, float* h_out, uint8_t* h_valid, double* h_stats);
 
 /* ------------------------------------------------------------------------------------------
+ * K6  Landmarks at a known pose: the rotation training tensor, and one pose per face.
+ * Replaces the rotation branch of CreateTensor.Compose_Tensor (CreateTensor.py:96-114, use_rotation_features=1, the
+ * default source of the training tensor, TD_main.py:58) and helpers/IntrinsicRotation.apply_rotations
+ * (IntrinsicRotation.py:108-120).  No trigonometry runs on the device: the 3x3 f64 matrices are inputs, built on
+ * the host as rotation_matrix builds them (IntrinsicRotation.py:90-105).
+ *
+ * The contract is the operation order, numpy's own for a [468,3] block, with a[i] = (double)lm[i][.]:
+ *   1. a stage is b = a @ M:  b[j] = fma(a[2], M[2][j], fma(a[1], M[1][j], fma(a[0], M[0][j], +0.0))).  The
+ *      accumulator starts at +0.0 and the first term is an fma too: a product that is -0.0 gives +0.0.
+ *   2. a pose is three stages, every stage's outputs rounded to f64 before the next:
+ *        NLML_ROT_INTRINSIC   ((L @ Rx(pitch)) @ Ry(yaw)) @ Rz(roll)            stages pitch, yaw, roll
+ *        NLML_ROT_EXTRINSIC   ((L @ Rz(roll)^T) @ Ry(yaw)^T) @ Rx(pitch)^T      stages roll, yaw, pitch; the CALLER
+ *                             passes the transposed matrices
+ *   3. out = (float)(third stage): one rounding to f32 (CreateTensor.py:110);  out64 = the third stage itself.
+ *   4. copy rule (grid mode only, CreateTensor.py:97-98): the cell whose three bins are the zero bins is the base
+ *      landmarks bit for bit (a -0.0 coordinate stays -0.0; rotating by identity matrices would give +0.0); its
+ *      out64 is the same values widened.
+ * NaN and Inf inputs propagate as in numpy.  Bit-exact with the reference.
+ *
+ * nlml_compose_rotation_tensor (grid mode):
+ *   base      f32[I,468,3]   the pose-(0,0,0) landmarks per identity
+ *   rot_yaw   f64[ny,3,3], rot_pitch f64[np,3,3], rot_roll f64[nr,3,3]   one matrix per bin, row-major
+ *   order     NLML_ROT_INTRINSIC or NLML_ROT_EXTRINSIC
+ *   zero_yaw, zero_pitch, zero_roll   index of the bin whose value is 0 on that axis, or -1 (no copy)
+ *   out       f32[I,ny,np,nr,1404]   the reference's composition_tensor[id, yaw, pitch, roll, :], x,y,z interleaved
+ *   out64     f64[I,ny,np,nr,1404] or NULL
+ * nlml_rotate_landmarks (one pose per face, apply_rotations itself, no copy rule):
+ *   lm        f32[B,468,3]
+ *   rot       f64[B,3,3,3]   each face's three matrices in application order
+ *   out       f32[B,468,3] or NULL;  out64 f64[B,468,3] or NULL;  at least one of them
+ * Checks, in this order, before any launch:
+ *   1. a required buffer is NULL (required: while no extent is 0)          -> NLML_E_BADARG
+ *   2. a negative extent                                                    -> NLML_E_BADARG
+ *   3. an unknown `order`                                                   -> NLML_E_BADARG
+ *   4. a zero_* outside -1 .. n-1                                           -> NLML_E_BADARG
+ *   5. I, ny, np, nr or B of 0                                              -> 0, no launch, no buffer looked at
+ *   6. alignment as nlml_normalize_centroid: f32 buffers 16-byte, f64 buffers 8-byte aligned;
+ *      a tensor of more than INT64_MAX elements                            -> NLML_E_BADARG
+ * All row and byte offsets are 64-bit.
+ *
+ * The *_host forms evaluate the same order on HOST buffers in plain C++ (no HIP call, no alignment rule, h_out may
+ * be NULL where h_out64 is given): the order can be pinned on a machine without a GPU.
+ */
+#define NLML_ROT_INTRINSIC 0
+#define NLML_ROT_EXTRINSIC 1
+int nlml_compose_rotation_tensor(const float* base, int64_t I, const double* rot_yaw, int ny, const double* rot_pitch, int np,
+                                 const double* rot_roll, int nr, int order, int zero_yaw, int zero_pitch, int zero_roll,
+                                 float* out, double* out64, void* stream);
+int nlml_rotate_landmarks(const float* lm, const double* rot, float* out, double* out64, int64_t B, void* stream);
+int nlml_compose_rotation_tensor_host(const float* h_base, int64_t I, const double* h_rot_yaw, int ny, const double* h_rot_pitch, int np,
+                                      const double* h_rot_roll, int nr, int order, int zero_yaw, int zero_pitch, int zero_roll,
+                                      float* h_out, double* h_out64);
+int nlml_rotate_landmarks_host(const float* h_lm, const double* h_rot, float* h_out, double* h_out64, int64_t B);
+
+/* ------------------------------------------------------------------------------------------
  * K2  Encoder + three heads, fused forward.
  * Replaces CombinedAnglePredictionModel.forward (NLML_HPE_Model_Builder.py:115-126), i.e.
  * LandmarkEncoder.forward (:55-68) and 3 x AnglePredictionNetwork.forward (:104-105), called

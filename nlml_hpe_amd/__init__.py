@@ -9,7 +9,8 @@ Host layer above the C ABI of ``include/nlml_hpe.h`` (``libnlml_hpe_hip.so``, bu
     pose, valid = model.from_landmarks(raw, return_valid=True)              # raw FaceMesh landmarks f32[B,468,3]
 
 Modules: ``ops`` (tensor-level operators, also ``torch.ops.nlml_hpe.*``), ``model``, ``TD_Tester`` (Tucker
-objective and device-side Powell under the reference's function names), ``video``, ``metrics``, ``pipeline``
+objective and device-side Powell under the reference's function names), ``CreateTensor`` and ``IntrinsicRotation`` (the rotation
+training tensor and landmarks at a known pose, under the reference's function names), ``video``, ``metrics``, ``pipeline``
 (host-resident batches), ``distributed`` (sharding + all-gather), ``weights`` (artefact layout, packing), ``synth``
 (seeded synthetic inputs/weights).
 """

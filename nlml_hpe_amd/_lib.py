@@ -44,6 +44,8 @@ def _td_entries():
     yield "nlml_tucker_gradient_host", (C.c_int, _TD_EVAL + [C.c_int, C.c_void_p])
 
 
+_ROT_GRID = ([C.c_void_p, C.c_int64] + [C.c_void_p, C.c_int] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p])
+
 SYMBOLS = {
     **dict(_k2_forwards()),
     **dict(_td_entries()),
@@ -53,6 +55,12 @@ SYMBOLS = {
     # raw, B, out, valid, stats[, stream]
     "nlml_normalize_centroid": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_normalize_centroid_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # K6: base, I, rot_yaw, ny, rot_pitch, np, rot_roll, nr, order, zero_yaw, zero_pitch, zero_roll, out, out64[, stream]
+    "nlml_compose_rotation_tensor": (C.c_int, _ROT_GRID + [C.c_void_p]),
+    "nlml_compose_rotation_tensor_host": (C.c_int, _ROT_GRID),
+    # lm, rot, out, out64, B[, stream]
+    "nlml_rotate_landmarks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nlml_rotate_landmarks_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "nlml_encoder_heads_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "nlml_encoder_heads_pack": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t]),
@@ -97,7 +105,10 @@ DEFAULT_MODE_NAME = "f16x2s"
 TD_ORDER_FAST = 0          # GEMM on the f64 matrix cores (<= 1e-12 rel. of the reference's objective)
 TD_ORDER_REFERENCE = 1     # np.einsum's own operation order + numpy's pairwise sum: the reference's bits
 TD_ORDER_NAMES = {"fast": TD_ORDER_FAST, "reference": TD_ORDER_REFERENCE}
-TUCKER_RANK_MIN, TUCKER_RANK_MAX = 1, 16   # NLML_TUCKER_RANK_MIN / NLML_TUCKER_RANK_MAX: identity ranks of the *_r entry points
+ROT_INTRINSIC = 0          # NLML_ROT_INTRINSIC: stages pitch, yaw, roll
+ROT_EXTRINSIC = 1          # NLML_ROT_EXTRINSIC: stages roll, yaw, pitch, the matrices transposed by the caller
+ROT_ORDER_NAMES = {"intrinsic": ROT_INTRINSIC, "extrinsic": ROT_EXTRINSIC}
+TUCKER_RANK_MIN, TUCKER_RANK_MAX = 1, 16  # NLML_TUCKER_RANK_MIN / NLML_TUCKER_RANK_MAX: identity ranks of the *_r entry points
 POSE_EVAL_MAX_INTERVALS = 64       # NLML_POSE_EVAL_MAX_INTERVALS
 POSE_EVAL_FACES_PER_RECORD = 2048  # NLML_POSE_EVAL_FACES_PER_RECORD
 
@@ -109,6 +120,17 @@ def td_order_from_name(order) -> int:
         return TD_ORDER_NAMES[order]
     if int(order) not in TD_ORDER_NAMES.values():
         raise ValueError(f"unknown TD order {order!r}")
+    return int(order)
+
+
+def rot_order_from_name(order) -> int:
+    """Accepts a NLML_ROT_* constant or the reference's rotation_type string ("intrinsic", "extrinsic")."""
+    if isinstance(order, str):
+        if order not in ROT_ORDER_NAMES:
+            raise ValueError("Rotation type must be 'intrinsic' or 'extrinsic'.")
+        return ROT_ORDER_NAMES[order]
+    if int(order) not in ROT_ORDER_NAMES.values():
+        raise ValueError(f"unknown rotation order {order!r}")
     return int(order)
 
 

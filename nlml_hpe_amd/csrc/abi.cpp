@@ -11,6 +11,7 @@
 #include "centroid_ref.h"
 #include "layout.h"
 #include "powell.h"
+#include "rotate_ref.h"
 #include "tucker_grad_ref.h"
 
 namespace nlml {
@@ -57,6 +58,79 @@ int nlml_normalize_centroid_host(const float* h_raw, int64_t B, float* h_out, ui
     const int v = cn_face_host(h_raw + b * NLML_F_REFERENCE, h_out + b * NLML_F_REFERENCE, h_stats ? h_stats + 4 * b : nullptr);
     if (h_valid) h_valid[b] = (uint8_t)v;
   }
+  return 0;
+}
+
+// K6: the checks of include/nlml_hpe.h in their stated order, shared by the device and the host forms.  -> 0 with *rows = the number
+// of rows to write (0: nothing to do), or the error.
+static int check_rotation_grid(const char* who, bool have_buffers, int64_t I, int ny, int np, int nr, int order, int zy, int zp, int zr,
+                               int64_t* rows) {
+  char msg[128];
+  const bool empty = I == 0 || ny == 0 || np == 0 || nr == 0;
+  auto refuse = [&](const char* what) {
+    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return fail(NLML_E_BADARG, msg);
+  };
+  if (!empty && !have_buffers) return refuse("null buffer");
+  if (I < 0 || ny < 0 || np < 0 || nr < 0) return refuse("negative extent");
+  if (order != NLML_ROT_INTRINSIC && order != NLML_ROT_EXTRINSIC) return refuse("unknown order");
+  if (zy < -1 || zy >= ny || zp < -1 || zp >= np || zr < -1 || zr >= nr) return refuse("zero index outside -1..n-1");
+  *rows = 0;
+  if (empty) return 0;
+  int64_t n = 0;
+  if (__builtin_mul_overflow(I, (int64_t)ny, &n) || __builtin_mul_overflow(n, (int64_t)np, &n) || __builtin_mul_overflow(n, (int64_t)nr, &n) ||
+      n > INT64_MAX / (NLML_F_REFERENCE * 8))
+    return refuse("tensor too large for 64-bit byte offsets");
+  *rows = n;
+  return 0;
+}
+
+int nlml_compose_rotation_tensor(const float* base, int64_t I, const double* rot_yaw, int ny, const double* rot_pitch, int np,
+                                 const double* rot_roll, int nr, int order, int zero_yaw, int zero_pitch, int zero_roll, float* out,
+                                 double* out64, void* stream) {
+  int64_t rows;
+  if (const int rc = check_rotation_grid("compose_rotation_tensor", base && rot_yaw && rot_pitch && rot_roll && out, I, ny, np, nr, order,
+                                         zero_yaw, zero_pitch, zero_roll, &rows))
+    return rc;
+  if (rows == 0) return 0;
+  if ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(out)) & 15)
+    return fail(NLML_E_BADARG, "compose_rotation_tensor: base/out must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(rot_yaw) | reinterpret_cast<uintptr_t>(rot_pitch) | reinterpret_cast<uintptr_t>(rot_roll) |
+       reinterpret_cast<uintptr_t>(out64)) & 7)
+    return fail(NLML_E_BADARG, "compose_rotation_tensor: the matrices and out64 must be 8-byte aligned");
+  return launch_compose_rotation_tensor(base, rows, rot_yaw, ny, rot_pitch, np, rot_roll, nr, order, zero_yaw, zero_pitch, zero_roll, out,
+                                        out64, stream);
+}
+
+int nlml_compose_rotation_tensor_host(const float* h_base, int64_t I, const double* h_rot_yaw, int ny, const double* h_rot_pitch, int np,
+                                      const double* h_rot_roll, int nr, int order, int zero_yaw, int zero_pitch, int zero_roll,
+                                      float* h_out, double* h_out64) {
+  int64_t rows;
+  if (const int rc = check_rotation_grid("compose_rotation_tensor_host", h_base && h_rot_yaw && h_rot_pitch && h_rot_roll && (h_out || h_out64),
+                                         I, ny, np, nr, order, zero_yaw, zero_pitch, zero_roll, &rows))
+    return rc;
+  if (rows) rt_grid_host(h_base, I, h_rot_yaw, ny, h_rot_pitch, np, h_rot_roll, nr, order, zero_yaw, zero_pitch, zero_roll, h_out, h_out64);
+  return 0;
+}
+
+int nlml_rotate_landmarks(const float* lm, const double* rot, float* out, double* out64, int64_t B, void* stream) {
+  if (B != 0 && (!lm || !rot || (!out && !out64))) return fail(NLML_E_BADARG, "rotate_landmarks: null buffer (lm, rot, and out or out64)");
+  if (B < 0) return fail(NLML_E_BADARG, "rotate_landmarks: negative extent");
+  if (B == 0) return 0;
+  if (B > INT64_MAX / (NLML_F_REFERENCE * 8)) return fail(NLML_E_BADARG, "rotate_landmarks: too many faces for 64-bit byte offsets");
+  if ((reinterpret_cast<uintptr_t>(lm) | reinterpret_cast<uintptr_t>(out)) & 15)
+    return fail(NLML_E_BADARG, "rotate_landmarks: lm/out must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(rot) | reinterpret_cast<uintptr_t>(out64)) & 7)
+    return fail(NLML_E_BADARG, "rotate_landmarks: rot/out64 must be 8-byte aligned");
+  return launch_rotate_landmarks(lm, rot, out, out64, B, stream);
+}
+
+int nlml_rotate_landmarks_host(const float* h_lm, const double* h_rot, float* h_out, double* h_out64, int64_t B) {
+  if (B != 0 && (!h_lm || !h_rot || (!h_out && !h_out64))) return fail(NLML_E_BADARG, "rotate_landmarks_host: null buffer (lm, rot, and out or out64)");
+  if (B < 0) return fail(NLML_E_BADARG, "rotate_landmarks_host: negative extent");
+  for (int64_t b = 0; b < B; ++b)
+    rt_face_host(h_lm + b * NLML_F_REFERENCE, h_rot + b * 27, h_rot + b * 27 + 9, h_rot + b * 27 + 18,
+                 h_out ? h_out + b * NLML_F_REFERENCE : nullptr, h_out64 ? h_out64 + b * NLML_F_REFERENCE : nullptr);
   return 0;
 }
 

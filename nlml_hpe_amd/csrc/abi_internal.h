@@ -90,6 +90,11 @@ int launch_normalize_ipd(const float* raw, int64_t B, int normalize, float* out,
                          void* stream);
 // normalize_centroid.hip
 int launch_normalize_centroid(const float* raw, int64_t B, float* out, uint8_t* valid, double* stats, void* stream);
+// rotate_landmarks.hip (K6): rows = I * ny * np * nr of the grid, one face and pose each
+int launch_compose_rotation_tensor(const float* base, int64_t rows, const double* rot_yaw, int ny, const double* rot_pitch, int np,
+                                   const double* rot_roll, int nr, int order, int zero_yaw, int zero_pitch, int zero_roll, float* out,
+                                   double* out64, void* stream);
+int launch_rotate_landmarks(const float* lm, const double* rot, float* out, double* out64, int64_t B, void* stream);
 // tucker_objective.hip, tucker_powell.hip: K3 and the device-side Powell minimiser for an identity rank r_id = 1..NLML_TUCKER_RANK_MAX
 // (Wm [27 r_id, 1404], 3 + r_id parameters).  r_id == 5 runs the kernels with the rank as a constant, the shipped artefacts' code.
 int launch_tucker_objective(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,

@@ -85,6 +85,55 @@ at::Tensor normalize_centroid(const at::Tensor& raw_) {
   return out;
 }
 
+// K6, grid mode: base f32[I,468,3], one f64[n,3,3] table per axis -> (out f32[I,ny,np,nr,1404], out64 f64[same] or an empty f64[0]).
+// zero_index: the three zero bins (yaw, pitch, roll), -1 = none.
+std::tuple<at::Tensor, at::Tensor> compose_rotation_tensor(const at::Tensor& base_, const at::Tensor& ry_, const at::Tensor& rp_,
+                                                           const at::Tensor& rr_, int64_t order, at::IntArrayRef zero_index, bool return_f64) {
+  need(base_, "base", at::kFloat);
+  TORCH_CHECK(base_.dim() == 3 && base_.size(1) == 468 && base_.size(2) == 3, "base: expected [I,468,3], got ", base_.sizes());
+  const at::Tensor* const tabs[] = {&ry_, &rp_, &rr_};
+  const char* const names[] = {"rot_yaw", "rot_pitch", "rot_roll"};
+  for (int k = 0; k < 3; ++k) {
+    need(*tabs[k], names[k], at::kDouble);
+    same_device(base_, *tabs[k], names[k]);
+    TORCH_CHECK(tabs[k]->dim() == 3 && tabs[k]->size(1) == 3 && tabs[k]->size(2) == 3, names[k], ": expected [n,3,3], got ", tabs[k]->sizes());
+  }
+  TORCH_CHECK(zero_index.size() == 3, "zero_index: expected 3 values (yaw, pitch, roll)");
+  const at::Tensor base = base_.contiguous(), ry = ry_.contiguous(), rp = rp_.contiguous(), rr = rr_.contiguous();
+  const int64_t I = base.size(0), ny = ry.size(0), np = rp.size(0), nr = rr.size(0);
+  TORCH_CHECK(ny <= INT32_MAX && np <= INT32_MAX && nr <= INT32_MAX, "more than 2^31 - 1 bins on an axis");
+  for (int k = 0; k < 3; ++k)
+    TORCH_CHECK(zero_index[k] >= -1 && zero_index[k] < tabs[k]->size(0), "zero_index[", k, "] = ", zero_index[k], " is outside -1..n-1");
+  at::Tensor out = at::empty({I, ny, np, nr, F_REF}, base.options());
+  at::Tensor out64 = return_f64 ? at::empty({I, ny, np, nr, F_REF}, ry.options()) : at::empty({0}, ry.options());
+  OnDevice dev(base);
+  check(nlml_compose_rotation_tensor(base.data_ptr<float>(), I, ry.data_ptr<double>(), (int)ny, rp.data_ptr<double>(), (int)np,
+                                     rr.data_ptr<double>(), (int)nr, (int)order, (int)zero_index[0], (int)zero_index[1], (int)zero_index[2],
+                                     out.data_ptr<float>(), return_f64 ? out64.data_ptr<double>() : nullptr, dev.stream),
+        "nlml_compose_rotation_tensor");
+  return {out, out64};
+}
+
+// K6, one pose per face: lm f32[B,468,3], rot f64[B,3,3,3] (application order) -> (f32[B,468,3], f64[B,468,3]); the one not asked for
+// is an empty [0]
+std::tuple<at::Tensor, at::Tensor> rotate_landmarks(const at::Tensor& lm_, const at::Tensor& rot_, bool return_f32, bool return_f64) {
+  need(lm_, "lm", at::kFloat);
+  need(rot_, "rot", at::kDouble);
+  same_device(lm_, rot_, "rot");
+  TORCH_CHECK(lm_.dim() == 3 && lm_.size(1) == 468 && lm_.size(2) == 3, "lm: expected [B,468,3], got ", lm_.sizes());
+  const int64_t B = lm_.size(0);
+  TORCH_CHECK(rot_.dim() == 4 && rot_.size(0) == B && rot_.size(1) == 3 && rot_.size(2) == 3 && rot_.size(3) == 3, "rot: expected [", B,
+              ",3,3,3], got ", rot_.sizes());
+  TORCH_CHECK(return_f32 || return_f64, "rotate_landmarks: at least one of return_f32, return_f64");
+  const at::Tensor lm = lm_.contiguous(), rot = rot_.contiguous();
+  at::Tensor out = return_f32 ? at::empty({B, 468, 3}, lm.options()) : at::empty({0}, lm.options());
+  at::Tensor out64 = return_f64 ? at::empty({B, 468, 3}, rot.options()) : at::empty({0}, rot.options());
+  OnDevice dev(lm);
+  check(nlml_rotate_landmarks(lm.data_ptr<float>(), rot.data_ptr<double>(), return_f32 ? out.data_ptr<float>() : nullptr,
+                              return_f64 ? out64.data_ptr<double>() : nullptr, B, dev.stream), "nlml_rotate_landmarks");
+  return {out, out64};
+}
+
 // The K2 forwards: the checks, the allocation and the call behind the five forward ops and landmarks_to_pose_valid.  in_ is the raw
 // landmarks [B,468,3] (landmarks) or the feature rows [B,F]; ws given = the layer-per-launch path through that workspace, else the fused
 // launch; want_valid adds the "a face was found" mask u8[B] (row not all-zero).
@@ -319,6 +368,15 @@ std::tuple<at::Tensor, at::Tensor> pose_eval_merge(const at::Tensor& records_, i
 // ---- shapes only (Meta backend: tracing / fake tensors) -------------------------------------------------------------
 at::Tensor normalize_ipd_meta(const at::Tensor& raw, bool) { return at::empty({raw.size(0), F_REF}, raw.options()); }
 at::Tensor normalize_centroid_meta(const at::Tensor& raw) { return at::empty({raw.size(0), F_REF}, raw.options()); }
+std::tuple<at::Tensor, at::Tensor> compose_rotation_tensor_meta(const at::Tensor& base, const at::Tensor& ry, const at::Tensor& rp,
+                                                                const at::Tensor& rr, int64_t, at::IntArrayRef, bool return_f64) {
+  const std::vector<int64_t> shape = {base.size(0), ry.size(0), rp.size(0), rr.size(0), F_REF};
+  return {at::empty(shape, base.options()), return_f64 ? at::empty(shape, ry.options()) : at::empty({0}, ry.options())};
+}
+std::tuple<at::Tensor, at::Tensor> rotate_landmarks_meta(const at::Tensor& lm, const at::Tensor& rot, bool return_f32, bool return_f64) {
+  return {return_f32 ? at::empty({lm.size(0), 468, 3}, lm.options()) : at::empty({0}, lm.options()),
+          return_f64 ? at::empty({lm.size(0), 468, 3}, rot.options()) : at::empty({0}, rot.options())};
+}
 template <class... Rest> at::Tensor pose_meta(const at::Tensor& x, const at::Tensor&, Rest...) { return at::empty({x.size(0), 3}, x.options()); }
 at::Tensor tucker_objective_meta(const at::Tensor&, const at::Tensor&, const at::Tensor& params, const at::Tensor&, std::string) {
   return at::empty({params.size(0)}, params.options());
@@ -354,6 +412,9 @@ std::tuple<at::Tensor, at::Tensor> pose_eval_merge_meta(const at::Tensor& record
 TORCH_LIBRARY(nlml_hpe, m) {
   m.def("normalize_ipd(Tensor raw, bool normalize) -> Tensor");
   m.def("normalize_centroid(Tensor raw) -> Tensor");
+  m.def("compose_rotation_tensor(Tensor base, Tensor rot_yaw, Tensor rot_pitch, Tensor rot_roll, int order, int[] zero_index, "
+        "bool return_f64=False) -> (Tensor, Tensor)");
+  m.def("rotate_landmarks(Tensor lm, Tensor rot, bool return_f32=True, bool return_f64=False) -> (Tensor, Tensor)");
   m.def("encoder_heads_fwd(Tensor x, Tensor packed_w, int F) -> Tensor");
   m.def("landmarks_to_pose(Tensor raw, Tensor packed_w, bool normalize) -> Tensor");
   m.def("encoder_heads_fwd_small(Tensor x, Tensor packed_w, int F, Tensor workspace) -> Tensor");
@@ -373,6 +434,8 @@ TORCH_LIBRARY(nlml_hpe, m) {
 TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CUDA key
   m.impl("normalize_ipd", &normalize_ipd);
   m.impl("normalize_centroid", &normalize_centroid);
+  m.impl("compose_rotation_tensor", &compose_rotation_tensor);
+  m.impl("rotate_landmarks", &rotate_landmarks);
   m.impl("encoder_heads_fwd", &encoder_heads_fwd);
   m.impl("landmarks_to_pose", &landmarks_to_pose);
   m.impl("encoder_heads_fwd_small", &encoder_heads_fwd_small);
@@ -390,6 +453,8 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
 TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("normalize_ipd", &normalize_ipd_meta);
   m.impl("normalize_centroid", &normalize_centroid_meta);
+  m.impl("compose_rotation_tensor", &compose_rotation_tensor_meta);
+  m.impl("rotate_landmarks", &rotate_landmarks_meta);
   m.impl("encoder_heads_fwd", &pose_meta<int64_t>);
   m.impl("landmarks_to_pose", &pose_meta<bool>);
   m.impl("encoder_heads_fwd_small", &pose_meta<int64_t, const at::Tensor&>);

@@ -92,6 +92,61 @@ def normalize_centroid(raw: torch.Tensor, return_valid: bool = False, return_sta
     return res[0] if len(res) == 1 else tuple(res)
 
 
+def _rot_table(t: torch.Tensor, name: str) -> torch.Tensor:
+    _need_cuda(t, name, torch.float64)
+    if t.dim() != 3 or t.shape[1:] != (3, 3):
+        raise ValueError(f"{name}: expected [n,3,3], got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def compose_rotation_tensor(base: torch.Tensor, rot_yaw: torch.Tensor, rot_pitch: torch.Tensor, rot_roll: torch.Tensor,
+                            order="intrinsic", zero_index=None, return_f64: bool = False):
+    """The rotation training tensor (CreateTensor.py:96-114): base f32[I,468,3], one f64[n,3,3] matrix table per axis ->
+    f32[I,ny,np,nr,1404] (+ f64 of the same shape), the reference's bits.  order: "intrinsic" (stages pitch, yaw, roll) or "extrinsic"
+    (stages roll, yaw, pitch; pass the transposed matrices).  zero_index: (yaw, pitch, roll) indices of the bins whose value is 0 --
+    that cell is the base copied bit for bit -- or -1 / None where there is none."""
+    _need_cuda(base, "base", torch.float32)
+    if base.dim() != 3 or base.shape[1:] != (468, 3):
+        raise ValueError(f"base: expected [I,468,3], got {tuple(base.shape)}")
+    base = base.contiguous()
+    rot_yaw, rot_pitch, rot_roll = _rot_table(rot_yaw, "rot_yaw"), _rot_table(rot_pitch, "rot_pitch"), _rot_table(rot_roll, "rot_roll")
+    order = _lib.rot_order_from_name(order)
+    zero = [-1, -1, -1] if zero_index is None else [int(z) for z in zero_index]
+    I, ny, np_, nr = base.shape[0], rot_yaw.shape[0], rot_pitch.shape[0], rot_roll.shape[0]
+    if len(zero) != 3 or any(not -1 <= z < n for z, n in zip(zero, (ny, np_, nr))):
+        raise ValueError(f"zero_index: expected (yaw, pitch, roll) indices in -1..n-1 for {ny} x {np_} x {nr} bins, got {zero_index!r}")
+    out = torch.empty((I, ny, np_, nr, F_REF), dtype=torch.float32, device=base.device)
+    out64 = torch.empty((I, ny, np_, nr, F_REF), dtype=torch.float64, device=base.device) if return_f64 else None
+    with _on_device_of(("base", base), ("rot_yaw", rot_yaw), ("rot_pitch", rot_pitch), ("rot_roll", rot_roll)) as stream:
+        _lib.check(_lib.lib().nlml_compose_rotation_tensor(
+            base.data_ptr(), I, rot_yaw.data_ptr(), ny, rot_pitch.data_ptr(), np_, rot_roll.data_ptr(), nr, order, *zero, out.data_ptr(),
+            out64.data_ptr() if return_f64 else None, stream), "nlml_compose_rotation_tensor")
+    return (out, out64) if return_f64 else out
+
+
+def rotate_landmarks(lm: torch.Tensor, rot: torch.Tensor, return_f64: bool = False, return_f32: bool = True):
+    """apply_rotations (IntrinsicRotation.py:108-120) with one pose per face: lm f32[B,468,3], rot f64[B,3,3,3] (each face's three
+    matrices in application order) -> f32[B,468,3] (one rounding of the f64 result) and / or the f64[B,468,3] itself, the reference's
+    bits."""
+    _need_cuda(lm, "lm", torch.float32)
+    _need_cuda(rot, "rot", torch.float64)
+    lm = _raw_rows(lm)
+    B = lm.shape[0]
+    if tuple(rot.shape) != (B, 3, 3, 3):
+        raise ValueError(f"rot: expected [{B},3,3,3], got {tuple(rot.shape)}")
+    if not (return_f32 or return_f64):
+        raise ValueError("rotate_landmarks: at least one of return_f32, return_f64")
+    rot = rot.contiguous()
+    out = torch.empty((B, 468, 3), dtype=torch.float32, device=lm.device) if return_f32 else None
+    out64 = torch.empty((B, 468, 3), dtype=torch.float64, device=lm.device) if return_f64 else None
+    with _on_device_of(("lm", lm), ("rot", rot)) as stream:
+        _lib.check(_lib.lib().nlml_rotate_landmarks(lm.data_ptr(), rot.data_ptr(), out.data_ptr() if return_f32 else None,
+                                                    out64.data_ptr() if return_f64 else None, B, stream), "nlml_rotate_landmarks")
+    if return_f32 and return_f64:
+        return out, out64
+    return out if return_f32 else out64
+
+
 # ---- the K2 forward (encoder + heads): one private forward behind the five public wrappers ---------------------------------------
 _k2_ws: dict = {}
 
@@ -289,7 +344,7 @@ def _load_torch_ops():
     # the registered ops; *_small take an explicit workspace, landmarks_to_pose_valid is the video tick's forward (pose + face mask)
     for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
-                 "pose_eval_merge"):
+                 "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
 
