@@ -28,6 +28,15 @@ inline K2Input k2_input(const float* x, int64_t ldx, const float* raw, int norma
   a.vec4 = (F % 4 == 0) && (a.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.src) & 15) == 0);
   return a;
 }
+// The arguments every K2 kernel takes (Args: hx::Args, bf::w8::Args or the f32 kernel's EncArgs), from a launcher's own arguments and
+// its input; whatever else an Args holds keeps its default or is the launcher's to fill.
+template <class Args>
+Args k2_args(const K2Input& in, int64_t B, int F, const void* blob, float* out, float* latent, uint8_t* valid) {
+  Args a{};
+  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid;
+  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
+  return a;
+}
 // The <VEC4, NORM> kernel instance of an input: calls fn(std::bool_constant<VEC4>{}, std::bool_constant<NORM>{}).
 template <class Fn> void k2_with_variant(const K2Input& in, Fn&& fn) {
   if (in.norm) {

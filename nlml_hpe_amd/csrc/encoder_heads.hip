@@ -667,7 +667,7 @@ __global__ __launch_bounds__(256, 1) void encoder_heads_f32_kernel(EncArgs a) {
           }
       NLML_STAMP(4 + 4 * pass);
     }
-    if (a.valid && a.reeval_over < 0) {  // all-zero feature row == "no face" (FeatureExtractor.py:105-106)
+    if (a.valid && a.reeval_over < 0) {  // write_valid<8> (encoder_heads_common.h) for this thread's TWO rows, both ballots first
       const unsigned long long m0 = __ballot(g.nzbits0 != 0u), m1 = __ballot(g.nzbits1 != 0u);
       if ((tid & 7) == 0) {
         const int sh = c.lane & 56;
@@ -817,21 +817,12 @@ int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int 
                              int64_t B, int F, const void* blob, float* out, float* latent,
                              uint8_t* valid, float* pre_tanh, unsigned long long* stamps, void* stream, int reeval_over) {
   if (B == 0) return 0;
-  EncArgs a;
-  a.reeval_over = reeval_over;
-  a.B = B;
-  a.F = F;
-  a.blob = blob;
-  a.out = out;
-  a.latent = latent;
-  a.valid = valid;
+  const K2Input in = k2_input(x, ldx, raw, normalize, F);
+  EncArgs a = k2_args<EncArgs>(in, B, F, blob, out, latent, valid);
   a.pre_tanh = pre_tanh;
   a.stamps = stamps;
+  a.reeval_over = reeval_over;
   const bool dbg = pre_tanh || stamps;
-  const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  a.x = in.src;
-  a.ldx = in.ld;
-  a.norm = in.norm;
   // 64-face tiles halve the weight stream per face (a 64-face tile takes ~1.9x a 32-face tile, measured), but the
   // launch lasts whole ROUNDS of tiles over the 256 CUs (one tile per CU, LDS-bound): pick the tiling whose
   // rounds x tile time is smaller, so small batches and awkward tile counts (257 tiles = 2 rounds) do not pay for it.

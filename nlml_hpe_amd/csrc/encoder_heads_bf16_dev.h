@@ -13,7 +13,7 @@ namespace nlml {
 namespace bf {   // (stage table, strides and LDS offsets of the bf16 mode: layout.h)
 namespace w8 {
 
-// f32 vector types, ACT_*, activate<ACT> and load_bias<NB, NFB>: encoder_heads_common.h
+// f32 vector types, ACT_*, activate<ACT>, load_bias<NB, NFB> and write_valid<LANES>: encoder_heads_common.h
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 

@@ -22,6 +22,11 @@
 #include "ipd_norm.h"
 #include "layout.h"
 
+// -DBF8_D0=<n>: K steps the weights of layer 0's ring are requested ahead (stage_e0; same bits)
+#ifndef BF8_D0
+#define BF8_D0 3
+#endif
+
 namespace nlml {
 namespace bf {
 namespace w8 {
@@ -121,9 +126,6 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
 
   const int job = jw;
   const bf16x8* w = c.blob8 + c.hdr->w_off[ST_E0] + (size_t)job * c.hdr->job_w16[ST_E0] + (size_t)(4 * nbh) * 64 + c.lane;
-#ifndef BF8_D0
-#define BF8_D0 3
-#endif
   constexpr int R0 = 4, D0 = BF8_D0;   // weight ring: K step ks in slot ks % 4 (a slab holds 4 steps), loaded D0 steps ahead
   static_assert(XS_STEPS == R0, "slab steps == ring slots");
   bf16x8 wr[R0][NB];
@@ -170,10 +172,7 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
     const int t0 = o0;   // rotate: (o0, o1, o2) <- (o1, o2, o0)
     o0 = o1; o1 = o2; o2 = t0;
   }
-  if (a.valid) {  // all-zero feature row == "no face" (FeatureExtractor.py:105-106); 8 lanes share a row
-    const unsigned long long m = __ballot(nzbits != 0u);
-    if ((tid & 7) == 0 && live) a.valid[row0 + srow] = ((m >> (c.lane & 56)) & 0xFFull) ? 1 : 0;
-  }
+  if (a.valid) write_valid<8>(a.valid, nzbits, tid & 7, c.lane, live, row0 + srow);   // 8 lanes share a row
 }
 
 // ------------------------------------------------------------------------------------------
@@ -226,10 +225,8 @@ __global__ __launch_bounds__(512) void encoder_heads_bf16_w8_kernel(Args a) {
 int launch_encoder_heads_bf16(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
                               const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
   if (B == 0) return 0;
-  bf::w8::Args a;
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid;
   const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
+  const bf::w8::Args a = k2_args<bf::w8::Args>(in, B, F, blob, out, latent, valid);
   const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   k2_with_variant(in, [&](auto V, auto N) {

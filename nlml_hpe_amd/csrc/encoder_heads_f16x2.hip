@@ -227,10 +227,7 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
     slab(s, std::integral_constant<int, 0>{});
     slab(s + 1, std::integral_constant<int, 1>{});
   }
-  if (a.valid) {  // all-zero feature row == "no face" (FeatureExtractor.py:105-106); 4 lanes share a row
-    const unsigned long long m = __ballot(nzbits != 0u);
-    if ((tid & 3) == 0 && live) a.valid[row0 + srow] = ((m >> (c.lane & 60)) & 0xFull) ? 1 : 0;
-  }
+  if (a.valid) write_valid<4>(a.valid, nzbits, tid & 3, c.lane, live, row0 + srow);   // 4 lanes share a row
 }
 
 // ------------------------------------------------------------------------------------------
@@ -243,15 +240,7 @@ __global__ __launch_bounds__(256, 1) void encoder_heads_f16x2_kernel(Args a) {
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
 
   const int tid = threadIdx.x;
-  Ctx c;
-  c.blob8 = reinterpret_cast<const h8*>(a.blob);
-  c.blob4 = reinterpret_cast<const f32x4*>(a.blob);
-  c.hdr = load_hdr(reinterpret_cast<const Header*>(a.blob));
-  c.lds = lds;
-  c.lane = tid & 63;
-  c.f = c.lane & 31;
-  c.h = c.lane >> 5;
-  c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const Ctx c = make_ctx(a.blob, lds, tid);
   const int wv = c.wv;
   const int64_t row0 = (int64_t)blockIdx.x * TILE_FACES;
 
@@ -331,10 +320,8 @@ int launch_encoder_heads_f16x2(const float* x, int64_t ldx, const float* raw, in
   if (B == 0) return 0;
   // the strict-fast mode runs on the eight-wave kernel (encoder_heads_f16x2_w8.hip)
   if (split) return launch_encoder_heads_f16x2_w8(x, ldx, raw, normalize, B, F, blob, out, latent, valid, stream);
-  hx::Args a;
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid;
   const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
+  const hx::Args a = k2_args<hx::Args>(in, B, F, blob, out, latent, valid);
   const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   k2_with_variant(in, [&](auto V, auto N) {

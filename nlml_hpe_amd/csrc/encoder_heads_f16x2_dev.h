@@ -1,7 +1,7 @@
 // encoder_heads_f16x2_dev.h -- device helpers of the split-f16 kernels (encoder_heads_f16x2.hip: the fused kernel;
 // encoder_heads_f16x2_small.hip: the layer-per-launch path, whose last launch runs tail_stages() below): operand types,
-// the three-product MFMA steps, the K loops over LDS images, the hi/lo store, and the network's tail (layers E3, E4, E5
-// and the three heads) as one function over a 64-face tile whose E2 output sits in the H3 LDS image.
+// the three-product MFMA steps, the K loops over LDS images, the hi/lo store, a kernel's entry context (Ctx, make_ctx), and the
+// network's tail (layers E3, E4, E5 and the three heads) as one function over a 64-face tile whose E2 output sits in the H3 LDS image.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,7 +14,7 @@
 namespace nlml {
 namespace hx {
 
-// f32 vector types, ACT_*, activate<ACT> and load_bias<NB, NFB>: encoder_heads_common.h
+// f32 vector types, ACT_*, activate<ACT>, load_bias<NB, NFB> and write_valid<LANES>: encoder_heads_common.h
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
@@ -358,6 +358,20 @@ struct Ctx {
   int lane, f, h, wv;
   int helper = 0;   // eight-wave kernel, tail_stages<.., H1W8 = true>: waves 4..7 (wv = wave & 3, helper = 1) stay for the heads' H1 stage
 };
+
+// A kernel's context at its entry: the blob's views and header, the workgroup's LDS, this thread's lane coordinates and its wave (scalar).
+__device__ __forceinline__ Ctx make_ctx(const void* blob, char* lds, int tid) {
+  Ctx c;
+  c.blob8 = reinterpret_cast<const h8*>(blob);
+  c.blob4 = reinterpret_cast<const f32x4*>(blob);
+  c.hdr = load_hdr(reinterpret_cast<const Header*>(blob));
+  c.lds = lds;
+  c.lane = tid & 63;
+  c.f = c.lane & 31;
+  c.h = c.lane >> 5;
+  c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  return c;
+}
 
 }  // namespace hx
 }  // namespace nlml

@@ -33,11 +33,10 @@ using hx::h4;
 using hx::h8;
 constexpr int STEP_UNITS = 2 * 2 * 64;   // h8 units per (tile, K step): 2 face blocks x 2 pieces x 64 lanes = 4 KiB
 
-__device__ __forceinline__ float activate(int act, float v) {
-  if (act == ACT_RELU) return v < 0.0f ? 0.0f : v;
-  if (act == ACT_TANH) return tanhf(v);
-  return v;
-}
+// -DHXS_RS1=<n>: ring depth of the split-throughout layer kernels in the one-wave-per-workgroup launches (tools/README.md)
+#ifndef HXS_RS1
+#define HXS_RS1 8
+#endif
 
 // ---- pre-pass: x (f32 rows, or raw landmarks with optional IPD normalisation) -> hi/lo fragments of layer 0's input.
 // One wave per face; lane handles 8-column chunks c = lane, lane + 64, ... (chunk c = K step c/2, half c&1).
@@ -129,12 +128,9 @@ struct LayerArgs {
   const void* blob;
   const h8* xin;
   h8* xout;
-  int64_t B;
-  int stage, K16, nb_stage, jobs, ntiles, buf_steps, act;
+  int stage, K16, nb_stage, jobs, ntiles, buf_steps;   // every job reads the tile's input from K step 0; job j writes columns 32 * nb_stage * j ..
   int fold_step;      // K step after which the small accumulator is folded into the big one mid-way (layer 1 in NLML_MODE_F16X2S: 32; else 0)
   int split_from;     // first K step whose small products go to the small accumulator (SPLIT kernels; layer 1 in NLML_MODE_F16X2: 32)
-  int in_step0[12];   // first input K step of job j (its input column / 16)
-  int out_col0[12];   // first output column of job j
 };
 
 // R = depth of the operand ring.  With few units (one wave per CU) a unit's rate is its own loads in flight, so those
@@ -161,22 +157,10 @@ __global__ __launch_bounds__(256) void layer_kernel(LayerArgs a) {
   const int st = a.stage, NBS = a.nb_stage, K16 = a.K16;
 
   f32x16 acc[NBW][NFB];
-  {  // bias in accumulator-register order (layout.h), scaled like the weights
-    const f32x4* b = blob4 + hdr->b_off[st] + (size_t)job * (NBS * 8);
-#pragma unroll
-    for (int i = 0; i < NBW; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = b[((nb0 + i) * 2 + h) * 4 + q];
-#pragma unroll
-        for (int fb = 0; fb < NFB; ++fb) {
-          acc[i][fb][4 * q + 0] = v[0]; acc[i][fb][4 * q + 1] = v[1];
-          acc[i][fb][4 * q + 2] = v[2]; acc[i][fb][4 * q + 3] = v[3];
-        }
-      }
-  }
+  // bias in accumulator-register order (layout.h), scaled like the weights
+  load_bias<NBW, NFB>(acc, blob4 + hdr->b_off[st] + (size_t)job * (NBS * 8) + nb0 * 8, h);
   const h8* w = blob8 + hdr->w_off[st] + (size_t)job * hdr->job_w16[st] + (size_t)nb0 * 128 + lane;   // + step*NBS*128
-  const h8* xi = a.xin + ((size_t)tile * a.buf_steps + a.in_step0[job]) * STEP_UNITS + lane;          // + step*256
+  const h8* xi = a.xin + (size_t)tile * a.buf_steps * STEP_UNITS + lane;                              // + step*256
 
   constexpr int D = R - 1;
   h8 wr[R][NBW][2], xr[R][NFB][2];
@@ -281,18 +265,18 @@ __global__ __launch_bounds__(256) void layer_kernel(LayerArgs a) {
 
   fold(false);
   const float inv = hdr->inv_scale[st];
-  // accumulators * inv -> activation -> hi/lo -> the next layer's input fragments
+  // accumulators * inv -> ReLU (the three big layers' activation) -> hi/lo -> the next layer's input fragments
 #pragma unroll
   for (int i = 0; i < NBW; ++i)
 #pragma unroll
     for (int fb = 0; fb < NFB; ++fb)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int n = a.out_col0[job] + 32 * (nb0 + i) + 8 * q + 4 * h;   // this lane's 4 neurons n .. n+3
+        const int n = 32 * NBS * job + 32 * (nb0 + i) + 8 * q + 4 * h;   // this lane's 4 neurons n .. n+3
         h4 hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v = activate(a.act, acc[i][fb][4 * q + e] * inv);
+          const float v = activate<ACT_RELU>(acc[i][fb][4 * q + e] * inv);
           const _Float16 hv = (_Float16)v;
           hi[e] = hv;
           lo[e] = (_Float16)(v - (float)hv);
@@ -307,33 +291,29 @@ __global__ __launch_bounds__(256) void layer_kernel(LayerArgs a) {
 // ---- the network's tail (E3, E4, E5 and the three heads: 8 of the 11 layers, 7 % of the FLOP) as ONE launch: a
 // workgroup per 32-FACE BLOCK copies its half of E2's output fragments into the H3 LDS image and runs the fused
 // kernel's tail_stages() on that block (two workgroups per tile: half the sequential stages of the 64-face form).
+// E2's output of face block fb of a tile (256 columns = 16 K steps; `src`: the tile's fragments) -> the H3 LDS image:
+// fragment (step, fb, piece, lane) -> image row 32*fb + (lane & 31), columns 16*step + 8*(lane >> 5) .. +7 of plane `piece`
+__device__ __forceinline__ void h3_image_from_frags(char* lds, const h8* __restrict__ src, int fb, int tid) {
+  for (int i = tid; i < 16 * 128; i += 256) {
+    const int l = i & 63, piece = (i >> 6) & 1, step = i >> 7;
+    const int face = 32 * fb + (l & 31), k = 16 * step + 8 * (l >> 5);
+    *reinterpret_cast<h8*>(lds + hx::O_H3 + piece * hx::P_H3 + (face * hx::S_H3 + k) * 2) =
+        src[(size_t)step * STEP_UNITS + (fb * 2 + piece) * 64 + l];
+  }
+}
+
 template <int RESCUE_UP_TO>
 __global__ __launch_bounds__(256, 1) void tail_kernel(hx::Args a, const h8* __restrict__ xin, int buf_steps) {
   __shared__ __attribute__((aligned(16))) char lds[hx::LDS_BYTES];
   const int tid = threadIdx.x;
-  hx::Ctx c;
-  c.blob8 = reinterpret_cast<const h8*>(a.blob);
-  c.blob4 = reinterpret_cast<const f32x4*>(a.blob);
-  c.hdr = hx::load_hdr(reinterpret_cast<const Header*>(a.blob));
-  c.lds = lds;
-  c.lane = tid & 63;
-  c.f = c.lane & 31;
-  c.h = c.lane >> 5;
-  c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const hx::Ctx c = hx::make_ctx(a.blob, lds, tid);
   const int64_t tile = blockIdx.x >> 1, row0 = tile * TILE_FACES;
   const int fbsel = blockIdx.x & 1;
   if (row0 + 32 * fbsel >= a.B) return;                       // no live face in this block (whole workgroup leaves)
   f32x16 acc3[1][1];
   h8 wr3[hx::ring_slots(1, 1)][1][2];
   hx::tail_pre_e3<true>(c, acc3, wr3);                        // E3's bias and first weights fly while the image is copied
-  // fragment (step, fb, piece, lane) -> image row 32*fb + (lane & 31), columns 16*step + 8*(lane >> 5) .. +7 of plane `piece`
-  const h8* src = xin + (size_t)tile * buf_steps * STEP_UNITS;
-  for (int i = tid; i < 16 * 128; i += 256) {                 // E2's output: 256 columns = 16 K steps, this face block
-    const int l = i & 63, piece = (i >> 6) & 1, step = i >> 7;
-    const int face = 32 * fbsel + (l & 31), k = 16 * step + 8 * (l >> 5);
-    *reinterpret_cast<h8*>(lds + hx::O_H3 + piece * hx::P_H3 + (face * hx::S_H3 + k) * 2) =
-        src[(size_t)step * STEP_UNITS + (fbsel * 2 + piece) * 64 + l];
-  }
+  h3_image_from_frags(lds, xin + (size_t)tile * buf_steps * STEP_UNITS, fbsel, tid);
   __syncthreads();
   hx::tail_stages<true, RESCUE_UP_TO>(c, a, row0, acc3, wr3, fbsel);
 }
@@ -349,18 +329,24 @@ namespace hx {
 constexpr int LAT_ROW_BYTES = S_LAT * 2, LAT_BLOCK_BYTES = 32 * LAT_ROW_BYTES;   // one plane of one face block: 3,584 B
 static_assert(LAT_ROW_BYTES % 16 == 0 && O_LAT % 16 == 0 && P_LAT % 16 == 0, "16-byte copies of the latent image");
 
+// the rows of face block fb of a tile in the latent image, both planes: LDS -> workspace (TO_WS) or workspace -> LDS
+template <bool TO_WS>
+__device__ __forceinline__ void latent_block_copy(char* lds, std::conditional_t<TO_WS, char, const char>* latws, int64_t tile, int fb, int tid) {
+  typedef unsigned u4 __attribute__((ext_vector_type(4)));
+  auto* ws = latws + ((size_t)tile * 2 + fb) * (2 * LAT_BLOCK_BYTES);
+  for (int i = tid; i < 2 * LAT_BLOCK_BYTES / 16; i += 256) {
+    const int piece = i / (LAT_BLOCK_BYTES / 16), o = (i % (LAT_BLOCK_BYTES / 16)) * 16;
+    char* l = lds + O_LAT + piece * P_LAT + 32 * fb * LAT_ROW_BYTES + o;
+    auto* w = ws + piece * LAT_BLOCK_BYTES + o;
+    if constexpr (TO_WS) *reinterpret_cast<u4*>(w) = *reinterpret_cast<const u4*>(l);
+    else *reinterpret_cast<u4*>(l) = *reinterpret_cast<const u4*>(w);
+  }
+}
+
 __global__ __launch_bounds__(256, 1) void tail_encoder_kernel(Args a, const h8* __restrict__ xin, int buf_steps, char* __restrict__ latws) {
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
   const int tid = threadIdx.x;
-  Ctx c;
-  c.blob8 = reinterpret_cast<const h8*>(a.blob);
-  c.blob4 = reinterpret_cast<const f32x4*>(a.blob);
-  c.hdr = load_hdr(reinterpret_cast<const Header*>(a.blob));
-  c.lds = lds;
-  c.lane = tid & 63;
-  c.f = c.lane & 31;
-  c.h = c.lane >> 5;
-  c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const Ctx c = make_ctx(a.blob, lds, tid);
   const int wv = c.wv;
   const int64_t tile = blockIdx.x >> 1, row0 = tile * TILE_FACES;
   const int fb = blockIdx.x & 1, face0 = 32 * fb;
@@ -368,12 +354,7 @@ __global__ __launch_bounds__(256, 1) void tail_encoder_kernel(Args a, const h8* 
   f32x16 acc3[1][1];
   h8 wr3[ring_slots(1, 1)][1][2];
   tail_pre_e3<true>(c, acc3, wr3);                            // E3's bias and first weights fly while the image is copied
-  const h8* src = xin + (size_t)tile * buf_steps * hxs::STEP_UNITS;
-  for (int i = tid; i < 16 * 128; i += 256) {                 // E2's output: 256 columns = 16 K steps, this face block
-    const int l = i & 63, piece = (i >> 6) & 1, step = i >> 7;
-    const int face = face0 + (l & 31), k = 16 * step + 8 * (l >> 5);
-    *reinterpret_cast<h8*>(lds + O_H3 + piece * P_H3 + (face * S_H3 + k) * 2) = src[(size_t)step * hxs::STEP_UNITS + (fb * 2 + piece) * 64 + l];
-  }
+  hxs::h3_image_from_frags(lds, xin + (size_t)tile * buf_steps * hxs::STEP_UNITS, fb, tid);
   __syncthreads();
   const bool do4 = wv < 2, do5 = wv == 0;                     // E4: neuron block wv (waves 0, 1); E5: wave 0
   f32x16 acc4[1][1], acc5[2][1];
@@ -403,27 +384,13 @@ __global__ __launch_bounds__(256, 1) void tail_encoder_kernel(Args a, const h8* 
     job_store<2, 1, ACT_NONE, S_LAT>(c, acc5, O_LAT, P_LAT, S_LAT, 0, face0, inv);
   }
   __syncthreads();
-  // the face block's rows of the latent image, both planes, to the workspace
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  char* dst = latws + ((size_t)tile * 2 + fb) * (2 * LAT_BLOCK_BYTES);
-  for (int i = tid; i < 2 * LAT_BLOCK_BYTES / 16; i += 256) {
-    const int piece = i / (LAT_BLOCK_BYTES / 16), o = (i % (LAT_BLOCK_BYTES / 16)) * 16;
-    *reinterpret_cast<u4*>(dst + piece * LAT_BLOCK_BYTES + o) = *reinterpret_cast<const u4*>(lds + O_LAT + piece * P_LAT + face0 * LAT_ROW_BYTES + o);
-  }
+  latent_block_copy<true>(lds, latws, tile, fb, tid);
 }
 
 __global__ __launch_bounds__(256, 1) void head_kernel(Args a, const char* __restrict__ latws) {
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
   const int tid = threadIdx.x;
-  Ctx cl;
-  cl.blob8 = reinterpret_cast<const h8*>(a.blob);
-  cl.blob4 = reinterpret_cast<const f32x4*>(a.blob);
-  cl.hdr = load_hdr(reinterpret_cast<const Header*>(a.blob));
-  cl.lds = lds;
-  cl.lane = tid & 63;
-  cl.f = cl.lane & 31;
-  cl.h = cl.lane >> 5;
-  cl.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const Ctx cl = make_ctx(a.blob, lds, tid);
   const int wv = cl.wv;
   const int g = blockIdx.x % 3, fb = (blockIdx.x / 3) & 1, face0 = 32 * fb;
   const int64_t tile = blockIdx.x / 6, row0 = tile * TILE_FACES;
@@ -432,12 +399,7 @@ __global__ __launch_bounds__(256, 1) void head_kernel(Args a, const char* __rest
   f32x16 acc0[1][1], acc1[2][1], acc2[1][1], acc3[1][1], acc4[1][1];
   h8 wr0[6][1][2], wr1[6][2][2], wr2[6][1][2], wr3[6][1][2], wr4[6][1][2];
   job_pre<1, 1, ST_H0>(cl, job, acc0, wr0);                   // H0's operands fly while the latent image is copied in
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  const char* src = latws + ((size_t)tile * 2 + fb) * (2 * LAT_BLOCK_BYTES);
-  for (int i = tid; i < 2 * LAT_BLOCK_BYTES / 16; i += 256) {
-    const int piece = i / (LAT_BLOCK_BYTES / 16), o = (i % (LAT_BLOCK_BYTES / 16)) * 16;
-    *reinterpret_cast<u4*>(lds + O_LAT + piece * P_LAT + face0 * LAT_ROW_BYTES + o) = *reinterpret_cast<const u4*>(src + piece * LAT_BLOCK_BYTES + o);
-  }
+  latent_block_copy<false>(lds, latws, tile, fb, tid);
   __syncthreads();
   // H0_g: 3 -> 128 (K padded to 16), ReLU; wave = neuron block
   job_run<1, 1, ST_H0>(cl, job, acc0, wr0, O_LAT, P_LAT, S_LAT, 16 * g, face0);
@@ -467,6 +429,15 @@ __global__ __launch_bounds__(256, 1) void head_kernel(Args a, const char* __rest
 }  // namespace hx
 namespace hxs {
 static int e0_k16(int F) { return (F + 2 * hx::XS_COLS - 1) / (2 * hx::XS_COLS) * (2 * hx::XS_STEPS); }   // as pack.cpp
+
+// A layer's launch with NB blocks per wave: the kernel without a second accumulator set (ring R), split throughout (ring RS), or split
+// from a.split_from on (ring R)
+template <int NB, int R, int RS, int NFB = 2>
+static void launch_layer(const LayerArgs& a, bool use_split, dim3 grid, dim3 block, hipStream_t st) {
+  if (!use_split) hipLaunchKernelGGL((layer_kernel<NB, R, 0, NFB>), grid, block, 0, st, a);
+  else if (a.split_from == 0) hipLaunchKernelGGL((layer_kernel<NB, RS, 1, NFB>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((layer_kernel<NB, R, 2, NFB>), grid, block, 0, st, a);
+}
 
 }  // namespace hxs
 
@@ -506,8 +477,8 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
   h8* outb = bufB;
   for (int s = 0; s < 3; ++s) {
     LayerArgs a{};
-    a.blob = blob; a.xin = in; a.xout = outb; a.B = B; a.stage = stages[s].stage; a.K16 = stages[s].K16;
-    a.nb_stage = stages[s].nb; a.jobs = stages[s].jobs; a.ntiles = ntiles; a.buf_steps = buf_steps; a.act = ACT_RELU;
+    a.blob = blob; a.xin = in; a.xout = outb; a.stage = stages[s].stage; a.K16 = stages[s].K16;
+    a.nb_stage = stages[s].nb; a.jobs = stages[s].jobs; a.ntiles = ntiles; a.buf_steps = buf_steps;
     // which K steps run on split accumulators, exactly as the fused kernel of the blob's mode (encoder_heads_f16x2.hip):
     //   NLML_MODE_F16X2S: all of layers 0, 1, 2, layer 1's small sums added at its K midpoint as well as at its end;
     //   NLML_MODE_F16X2:  layer 1 from its K midpoint on, layer 2; layer 0 never (kernel without the second set)
@@ -515,19 +486,6 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
     const bool use_split = split || !e0;
     a.fold_step = (split && e1) ? 32 : 0;     // (like split_from a multiple of the split kernels' ring depths, 4 and 8)
     a.split_from = (!split && e1) ? 32 : 0;   // (a multiple of every ring depth the split kernels are launched with: 4 and 8)
-    for (int j = 0; j < a.jobs; ++j) {
-      a.in_step0[j] = 0;
-      a.out_col0[j] = 32 * a.nb_stage * j;
-    }
-#ifndef HXS_RS1
-#define HXS_RS1 8
-#endif
-#define NLML_HXS_LAUNCH(NB, R, RS)                                                                   \
-  do {                                                                                               \
-    if (!use_split) hipLaunchKernelGGL((layer_kernel<NB, R, 0>), grid, block, 0, st, a);             \
-    else if (a.split_from == 0) hipLaunchKernelGGL((layer_kernel<NB, RS, 1>), grid, block, 0, st, a); \
-    else hipLaunchKernelGGL((layer_kernel<NB, R, 2>), grid, block, 0, st, a);                        \
-  } while (0)
     // blocks per wave: as many as still leave enough waves to keep the weight loads of every CU in flight
     int nbw = a.nb_stage;
     if (use_split && nbw > 2) nbw = 2;    // two accumulator sets per block: four blocks per wave would not fit the register file
@@ -536,27 +494,23 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
     const int64_t units = (int64_t)ntiles * a.jobs * (a.nb_stage / nbw);
     if (nbw == 1 && units <= 256) {   // (wider thresholds, 512 .. 4,096 units, measured: no change)   // at most one wave per CU even so: one unit per (.., face block), see layer_kernel
       const dim3 grid((unsigned)(2 * units)), block(64);
-      if (!use_split) hipLaunchKernelGGL((layer_kernel<1, 8, 0, 1>), grid, block, 0, st, a);
-      else if (a.split_from == 0) hipLaunchKernelGGL((layer_kernel<1, HXS_RS1, 1, 1>), grid, block, 0, st, a);
-      else hipLaunchKernelGGL((layer_kernel<1, 8, 2, 1>), grid, block, 0, st, a);
+      launch_layer<1, 8, HXS_RS1, 1>(a, use_split, grid, block, st);
     } else if (units < 1024) {   // fewer than four waves per CU: one wave per workgroup, deep ring
       const dim3 grid((unsigned)units), block(64);
       if (nbw == 4) hipLaunchKernelGGL((layer_kernel<4, 6, 0>), grid, block, 0, st, a);   // (four blocks per wave: layer 0 without a second set only)
-      else if (nbw == 2) NLML_HXS_LAUNCH(2, 8, HXS_RS1);
-      else NLML_HXS_LAUNCH(1, 8, HXS_RS1);
+      else if (nbw == 2) launch_layer<2, 8, HXS_RS1>(a, use_split, grid, block, st);
+      else launch_layer<1, 8, HXS_RS1>(a, use_split, grid, block, st);
     } else {
       const dim3 grid((unsigned)((units + 3) / 4)), block(256);
       if (nbw == 4) hipLaunchKernelGGL((layer_kernel<4, 4, 0>), grid, block, 0, st, a);
-      else if (nbw == 2) NLML_HXS_LAUNCH(2, 4, 4);
-      else NLML_HXS_LAUNCH(1, 4, 4);
+      else if (nbw == 2) launch_layer<2, 4, 4>(a, use_split, grid, block, st);
+      else launch_layer<1, 4, 4>(a, use_split, grid, block, st);
     }
-#undef NLML_HXS_LAUNCH
     h8* t = in; in = outb; outb = t;
   }
   {
-    hx::Args ta{};
-    ta.B = B; ta.F = F; ta.blob = blob; ta.out = out; ta.latent = latent; ta.valid = nullptr;
-    ta.x = rows.src; ta.ldx = rows.ld; ta.norm = rows.norm;   // the tail's slow path re-reads the face's input
+    // (no mask: the pre-pass wrote it; x: the tail's slow path re-reads the face's input)
+    const hx::Args ta = k2_args<hx::Args>(rows, B, F, blob, out, latent, nullptr);
     if (split) {   // E3..E5, then the three heads as workgroups of their own; the latent image passes through the free buffer
       hipLaunchKernelGGL(hx::tail_encoder_kernel, dim3((unsigned)(2 * ntiles)), dim3(256), 0, st, ta, (const h8*)in, buf_steps, reinterpret_cast<char*>(outb));
       hipLaunchKernelGGL(hx::head_kernel, dim3((unsigned)(6 * ntiles)), dim3(256), 0, st, ta, reinterpret_cast<const char*>(outb));

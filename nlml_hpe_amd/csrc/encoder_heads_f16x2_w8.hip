@@ -24,6 +24,14 @@
 #include "encoder_heads_f16x2_dev.h"
 #include "layout.h"
 
+// -DW8_D0_HI=<n> / -DW8_D0_LO=<n>: K steps the hi / lo weight pieces of layer 0's ring are requested ahead (stage_e0_pass_w8; same bits)
+#ifndef W8_D0_HI
+#define W8_D0_HI 2
+#endif
+#ifndef W8_D0_LO
+#define W8_D0_LO 2
+#endif
+
 namespace nlml {
 namespace hx {
 
@@ -157,12 +165,6 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   // ahead) fit the register budget since step_w8 single-buffers the lo operands, but need the loop unrolled by two for static set
   // indices, and hipcc's allocation of that 96-MFMA body spills 166 registers, 30 reloads inside the loop: 1.25 ms against 0.84 (measured).
   Set set[2];
-#ifndef W8_D0_HI
-#define W8_D0_HI 2
-#endif
-#ifndef W8_D0_LO
-#define W8_D0_LO 2
-#endif
   // weight ring: K step ks in slot ks % 4 = its step within the iteration, its hi / lo pieces requested DH / DL steps ahead
   constexpr int R0 = 4, DH = W8_D0_HI, DL = W8_D0_LO;
   h8 wr[R0][NB][2];
@@ -235,10 +237,7 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
     }
     const int t0 = cur; cur = nxt; nxt = t0;
   }
-  if (pass == 0 && a.valid) {  // all-zero feature row == "no face" (FeatureExtractor.py:105-106); 8 lanes share a row
-    const unsigned long long m = __ballot(nzbits != 0u);
-    if ((tid & 7) == 0 && live) a.valid[row0 + srow] = ((m >> (c.lane & 56)) & 0xFFull) ? 1 : 0;
-  }
+  if (pass == 0 && a.valid) write_valid<8>(a.valid, nzbits, tid & 7, c.lane, live, row0 + srow);   // 8 lanes share a row
 }
 
 // Timing-only diagnostic build (-DHX_STAMPS, tools/w8_stage_shares.py): per-wave s_memtime stamps at the trunk's stage boundaries into
@@ -267,7 +266,7 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
 
   const int tid = threadIdx.x;
-  Ctx c;
+  Ctx c;   // make_ctx(a.blob, lds, tid) written out: through the call this kernel's prologue is scheduled differently (profiles/k2_scaffold_ab.md)
   c.blob8 = reinterpret_cast<const h8*>(a.blob);
   c.blob4 = reinterpret_cast<const f32x4*>(a.blob);
   c.hdr = load_hdr(reinterpret_cast<const Header*>(a.blob));
@@ -403,10 +402,9 @@ int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* 
   if (B == 0) return 0;
   if (!workspace || ws_bytes < tailws_workspace_bytes(B, F)) return fail(NLML_E_BADARG, "streamed-tail path: workspace too small");
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(NLML_E_BADARG, "streamed-tail path: workspace must be 16-byte aligned");
-  hx::Args a;
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid; a.h3ws = workspace;
   const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
+  hx::Args a = k2_args<hx::Args>(in, B, F, blob, out, latent, valid);
+  a.h3ws = workspace;
   if (!in.vec4) return fail(NLML_E_BADARG, "streamed-tail path: x must be 16-byte aligned with F and ldx multiples of 4");
   const int64_t ntiles = (B + TILE_FACES - 1) / TILE_FACES;
   const dim3 grid((unsigned)ntiles), block(512);
@@ -421,10 +419,8 @@ int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* 
 int launch_encoder_heads_f16x2_w8(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
                                   const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
   if (B == 0) return 0;
-  hx::Args a;
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid;
   const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
+  const hx::Args a = k2_args<hx::Args>(in, B, F, blob, out, latent, valid);
   const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   k2_with_variant(in, [&](auto V, auto N) {

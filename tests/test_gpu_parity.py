@@ -406,6 +406,20 @@ def test_fused_valid_mask_edge_cases(head_sds, device):
     assert not ref_valid[3] and not ref_valid[64] and not ref_valid[130] and ref_valid.sum() == 128
     assert np.array_equal(v1.cpu().numpy(), ref_valid) and np.array_equal(v2.cpu().numpy(), ref_valid)
     assert torch.equal(pose, ops.encoder_heads_fwd(feats, blob, 1404))
+    # every fused kernel, with "no face" rows also at the first and the last lane group of a wave: the staging threads of a row are
+    # 8 consecutive lanes (rows 0, 7 | 8, 15 of waves 0 | 1) or 4 (rows 0, 15 | 16, 63 of waves 0 | 1, 3), and the mask of a row is
+    # cut out of the wave's ballot by the row's lane group
+    from nlml_hpe_amd import _lib
+    raw[[0, 7, 8, 15, 16, 63]] = 0.0
+    rt = torch.from_numpy(raw).to(device)
+    feats = ops.normalize_ipd(rt, True)
+    ref_valid = ~FN.no_face_mask(FN.normalize_ipd(raw, True))
+    assert not ref_valid[[0, 3, 7, 8, 15, 16, 63, 64, 130]].any() and ref_valid.sum() == 122
+    for mode_name in ("bf16", "f16x2s", "f16x2", "f32"):
+        mblob = torch.from_numpy(weights.pack_blob(sd, head_sds, _lib.mode_from_name(mode_name))).to(device)
+        pose, v = ops.landmarks_to_pose(rt, mblob, True, return_valid=True)
+        assert np.array_equal(v.cpu().numpy(), ref_valid), mode_name
+        assert torch.equal(pose, ops.encoder_heads_fwd(feats, mblob, 1404)), mode_name
 
 
 def test_full_batch_65536_properties(head_sds, device):
@@ -516,6 +530,18 @@ def test_bf16_fused_landmarks(head_sds, device):
     assert not bool(valid[11]) and int(valid.sum()) == 199
     ref = EH.forward_numpy(FN.normalize_ipd(raw, True), EH.Params(sd, head_sds), np.float64)
     assert np.degrees(np.abs(fused.cpu().numpy() - ref).max()) <= 0.5
+    # the 131 faces of test_fused_valid_mask_edge_cases (coinciding landmarks, a zero row at a tile's start, the last row of a
+    # partial tile): the mask against the oracle's
+    raw = synth.raw_landmarks(131, seed=17)
+    raw[3] = np.array([0.25, 0.5, 0.75], np.float32)
+    raw[64] = 0.0
+    raw[130] = np.array([0.1, 0.1, 0.1], np.float32)
+    rt = torch.from_numpy(raw).to(device)
+    fused, valid = ops.landmarks_to_pose(rt, blob, True, return_valid=True)
+    ref_valid = ~FN.no_face_mask(FN.normalize_ipd(raw, True))
+    assert not ref_valid[3] and not ref_valid[64] and not ref_valid[130] and ref_valid.sum() == 128
+    assert np.array_equal(valid.cpu().numpy(), ref_valid)
+    assert torch.equal(fused, ops.encoder_heads_fwd(ops.normalize_ipd(rt, True), blob, 1404))
 
 
 @pytest.mark.parametrize("mode_name", ["bf16", "f16x2s", "f16x2", "f32"])
@@ -928,12 +954,17 @@ def test_small_batch_path_landmarks_workspace_and_errors(hx, head_sds, device):
     raw = synth.raw_landmarks(131, seed=17)
     raw[3] = np.array([0.25, 0.5, 0.75], np.float32)
     raw[64] = 0.0
+    raw[130] = np.array([0.1, 0.1, 0.1], np.float32)
+    raw[[0, 7, 8, 15, 16, 63]] = 0.0    # the first and the last lane group of a wave in the fused kernels' mask (test_fused_valid_mask_edge_cases)
     rt = torch.from_numpy(raw).to(device)
     a, va = ops.landmarks_to_pose(rt, blob, True, return_valid=True)
     need = _lib.lib().nlml_encoder_heads_small_workspace_bytes(131, 1404)
     ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=device)          # every f16 in it is a NaN
     b, vb = ops.landmarks_to_pose_small(rt, blob, True, return_valid=True, workspace=ws)
     assert torch.equal(a, b) and torch.equal(va, vb)
+    ref_valid = ~FN.no_face_mask(FN.normalize_ipd(raw, True))
+    assert not ref_valid[[0, 3, 7, 8, 15, 16, 63, 64, 130]].any() and ref_valid.sum() == 122
+    assert np.array_equal(vb.cpu().numpy(), ref_valid)
     c = ops.landmarks_to_pose_small(rt, blob, False, workspace=ws)
     assert torch.equal(c, ops.landmarks_to_pose(rt, blob, False))
     with pytest.raises(_lib.NlmlError):
