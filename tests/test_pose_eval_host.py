@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from nlml_hpe_amd import _lib, ops  # noqa: F401  (ops registers torch.ops.nlml_hpe.*)
+from pose_eval_cases import chan as _chan, part as _part
 
 BADARG = -1
 FAKE = 4096       # an aligned non-null "device" pointer: every call below is refused before it could be used
@@ -96,23 +97,6 @@ def test_ops_refuse_cpu_tensors_and_bad_shapes():
         ops.pose_eval(torch.zeros((4, 3)), torch.zeros((4, 3), dtype=torch.float64))
     with pytest.raises(_lib.NlmlError):
         ops.pose_eval_merge(torch.zeros((2, 48), dtype=torch.float64), 18)
-
-
-def _chan(a, b):
-    """(n, mean, M2) merge, as the kernel's merge launch does it: an empty side leaves the other as it is."""
-    na, ma, Ma = a
-    nb, mb, Mb = b
-    if nb == 0:
-        return a
-    if na == 0:
-        return b
-    n = na + nb
-    d = mb - ma
-    return n, ma + d * (nb / n), Ma + Mb + d * d * (na * (nb / n))
-
-
-def _part(x):
-    return (len(x), float(x.mean()) if len(x) else 0.0, float(((x - x.mean()) ** 2).sum()) if len(x) else 0.0)
 
 
 @pytest.mark.parametrize("cuts", [(0, 1, 7, 7, 500, 999), (0, 0, 1000), (3, 3, 3, 998), (1000,), (250, 500, 750)])

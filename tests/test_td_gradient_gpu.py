@@ -22,30 +22,85 @@ def _dev_gradient(W, X, P, cp, device, x_index=None):
     return err.cpu().numpy(), grad.cpu().numpy()
 
 
+N_WIDE = 130                       # two full 64-evaluation workgroups of the second launch and a partial third
+WIDE_RANKS = (1, 5, 16)
+
+
 @pytest.fixture(scope="module")
-def host17(tucker_art):
-    """Per rank: 17 draws and the host restatement's (err, grad) on them -- computed once, shared by the size cases."""
+def host_draws(tucker_art):
+    """Per rank: the draws and the host restatement's (err, grad) on them -- computed once, sliced by the size cases.  130 draws for
+    the ranks 1, 5 and 16, 17 for the others."""
     out = {}
     cp = GC.cos_block(tucker_art)
     for R in (1, 3, 5, 8, 16):
-        W, P, X = GC.draws(tucker_art, R, 17)
+        W, P, X = GC.draws(tucker_art, R, N_WIDE if R in WIDE_RANKS else 17)
         out[R] = (W, P, X) + GC.gradient_host(W, X, P, cp)
     return out
 
 
 @pytest.mark.parametrize("R", [1, 3, 5, 8, 16])
 @pytest.mark.parametrize("N", [1, 2, 3, 8, 9, 17])
-def test_device_gradient_is_the_host_restatement_bit_for_bit(N, R, host17, tucker_art, device):
+def test_device_gradient_is_the_host_restatement_bit_for_bit(N, R, host_draws, tucker_art, device):
     """N crosses the pass grouping: one and two gradients per pass, a partial last workgroup, more than one workgroup."""
-    W, P, X, e_h, g_h = host17[R]
+    W, P, X, e_h, g_h = host_draws[R]
     err, grad = _dev_gradient(W, X[:N], P[:N], GC.cos_block(tucker_art), device)
     print(f"N={N} R={R}: err mismatches {int((err != e_h[:N]).sum())}, gradient mismatches {int((grad != g_h[:N]).sum())} of {grad.size}")
     assert np.array_equal(err, e_h[:N])
     assert np.array_equal(grad, g_h[:N])
 
 
-def test_device_gradient_with_shared_rows_and_a_padded_stride(host17, tucker_art, device):
-    W, P, X, _, _ = host17[5]
+@pytest.mark.parametrize("R", WIDE_RANKS)
+@pytest.mark.parametrize("N", [63, 64, 65, 128, N_WIDE])
+def test_device_gradient_past_one_workgroup_of_the_second_launch(N, R, host_draws, tucker_art, device):
+    """The second launch takes 64 evaluations per workgroup and reads t transposed with a row stride of N: one lane short of a full
+    workgroup, a full one, one evaluation into the second, two full ones, a partial third."""
+    W, P, X, e_h, g_h = host_draws[R]
+    err, grad = _dev_gradient(W, X[:N], P[:N], GC.cos_block(tucker_art), device)
+    print(f"N={N} R={R}: err mismatches {int((err != e_h[:N]).sum())}, gradient mismatches {int((grad != g_h[:N]).sum())} of {grad.size}")
+    assert np.array_equal(err, e_h[:N])
+    assert np.array_equal(grad, g_h[:N])
+
+
+@pytest.mark.parametrize("R", WIDE_RANKS)
+def test_wide_batch_with_shared_rows_without_err_and_through_a_used_workspace(R, host_draws, tucker_art, device):
+    W, P, X, e_h, g_h = host_draws[R]
+    cp = GC.cos_block(tucker_art)
+    N = N_WIDE
+    # x_index over 7 shared rows
+    idx = (np.arange(N) * 5 % 7).astype(np.int32)
+    e_i, g_i = GC.gradient_host(W, X[:7], P, cp, x_index=idx)
+    err, grad = _dev_gradient(W, X[:7], P, cp, device, x_index=idx)
+    assert np.array_equal(err, e_i) and np.array_equal(grad, g_i)
+    assert not np.array_equal(g_i, g_h)                                       # the index is used: other faces, another gradient
+    # the gradient alone
+    Wm, Xd = torch.from_numpy(W.reshape(-1, 1404)).to(device), torch.from_numpy(X).to(device)
+    Pd, cpd = torch.from_numpy(P).to(device), torch.from_numpy(cp).to(device)
+    g_only = ops.tucker_gradient(Wm, Xd, Pd, cpd, return_err=False)
+    assert np.array_equal(g_only.cpu().numpy(), g_h)
+    # the C ABI on a workspace filled with NaN, then on the same workspace as another call (the shared rows) left it
+    L = _lib.lib()
+    nb = L.nlml_tucker_gradient_workspace_bytes(N, R)
+    ws = torch.full((nb // 8,), float("nan"), dtype=torch.float64, device=device)
+    X7, idx_d = torch.from_numpy(X[:7].copy()).to(device), torch.from_numpy(idx).to(device)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(x, xi):
+        e = torch.full((N,), float("nan"), dtype=torch.float64, device=device)
+        g = torch.full((N, 3 + R), float("nan"), dtype=torch.float64, device=device)
+        _lib.check(L.nlml_tucker_gradient_r(Wm.data_ptr(), x.data_ptr(), 1404, None if xi is None else xi.data_ptr(), Pd.data_ptr(),
+                                            cpd.data_ptr(), N, e.data_ptr(), g.data_ptr(), R, ws.data_ptr(), nb, stream), "gradient")
+        torch.cuda.synchronize()
+        return e.cpu().numpy(), g.cpu().numpy()
+    e1, g1 = run(Xd, None)                                                     # workspace: NaN
+    e2, g2 = run(X7, idx_d)                                                    # a different call
+    e3, g3 = run(Xd, None)                                                     # workspace: that call's contents
+    assert np.array_equal(e1, e_h) and np.array_equal(g1, g_h)
+    assert np.array_equal(e2, e_i) and np.array_equal(g2, g_i)
+    assert np.array_equal(e3, e_h) and np.array_equal(g3, g_h)
+
+
+def test_device_gradient_with_shared_rows_and_a_padded_stride(host_draws, tucker_art, device):
+    W, P, X, _, _ = host_draws[5]
     cp = GC.cos_block(tucker_art)
     idx = np.array([2, 2, 0, 1, 1, 1, 2, 0, 0], np.int32)
     e_h, g_h = GC.gradient_host(W, X[:3], P[:9], cp, x_index=idx)
@@ -66,8 +121,8 @@ def test_device_gradient_with_shared_rows_and_a_padded_stride(host17, tucker_art
     assert np.array_equal(e2.cpu().numpy(), e_h9) and np.array_equal(g2.cpu().numpy(), g_h9)
 
 
-def test_err_is_the_reference_order_objective(host17, tucker_art, device):
-    W, P, X, _, _ = host17[8]
+def test_err_is_the_reference_order_objective(host_draws, tucker_art, device):
+    W, P, X, _, _ = host_draws[8]
     cp = GC.cos_block(tucker_art)
     err, _ = _dev_gradient(W, X, P, cp, device)
     want = ops.tucker_objective(torch.from_numpy(W.reshape(-1, 1404)).to(device), torch.from_numpy(X).to(device),
@@ -90,9 +145,9 @@ def test_device_gradient_is_fx10_bit_for_bit(R, tucker_art, golden_dir, device):
     assert np.array_equal(grad[:, 3:], g[:, 3:])
 
 
-def test_every_public_form_returns_the_same_bits(host17, tucker_art, device):
+def test_every_public_form_returns_the_same_bits(host_draws, tucker_art, device):
     from nlml_hpe_amd import TD_Tester as HT
-    W, P, X, e_h, g_h = host17[3]
+    W, P, X, e_h, g_h = host_draws[3]
     Py, Pp, Pr = RF.cos_rows(tucker_art)
     assert np.array_equal(HT.compute_gradient_batch(P, W, X, Py, Pp, Pr, impl="native"), g_h)
     e, g = HT.value_and_gradient_batch(P, W, X, Py, Pp, Pr)
