@@ -5,9 +5,8 @@
 //                                            then / 468.0
 //   d = a - centroid;  q = d ** 2            each product rounded on its own
 //   n = np.sum(q, axis=1)                    (q0 + q1) + q2
-//   m = np.mean(n)                           numpy's pairwise sum over 468 elements, then / 468.0:
-//                                            468 -> 232 + 236 -> (112 + 120) + (112 + 124); a leaf: eight accumulators seeded from its
-//                                            first eight elements, stride 8, ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)), remainder in sequence
+//   m = np.mean(n)                           numpy's pairwise sum over 468 elements (np_sum.h: four leaves, (112 + 120) + (112 + 124)),
+//                                            then / 468.0
 //   out = f32(d / sqrt(m))                   IEEE f64 square root and divide, one rounding to f32 (:101)
 //
 // Nothing here may be contracted into an fma: the functions that multiply switch contraction off.
@@ -16,6 +15,8 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "np_sum.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define NLML_CN_HD __host__ __device__
@@ -26,36 +27,9 @@
 namespace nlml {
 
 constexpr int CN_LM = 468;       // landmarks per face
-constexpr int CN_LEAVES = 4;     // leaves of numpy's pairwise tree for 468 elements
-
-// numpy's pairwise sum splits a range of more than 128 elements at n/2 rounded down to a multiple of 8
-constexpr int cn_split(int n) { return n / 2 - (n / 2) % 8; }
-// first element of leaf 0..3 (4: one past the last); constexpr functions, so device code may index them at run time
-constexpr int cn_leaf_off(int leaf) {
-  return leaf == 0 ? 0
-       : leaf == 1 ? cn_split(cn_split(CN_LM))
-       : leaf == 2 ? cn_split(CN_LM)
-       : leaf == 3 ? cn_split(CN_LM) + cn_split(CN_LM - cn_split(CN_LM))
-                   : CN_LM;
-}
-constexpr int cn_leaf_len(int leaf) { return cn_leaf_off(leaf + 1) - cn_leaf_off(leaf); }
-static_assert(cn_leaf_off(1) == 112 && cn_leaf_off(2) == 232 && cn_leaf_off(3) == 344, "468 -> (112 + 120) + (112 + 124)");
-static_assert(cn_leaf_len(0) == 112 && cn_leaf_len(1) == 120 && cn_leaf_len(2) == 112 && cn_leaf_len(3) == 124, "leaf lengths");
-static_assert(cn_split(CN_LM) > 128 && CN_LM - cn_split(CN_LM) > 128, "both halves split once more");
-static_assert(cn_leaf_len(1) <= 128 && cn_leaf_len(3) <= 128 && cn_leaf_len(0) >= 8, "a leaf: 8..128 elements, not split further");
-
-// one leaf of numpy's pairwise sum, 8 <= n <= 128
-NLML_CN_HD inline double cn_pairwise_leaf(const double* a, int n) {
-  double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-    r0 += a[i + 0]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
-    r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-  }
-  double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
+typedef NpTree<CN_LM> CnTree;    // numpy's pairwise tree for 468 elements (np_sum.h): 4 leaves, (112 + 120) + (112 + 124)
+constexpr int CN_LEAVES = CnTree::leaves;
+static_assert(CnTree::balanced, "np_tree_sum adds the leaves as a balanced tree");
 
 // np.sum(d ** 2, axis=1) of one landmark: three products rounded on their own, then (q0 + q1) + q2
 NLML_CN_HD inline double cn_sqnorm(double dx, double dy, double dz) {
@@ -64,9 +38,9 @@ NLML_CN_HD inline double cn_sqnorm(double dx, double dy, double dz) {
   return (q0 + q1) + q2;
 }
 
-// the four leaf sums -> the RMS radius: sqrt(pairwise / 468.0)
+// the leaf sums -> the RMS radius: sqrt(pairwise / 468.0)
 NLML_CN_HD inline double cn_scale(const double* leaf_sums) {
-  const double m = ((leaf_sums[0] + leaf_sums[1]) + (leaf_sums[2] + leaf_sums[3])) / (double)CN_LM;
+  const double m = np_tree_sum<CN_LEAVES>(leaf_sums) / (double)CN_LM;
   return sqrt(m);
 }
 
@@ -92,7 +66,7 @@ inline int cn_face_host(const float* raw, float* out, double* stats) {
   double n[CN_LM], leaf[CN_LEAVES];
   for (int i = 0; i < CN_LM; ++i)
     n[i] = cn_sqnorm((double)raw[3 * i] - cen[0], (double)raw[3 * i + 1] - cen[1], (double)raw[3 * i + 2] - cen[2]);
-  for (int l = 0; l < CN_LEAVES; ++l) leaf[l] = cn_pairwise_leaf(n + cn_leaf_off(l), cn_leaf_len(l));
+  for (int l = 0; l < CN_LEAVES; ++l) leaf[l] = np_leaf_sum(n + CnTree::off(l), CnTree::len(l));
   const double s = cn_scale(leaf);
   const int valid = cn_all_zero(raw) ? 0 : 1;
   for (int i = 0; i < CN_LM; ++i)

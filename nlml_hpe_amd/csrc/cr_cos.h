@@ -178,4 +178,21 @@ NLML_CR_HD float cr_f32_nab_sin(double a, double b, double t) {
   return (float)(nab * cr_sin(t));
 }
 
+// The f-vector entry f_a[j] and its derivative df_a[j] at the angle w from the cosine row (a, b, c, d) of (a, j) (TD_Tester.py:26):
+// b * w, + c rounded on their own, then the two functions above.
+NLML_CR_HD float cr_fvec(const double* row, double w) {
+  NLML_CR_STRICT
+  return cr_f32_a_cos_d(row[0], row[1] * w + row[2], row[3]);
+}
+NLML_CR_HD float cr_dfvec(const double* row, double w) {
+  NLML_CR_STRICT
+  return cr_f32_nab_sin(row[0], row[1], row[1] * w + row[2]);
+}
+
+// row q of Wm = W.reshape(27 R, 1404) is W[i, j, k, l], the einsum's nesting order: q -> i, j, k, l
+NLML_CR_HD constexpr int tucker_q_i(int q) { return q / 27; }
+NLML_CR_HD constexpr int tucker_q_j(int q) { return (q / 9) % 3; }
+NLML_CR_HD constexpr int tucker_q_k(int q) { return (q / 3) % 3; }
+NLML_CR_HD constexpr int tucker_q_l(int q) { return q % 3; }
+
 }  // namespace nlml

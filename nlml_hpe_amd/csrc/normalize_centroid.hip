@@ -98,7 +98,7 @@ __global__ __launch_bounds__(CN_THREADS) void normalize_centroid_kernel(const fl
     // P3: the leaves
     if (t < CN_PART * CN_LEAVES) {
       const int fl = t / CN_LEAVES, leaf = t - fl * CN_LEAVES;
-      if (fbase + fl < nf) s_leaf[(fbase + fl) * CN_LEAVES + leaf] = cn_pairwise_leaf(s_n + fl * CN_LM + cn_leaf_off(leaf), cn_leaf_len(leaf));
+      if (fbase + fl < nf) s_leaf[(fbase + fl) * CN_LEAVES + leaf] = np_leaf_sum(s_n + fl * CN_LM + CnTree::off(leaf), CnTree::len(leaf));
     }
     __syncthreads();
   }

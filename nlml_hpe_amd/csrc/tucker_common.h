@@ -104,21 +104,28 @@ __device__ __forceinline__ double row16_tree_sum(double v) {
   return v;
 }
 
-// par(e, k): parameter k (w_y, w_p, w_r, u_id[5]) of evaluation e.  cp4: this thread's cosine row
-// (threads < 144 only).  Leaves acc[mb][r] = x_hat of evaluation (lane>>4) + 4r at column
-// 16*(11*wave + mb) + (lane&15).
-// Coefficient phase: f-vectors and c[q][e] of all 16 evaluations into LDS (two barriers inside).
-template <typename ParT>
-__device__ __forceinline__ void tucker_coef(TuckerShared& sh, const ParT& par, const double (&cp4)[4], int tid) {
-#pragma clang fp contract(off)   // numpy rounds b*w, + c, a*cos, + d separately (TD_Tester.py:25-28); the coefficient products too
+// par(e, k): parameter k (w_y, w_p, w_r, u_id[R]) of evaluation e.  cp4: this thread's cosine row (threads < 144 only).
+// The f-vectors of all 16 evaluations into sh.fvec, on the double-double cos throughout (one barrier inside): the first half of the
+// coefficient phase of every rank (tucker_coef below, tucker_coef_r in tucker_rank.h).
+template <typename SH, typename ParT>
+__device__ __forceinline__ void tucker_coef_fvec(SH& sh, const ParT& par, const double (&cp4)[4], int tid) {
+#pragma clang fp contract(off)   // numpy rounds b*w, + c, a*cos, + d separately (TD_Tester.py:25-28)
   if (tid < EV * 9) {
     const int e = tid / 9, a = (tid % 9) / 3;
     const double v = cp4[0] * cr_cos(cp4[1] * par(e, a) + cp4[2]) + cp4[3];   // correctly rounded cos: cr_cos.h
     sh.fvec[e][a][tid % 3] = (double)(float)v;                     // .astype(np.float32), :37,40,43
   }
   __syncthreads();
+}
+
+// Coefficient phase: f-vectors and c[q][e] of all 16 evaluations into LDS (two barriers inside).
+template <typename ParT>
+__device__ __forceinline__ void tucker_coef(TuckerShared& sh, const ParT& par, const double (&cp4)[4], int tid) {
+#pragma clang fp contract(off)   // the coefficient products are rounded one by one
+  tucker_coef_fvec(sh, par, cp4, tid);
   for (int i = tid; i < TQS * 4 * EV; i += TNT) {
     const int q = i / EV, e = i % EV;
+    // (tucker_q_i .. tucker_q_l of cr_cos.h, written out: through the calls the rank-5 Powell kernel's scalar registers are allocated anew)
     const int ui = q / 27, j = (q / 9) % 3, k = (q / 3) % 3, l = q % 3;
     sh.coef[q][e] = q < TQ ? ((par(e, 3 + ui) * sh.fvec[e][0][j]) * sh.fvec[e][1][k]) * sh.fvec[e][2][l] : 0.0;
   }

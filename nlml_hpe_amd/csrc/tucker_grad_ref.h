@@ -5,7 +5,7 @@
 //   f_a  = float32(a cos(b w_a + c) + d)                       as the objective does (cr_cos.h)
 //   df_a = float32(((-a) b) sin(b w_a + c))                    :82,87,92, the sin correctly rounded (cr_cos.h, cr_f32_nab_sin)
 //   x_hat = einsum('ijklm,i,j,k,l->m', W, u, f_y, f_p, f_r)    numpy's generic loop (tucker_ref.h), r = x - x_hat, err = 0.5 sum(r^2)
-//   e_y   = the same einsum with df_y in f_y's place (e_p, e_r likewise);  grad_w_a = -np.sum(r * e_a)   numpy's pairwise tree
+//   e_y   = the same einsum with df_y in f_y's place (e_p, e_r likewise);  grad_w_a = -np.sum(r * e_a)   numpy's pairwise tree (np_sum.h)
 //   v     = einsum('ijklm,j,k,l->m', W, f_y, f_p, f_r)         all operands f32: numpy runs it IN F32, and it sums over i as well
 //           (the reference's quirk, kept): for q = (i,j,k,l) in nesting order, v[m] = f32(f32(f32(W f_yj) f_pk) f_rl) + v[m]
 //   grad_u[i] = -einsum('ijklm,m->i', W, t),  t = r * f64(v)
@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "cr_cos.h"
+#include "np_sum.h"
 
 namespace nlml {
 
@@ -47,29 +48,6 @@ NLML_CR_HD double tg_uid_combine(const AccAt acc) {
   return -o;
 }
 
-// numpy's pairwise sum (pairwise_sum_DOUBLE) of n contiguous doubles; n = 1404 gives the 16-leaf tree of tucker_ref.h
-inline double tg_pairwise(const double* a, int n) {
-  NLML_CR_STRICT
-  if (n < 8) {
-    double res = 0.0;
-    for (int i = 0; i < n; ++i) res += a[i];
-    return res;
-  }
-  if (n <= 128) {
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - n % 8; i += 8)
-      for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return tg_pairwise(a, n2) + tg_pairwise(a + n2, n - n2);
-}
-
 // One gradient on the host: Wm f32[27 R, 1404], x f32[1404], par f64[3 + R], cosp f64[3,3,4] -> *err (if given), grad f64[3 + R],
 // v f32[1404] (if given: the f32 einsum of the identity term, for tests).
 inline void tg_gradient_host(const float* Wm, const float* x, const double* par, const double* cosp, int rid, double* err, double* grad,
@@ -78,10 +56,9 @@ inline void tg_gradient_host(const float* Wm, const float* x, const double* par,
   float f[3][3], df[3][3];
   for (int a = 0; a < 3; ++a)
     for (int j = 0; j < 3; ++j) {
-      const double* c4 = cosp + (a * 3 + j) * 4;
-      const double t = c4[1] * par[a] + c4[2];
-      f[a][j] = cr_f32_a_cos_d(c4[0], t, c4[3]);
-      df[a][j] = cr_f32_nab_sin(c4[0], c4[1], t);
+      const double* row = cosp + (a * 3 + j) * 4;
+      f[a][j] = cr_fvec(row, par[a]);
+      df[a][j] = cr_dfvec(row, par[a]);
     }
   // chain 0: x_hat; chains 1..3: e_y, e_p, e_r (one factor triple swapped)
   static thread_local double ch[4][TG_M], r[TG_M], prod[TG_M], t[TG_M];
@@ -90,7 +67,7 @@ inline void tg_gradient_host(const float* Wm, const float* x, const double* par,
     for (int m = 0; m < TG_M; ++m) ch[c][m] = 0.0;
   for (int m = 0; m < TG_M; ++m) v[m] = 0.0f;
   for (int q = 0; q < 27 * rid; ++q) {
-    const int i = q / 27, j = (q / 9) % 3, k = (q / 3) % 3, l = q % 3;
+    const int i = tucker_q_i(q), j = tucker_q_j(q), k = tucker_q_k(q), l = tucker_q_l(q);
     const float* w = Wm + (int64_t)q * TG_M;
     for (int c = 0; c < 4; ++c) {
       const double u = par[3 + i], fy = (double)(c == 1 ? df[0][j] : f[0][j]), fp = (double)(c == 2 ? df[1][k] : f[1][k]),
@@ -103,11 +80,11 @@ inline void tg_gradient_host(const float* Wm, const float* x, const double* par,
   for (int m = 0; m < TG_M; ++m) r[m] = (double)x[m] - ch[0][m];
   if (err) {
     for (int m = 0; m < TG_M; ++m) prod[m] = r[m] * r[m];
-    *err = 0.5 * tg_pairwise(prod, TG_M);
+    *err = 0.5 * np_pairwise_sum(prod, TG_M);
   }
   for (int a = 0; a < 3; ++a) {
     for (int m = 0; m < TG_M; ++m) prod[m] = r[m] * ch[1 + a][m];
-    grad[a] = -tg_pairwise(prod, TG_M);
+    grad[a] = -np_pairwise_sum(prod, TG_M);
   }
   for (int m = 0; m < TG_M; ++m) t[m] = r[m] * (double)v[m];
   if (v_out)

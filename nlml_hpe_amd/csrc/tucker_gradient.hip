@@ -53,34 +53,21 @@ struct GradChainRow {
   __device__ __forceinline__ double* operator()(int slot) const { return x_hat + slot * TM; }
 };
 
-// numpy's pairwise sums of rs.d2[0 .. nrows), nrows <= 6 (the tree of tucker_ref_pass, levels 1-3): thread t < nrows returns row t's
+// numpy's pairwise sums of rs.d2[0 .. nrows), nrows <= TG_SUM_ROWS (np_sum.h over the pass's tree, TrTree): a lane per (row, leaf), then
+// thread t < nrows returns row t's.  Eight lanes of every wave take leaves: neighbouring leaves of a row start 48 words apart modulo the
+// 64 LDS banks (a row: a multiple of 64), so a wave's reads meet two or three to a bank; the sixteen leaves of four rows in one wave
+// would meet sixteen.
+constexpr int TG_SUM_ROWS = 6;              // r e_y, r e_p, r e_r of two gradients
+static_assert(TG_SUM_ROWS * TR_LEAVES <= TR_NT / 64 * 8, "eight leaves per wave");
 template <typename RS>
 __device__ __forceinline__ double tg_block_pairwise(RS& rs, int nrows, int tid) {
-#pragma clang fp contract(off)
-  for (int t = tid; t < nrows * TR_LEAVES * 8; t += TR_NT) {
-    const int n = t / (TR_LEAVES * 8), L = (t / 8) % TR_LEAVES, jj = t % 8;
-    const double* a = rs.d2[n] + tr_leaf_start(L);
-    const int nq = tr_leaf_len(L) >> 3;
-    double r = a[jj];
-    for (int q = 1; q < nq; ++q) r = r + a[jj + 8 * q];
-    rs.leaf8[n][L][jj] = r;
+  const int task = (tid >> 6) * 8 + (tid & 63);
+  if ((tid & 63) < 8 && task < nrows * TR_LEAVES) {
+    const int n = task / TR_LEAVES, L = task % TR_LEAVES;
+    rs.leaf[n][L] = np_leaf_sum(rs.d2[n] + tr_leaf_start(L), tr_leaf_len(L));
   }
   __syncthreads();
-  for (int t = tid; t < nrows * TR_LEAVES; t += TR_NT) {
-    const int n = t / TR_LEAVES, L = t % TR_LEAVES;
-    const double* r = rs.leaf8[n][L];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    const double* a = rs.d2[n] + tr_leaf_start(L);
-    const int len = tr_leaf_len(L);
-    for (int q = len - (len & 7); q < len; ++q) res = res + a[q];
-    rs.leaf[n][L] = res;
-  }
-  __syncthreads();
-  if (tid >= nrows) return 0.0;
-  const double* s = rs.leaf[tid];
-  const double a0 = (s[0] + s[1]) + (s[2] + s[3]), a1 = (s[4] + s[5]) + (s[6] + s[7]);
-  const double a2 = (s[8] + s[9]) + (s[10] + s[11]), a3 = (s[12] + s[13]) + (s[14] + s[15]);
-  return (a0 + a1) + (a2 + a3);
+  return tid < nrows ? np_tree_sum<TR_LEAVES>(rs.leaf[tid]) : 0.0;
 }
 
 __global__ __launch_bounds__(TR_NT, 1) void tucker_gradient_kernel(
@@ -101,10 +88,9 @@ __global__ __launch_bounds__(TR_NT, 1) void tucker_gradient_kernel(
   // f and df of the workgroup's gradients (a gradient beyond N repeats the last one: defined values, never stored)
   if (tid < TG_GPB * 9) {
     const int g = tid / 9, a = (tid % 9) / 3, j = tid % 3;
-    const double* c4 = cosp + (a * 3 + j) * 4;                    // (a,b,c,d) row, TD_Tester.py:26
-    const double t = c4[1] * par(4 * g, a) + c4[2];
-    ff[g][0][a][j] = cr_f32_a_cos_d(c4[0], t, c4[3]);
-    ff[g][1][a][j] = cr_f32_nab_sin(c4[0], c4[1], t);
+    const double* row = cosp + (a * 3 + j) * 4;                   // (a,b,c,d) row, TD_Tester.py:26
+    ff[g][0][a][j] = cr_fvec(row, par(4 * g, a));
+    ff[g][1][a][j] = cr_dfvec(row, par(4 * g, a));
   }
   __syncthreads();
   if (tid < EV * 9) {

@@ -38,17 +38,12 @@ using TuckerRefSharedR = TuckerRefSharedT<MAXE, TRK_RMAX + 9>;   // factor rows 
 // tucker_coef for 27 R rows (same expressions: at R = 5 the same table)
 template <typename ParT>
 __device__ __forceinline__ void tucker_coef_r(TuckerSharedR& sh, const ParT& par, const double (&cp4)[4], int tid, int rid) {
-#pragma clang fp contract(off)   // numpy rounds b*w, + c, a*cos, + d separately (TD_Tester.py:25-28); the coefficient products too
-  if (tid < EV * 9) {
-    const int e = tid / 9, a = (tid % 9) / 3;
-    const double v = cp4[0] * cr_cos(cp4[1] * par(e, a) + cp4[2]) + cp4[3];
-    sh.fvec[e][a][tid % 3] = (double)(float)v;
-  }
-  __syncthreads();
+#pragma clang fp contract(off)   // the coefficient products are rounded one by one
+  tucker_coef_fvec(sh, par, cp4, tid);
   const int tq = 27 * rid, rows = (tq + 3) & ~3;
   for (int i = tid; i < rows * EV; i += TNT) {
     const int q = i / EV, e = i % EV;
-    const int ui = q < tq ? q / 27 : rid - 1, j = (q / 9) % 3, k = (q / 3) % 3, l = q % 3;   // (a padding row reads a parameter that exists)
+    const int ui = q < tq ? tucker_q_i(q) : rid - 1, j = tucker_q_j(q), k = tucker_q_k(q), l = tucker_q_l(q);   // (a padding row reads a parameter that exists)
     const double c = ((par(e, 3 + ui) * sh.fvec[e][0][j]) * sh.fvec[e][1][k]) * sh.fvec[e][2][l];
     sh.coef[q][e] = q < tq ? c : 0.0;
   }
@@ -123,7 +118,9 @@ struct TdRankDyn {
   __device__ __forceinline__ TrDynRank pass_rank() const { return {rid}; }
 };
 
-// this thread's cosine row (a,b,c,d), TD_Tester.py:26 (threads < 144; zeros beyond)
+// this thread's cosine row (a,b,c,d), TD_Tester.py:26 (threads < 144; zeros beyond).  Row (tid % 9) / 3 * 3 + tid % 3 is row tid % 9;
+// the long spelling stays until these kernels may change: the short one takes eleven instructions out of every prologue
+// (profiles/np_sum_one_definition.md).
 __device__ __forceinline__ void load_cos_rows(const double* __restrict__ cosp, int tid, double (&cp4)[4]) {
   cp4[0] = cp4[1] = cp4[2] = cp4[3] = 0.0;
   if (tid < EV * 9) {

@@ -8,7 +8,7 @@
 //   np.einsum('ijklm,i,j,k,l->m', W, u, f_y, f_p, f_r)   numpy's generic sum-of-products loop: for (i,j,k,l) in nesting order,
 //       for every m:  x_hat[m] = ((((W[i,j,k,l,m] * u_i) * f_yj) * f_pk) * f_rl) + x_hat[m],  each operation rounded on its own;
 //   0.5 * np.sum((x - x_hat)**2)                         numpy's pairwise sum: 16 leaves of 80/88/92 elements, each as eight
-//       strided partial sums combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus remainder, the leaves added as a balanced tree.
+//       strided partial sums combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus remainder, the leaves added as a balanced tree (np_sum.h).
 //
 // W sits innermost in every product, so nothing can be shared between columns or evaluations: 5 separately rounded f64 operations
 // per (q, m) and evaluation -- 135 * 1404 * 5 = 947,700 vector-ALU operations per evaluation against one fma per (q, m) on the
@@ -36,6 +36,7 @@
 
 #include <type_traits>
 
+#include "np_sum.h"
 #include "tucker_common.h"
 
 namespace nlml {
@@ -46,7 +47,8 @@ namespace nlml {
 constexpr int TR_NT = TR_NT_N;                // threads of a reference-order workgroup: 12 waves, three per SIMD
 constexpr int TR_COLS = 2;                 // columns per thread: 2 * 768 = 1536 >= 1404
 constexpr int TR_MAXE = 8;                 // evaluations per pass over Wm
-constexpr int TR_LEAVES = 16;              // numpy pairwise tree for n = 1404 (tests/test_oracle_golden.py pins it to np.sum)
+typedef NpTree<TM> TrTree;                 // numpy's pairwise tree for n = 1404 (np_sum.h): 16 leaves of 80, 14 x 88, 92
+constexpr int TR_LEAVES = TrTree::leaves;
 #ifndef TR_ILV_N
 #define TR_ILV_N 4
 #endif
@@ -95,8 +97,19 @@ struct TrDynRank {
   __device__ __forceinline__ int r() const { return __builtin_amdgcn_readfirstlane(rid); }   // (arguments of a non-inlined function arrive in vector registers)
 };
 
-__device__ __forceinline__ int tr_leaf_start(int L) { return L == 0 ? 0 : 80 + 88 * (L - 1); }
-__device__ __forceinline__ int tr_leaf_len(int L) { return L == 0 ? 80 : (L == TR_LEAVES - 1 ? 92 : 88); }
+// Leaf L of TrTree in closed form (a multiply-add and two selects where the tree's own off / len are a chain of 15): the first leaf,
+// the last leaf, and equal ones between them.  TR_LEAF_NQ / TR_LEAF_REM: the most strided steps and remainder elements a leaf has.
+constexpr int TR_LEAF_FIRST = TrTree::len(0), TR_LEAF_MID = TrTree::len(1), TR_LEAF_LAST = TrTree::len(TR_LEAVES - 1);   // 80, 88, 92
+__device__ __forceinline__ constexpr int tr_leaf_start(int L) { return L == 0 ? 0 : TR_LEAF_FIRST + TR_LEAF_MID * (L - 1); }
+__device__ __forceinline__ constexpr int tr_leaf_len(int L) { return L == 0 ? TR_LEAF_FIRST : (L == TR_LEAVES - 1 ? TR_LEAF_LAST : TR_LEAF_MID); }
+constexpr int TR_LEAF_NQ = 11, TR_LEAF_REM = 4;
+constexpr bool tr_leaves_are_the_trees() {
+  for (int L = 0; L < TR_LEAVES; ++L)
+    if (tr_leaf_start(L) != TrTree::off(L) || tr_leaf_len(L) != TrTree::len(L) || tr_leaf_len(L) / 8 > TR_LEAF_NQ || tr_leaf_len(L) % 8 > TR_LEAF_REM)
+      return false;
+  return true;
+}
+static_assert(tr_leaves_are_the_trees() && TrTree::balanced, "the closed form is np_sum.h's tree; np_tree_sum adds its leaves as a balanced tree");
 
 // LDS accesses through a generic pointer, as ds_ instructions
 template <typename T>
@@ -344,7 +357,9 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
   }
   __syncthreads();
   TRS(3);
-  // numpy's pairwise sum, level 1: eight strided partial sums per leaf
+  // numpy's pairwise sum (np_sum.h), a leaf's eight accumulators on eight lanes.  Levels 1 and 2 are written out for this pass: as a
+  // function shared with tucker_gradient.hip every instantiation of the pass came out as other code (profiles/np_sum_one_definition.md).
+  // Level 1: eight strided partial sums per leaf
   for (int t = tid; t < NE * TR_LEAVES * 8; t += TR_NT) {
     const int n = t / (TR_LEAVES * 8), L = (t / 8) % TR_LEAVES, jj = t % 8;
     const __attribute__((address_space(3))) double* a = rl->d2[n] + tr_leaf_start(L);
@@ -352,12 +367,12 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
     // 10 or 11 elements (leaves of 80 / 88 / 92): all reads first (a loop with a run-time trip count waits for every LDS read on
     // its own: 1.1 k ticks per sum), then the adds in numpy's order; the surplus read of a 10-element sum is a clamped re-read
     const int nq = body >> 3;
-    double v[11];
+    double v[TR_LEAF_NQ];
 #pragma unroll
-    for (int q = 0; q < 11; ++q) v[q] = a[jj + 8 * (q < nq ? q : nq - 1)];
+    for (int q = 0; q < TR_LEAF_NQ; ++q) v[q] = a[jj + 8 * (q < nq ? q : nq - 1)];
     double r = v[0];
 #pragma unroll
-    for (int q = 1; q < 11; ++q) {
+    for (int q = 1; q < TR_LEAF_NQ; ++q) {
       const double r1 = r + v[q];
       r = q < nq ? r1 : r;
     }
@@ -373,11 +388,11 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
     const __attribute__((address_space(3))) double* a = rl->d2[n] + tr_leaf_start(L);
     const int len = tr_leaf_len(L);
     const int rem = len & 7, b8 = len - rem;            // 0 or 4 remainder elements
-    double w4[4];
+    double w4[TR_LEAF_REM];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) w4[q] = a[q < rem ? b8 + q : 0];
+    for (int q = 0; q < TR_LEAF_REM; ++q) w4[q] = a[q < rem ? b8 + q : 0];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < TR_LEAF_REM; ++q) {
       const double r1 = res + w4[q];
       res = q < rem ? r1 : res;
     }
@@ -390,9 +405,7 @@ __device__ __attribute__((noinline)) void tucker_ref_pass(const SH& sh, RS& rs, 
     double s[TR_LEAVES];
 #pragma unroll
     for (int L = 0; L < TR_LEAVES; ++L) s[L] = rl->leaf[tid][L];
-    const double a0 = (s[0] + s[1]) + (s[2] + s[3]), a1 = (s[4] + s[5]) + (s[6] + s[7]);
-    const double a2 = (s[8] + s[9]) + (s[10] + s[11]), a3 = (s[12] + s[13]) + (s[14] + s[15]);
-    rl->err[(slots >> (4 * tid)) & 15] = 0.5 * ((a0 + a1) + (a2 + a3));
+    rl->err[(slots >> (4 * tid)) & 15] = 0.5 * np_tree_sum<TR_LEAVES>(s);
   }
   __syncthreads();
   TRS(6);
@@ -406,7 +419,7 @@ __device__ __forceinline__ void tucker_fvec(SH& sh, const ParT& par, const doubl
   if (tid < EV * 9) {
     const int e = tid / 9, a = (tid % 9) / 3;
     // float32(a * cos(b * w + c) + d) with the cos correctly rounded, by the library cos wherever that cannot change the float (cr_cos.h)
-    sh.fvec[e][a][tid % 3] = (double)cr_f32_a_cos_d(cp4[0], cp4[1] * par(e, a) + cp4[2], cp4[3]);
+    sh.fvec[e][a][tid % 3] = (double)cr_fvec(cp4, par(e, a));
   }
   __syncthreads();
 }

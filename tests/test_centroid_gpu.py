@@ -68,6 +68,24 @@ def test_kernel_equals_host_restatement(device, B):
             assert same_bits(stats.cpu().numpy(), exp_stats), (B, wv, ws)
 
 
+@pytest.mark.parametrize("B", [24, 21])
+def test_kernel_sums_the_squared_norms_in_numpys_order(device, B):
+    """The first faces of test_centroid_host.test_pairwise_tree_is_numpys's input (the same draws: coordinates six decimal orders of
+    magnitude apart within a face, so the scale depends on the order in which the 468 squared norms are added): three workgroups of
+    eight faces, each in two LDS parts, and at 21 a ragged last one."""
+    g = synth.rng(43, 0)
+    raw = (g.standard_normal((300, 468, 3)) * 10.0 ** g.uniform(-3, 3, (300, 468, 1))).astype(np.float32)[:B]
+    exp_out, exp_valid, exp_stats = host(raw)
+    a = raw.astype(np.float64)
+    n = np.sum((a - np.mean(a, axis=1, keepdims=True)) ** 2, axis=2)
+    assert (np.cumsum(n, axis=1)[:, -1] != np.sum(n, axis=1)).any()          # added left to right, the norms give another sum
+    out, valid, stats = device_call(torch.from_numpy(raw).to(device), True, True)
+    torch.cuda.synchronize(device)
+    assert same_bits(stats.cpu().numpy(), exp_stats)
+    assert same_bits(out.cpu().numpy(), exp_out)
+    assert np.array_equal(valid.cpu().numpy(), exp_valid) and exp_valid.all()
+
+
 def test_empty_batch(device):
     raw = torch.zeros((0, 468, 3), dtype=torch.float32, device=device)
     out, valid, stats = ops.normalize_centroid(raw, return_valid=True, return_stats=True)

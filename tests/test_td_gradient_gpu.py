@@ -9,7 +9,8 @@ import torch
 
 import rank_fixture as RF
 import td_gradient_common as GC
-from nlml_hpe_amd import _lib, ops
+from nlml_hpe_amd import _lib, ops, synth
+from oracle import tucker as OT
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +58,46 @@ def test_device_gradient_past_one_workgroup_of_the_second_launch(N, R, host_draw
     W, P, X, e_h, g_h = host_draws[R]
     err, grad = _dev_gradient(W, X[:N], P[:N], GC.cos_block(tucker_art), device)
     print(f"N={N} R={R}: err mismatches {int((err != e_h[:N]).sum())}, gradient mismatches {int((grad != g_h[:N]).sum())} of {grad.size}")
+    assert np.array_equal(err, e_h[:N])
+    assert np.array_equal(grad, g_h[:N])
+
+
+@pytest.fixture(scope="module")
+def scaled_draws(tucker_art):
+    """Per rank 1 and 5: six draws whose x columns are scaled by 10 ** uniform(-6, 6), the host restatement's (err, grad) on them, and
+    the products r * e_a (f64[6, 3, 1404]) formed with numpy as the reference forms them (TD_Tester.py:60-102)."""
+    out = {}
+    cp = GC.cos_block(tucker_art)
+    rows = RF.cos_rows(tucker_art)
+    for R in (1, 5):
+        W, P, X = GC.draws(tucker_art, R, 6)
+        X = (X * 10.0 ** synth.rng(60 + R, 0).uniform(-6, 6, 1404)).astype(np.float32)
+        prods = np.empty((6, 3, 1404))
+        for n in range(6):
+            f = OT.f_vectors(P[n], *rows)
+            r = X[n] - np.einsum('ijklm,i,j,k,l->m', W, P[n, 3:], *f)
+            for a in range(3):
+                w, p = P[n, a], rows[a]
+                df = np.array([-q[0] * q[1] * np.sin(q[1] * w + q[2]) for q in p]).flatten().astype(np.float32)
+                prods[n, a] = r * np.einsum('ijklm,i,j,k,l->m', W, P[n, 3:], *(df if b == a else f[b] for b in range(3)))
+        out[R] = (W, P, X, prods) + GC.gradient_host(W, X, P, cp)
+    return out
+
+
+@pytest.mark.parametrize("R", [1, 5])
+@pytest.mark.parametrize("N", [1, 3, 4, 6])
+def test_angle_components_with_an_order_sensitive_residual(N, R, scaled_draws, tucker_art, device):
+    """The pairwise tree over r * e_a where its order shows: one gradient alone, an odd count in a workgroup (the tree on three rows),
+    a full workgroup, a second workgroup with two."""
+    W, P, X, prods, e_h, g_h = scaled_draws[R]
+    # the input does its job: the host's angle components are numpy's pairwise sums of these products, and added left to right
+    # (np.cumsum) at least one of them would be another double
+    pairwise, in_sequence = -np.sum(prods[:N], axis=2), -np.cumsum(prods[:N], axis=2)[:, :, -1]
+    assert np.array_equal(pairwise, g_h[:N, :3])
+    assert (in_sequence != pairwise).any()
+    err, grad = _dev_gradient(W, X[:N], P[:N], GC.cos_block(tucker_art), device)
+    print(f"N={N} R={R}: err mismatches {int((err != e_h[:N]).sum())}, gradient mismatches {int((grad != g_h[:N]).sum())} of {grad.size}; "
+          f"{int((in_sequence != pairwise).sum())} of {3 * N} angle components depend on the order")
     assert np.array_equal(err, e_h[:N])
     assert np.array_equal(grad, g_h[:N])
 
