@@ -336,6 +336,15 @@ int nlml_tucker_objective_ex(const float* Wm, const float* x, int64_t ldx, const
  *            np.degrees(result.x)[:3] (:196-199)
  *   fval f64[N], nfev i32[N], nit i32[N], status i32[N] (1 converged, 2 maxfev, 3 maxiter, 4 nan):
  *            scipy's res.fun / res.nfev / res.nit; each may be NULL.
+ * NON-FINITE FEATURES OR STARTS (n = the number of parameters, 8 here): what scipy returns for them, never an error.
+ *   a NaN feature, or a NaN / Inf in x0: the objective is NaN everywhere -> status 4 after 1 + 3 n evaluations and one iteration,
+ *       result and fval NaN;
+ *   an Inf feature: the objective is +inf everywhere -> status 2 after exactly 1000 n evaluations, result = x0, fval = +inf.  Such
+ *       a face keeps its workgroup, and with it the launch, busy for all 1000 n rounds (0.1-0.3 s on an MI355X): filter such faces out
+ *       first where that matters;
+ *   an all-zero row (the "no face" sentinel) from x0 = NULL converges in the first iteration: status 1, result = 0, fval = 0.
+ * Status 3 cannot occur with the fixed limits maxiter = maxfev = 1000 n: an iteration costs at least n evaluations, so maxfev comes
+ * first.  Status 0 is never written.  (tests/test_td_powell_edges_gpu.py)
  * The control flow is scipy 1.15.3's (restated in nlml_hpe_amd/csrc/powell.h, checked against scipy step for step on the CPU).
  *   NLML_TD_ORDER_REFERENCE (default, parity mode): every machine receives the reference's objective values bit for bit, so it
  *       walks scipy's own trajectory: same evaluation counts, same final angles (FX5: identical bits; 1e-4 deg is the bar).
