@@ -57,7 +57,7 @@ int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int 
                              int64_t B, int F, const void* blob, float* out, float* latent,
                              uint8_t* valid, float* pre_tanh, unsigned long long* stamps, void* stream,
                              int reeval_over = -1);   // >= 0: re-evaluation launch behind a split-f16 one (encoder_heads.hip)
-// the f32 image inside an NLML_MODE_F16X2S blob (pack.cpp): byte offset from the blob's start
+// the f32 image inside an NLML_MODE_F16X2S blob (layout.h, layout_strict_f32_image16): byte offset from the blob's start
 size_t strict_f32_image_offset(int F);
 // the strict-fast mode's re-evaluation launch behind its split-f16 kernels (fused, streamed, layer-per-launch): the f32 kernel on that image
 int launch_strict_reeval(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F, const void* blob,

@@ -379,7 +379,7 @@ __device__ __forceinline__ void stage_e0_pass(const Ctx& c, const EncArgs& a, E0
   f32x16 acc[NB][NFB];   // the running chain of the current 128-k block; `tot` collects the block sums (see fold_block)
   float* xs = c.lds + O_XS;
   const int F = a.F;
-  const int nslab = (int)c.hdr->k8_e0 / XS_STEPS;   // even: k8_e0 is a multiple of 2*XS_STEPS (pack.cpp)
+  const int nslab = (int)c.hdr->k8_e0 / XS_STEPS;   // even: k8_e0 is a multiple of 2*XS_STEPS (layout.h, layout_e0_steps)
 
   // x staging, software-pipelined over THREE LDS slab buffers (slab j lives in buffer j % 3):
   //   top of slab s     issue the global loads of slab s+3 into one of two register sets;

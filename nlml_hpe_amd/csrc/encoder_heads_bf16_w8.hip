@@ -39,7 +39,7 @@ template <bool VEC4, bool NORM>
 __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t row0, int tid, int jw, int nbh, f32x16 (&acc)[4][2]) {
   constexpr int NB = 4, NFB = 2, WSTEP = 8 * 64;
   const int F = a.F;
-  const int nslab = (int)c.hdr->k8_e0 / XS_STEPS;   // even (pack.cpp)
+  const int nslab = (int)c.hdr->k8_e0 / XS_STEPS;   // even (layout.h, layout_e0_steps)
   constexpr int SLAB_BYTES = 64 * S_XS * 2;
 
   const int srow = tid >> 3, scol = (tid & 7) * 8;

@@ -53,7 +53,7 @@ __device__ __forceinline__ void stage_e0(const Ctx& c, const Args& a, int64_t ro
                                          f32x16 (&accB)[4][2]) {
   constexpr int NB = 4, NFB = 2;
   const int F = a.F;
-  const int nslab = (int)c.hdr.k8_e0 / XS_STEPS;   // even (pack.cpp)
+  const int nslab = (int)c.hdr.k8_e0 / XS_STEPS;   // even (layout.h, layout_e0_steps)
   constexpr int SLAB_BYTES = 2 * P_XS;
 
   // staging role: row srow (0..63), 8 consecutive columns scol..scol+7 of every slab

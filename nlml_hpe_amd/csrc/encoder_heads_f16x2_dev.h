@@ -30,6 +30,41 @@ struct Args {
                           // the streamed tail (encoder_heads_f16x2_tailws.hip)
 };
 
+// The two buffers that carry activations from one launch to the next, ONCE: both hold MFMA B-operand fragments of 16 bytes per lane --
+// fragment (K16 step, piece, lane) of a 32-face block = the hi or lo f16 pieces of activations k = 16*step + 8*(lane>>5) .. +7 of its
+// face lane&31 -- and every writer, every reader and the host's size functions take the geometry from here (h8 / 16-byte units).
+//
+// LayerFrags: the layer-per-launch path's workspace (encoder_heads_f16x2_small.hip), [tile][K16 step][face block][piece][lane] with
+// `steps` K steps per 64-face tile; the path ping-pongs between two of them.
+struct LayerFrags {
+  static constexpr int STEP_UNITS = 2 * PIECES * 64;                                      // per (tile, K step): 4 KiB
+  // K steps per tile: layer 0's input (k16_e0) or layer 1's (1024 columns), whichever is longer
+  static NLML_HOST_DEVICE constexpr int steps(int k16_e0) { return k16_e0 > kStages[ST_E1].k8 ? k16_e0 : kStages[ST_E1].k8; }
+  static NLML_HOST_DEVICE constexpr size_t tile_units(int steps) { return (size_t)steps * STEP_UNITS; }
+  static NLML_HOST_DEVICE constexpr int frag(int fb, int piece) { return (fb * PIECES + piece) * 64; }   // within a K step
+  static NLML_HOST_DEVICE constexpr size_t unit(int steps, int64_t tile, int step, int fb, int piece, int lane) {
+    return ((size_t)tile * steps + step) * STEP_UNITS + (size_t)frag(fb, piece) + lane;
+  }
+  static NLML_HOST_DEVICE constexpr size_t in_tile(int step, int fb, int piece, int lane) {   // unit() from the tile's first unit
+    return (size_t)step * STEP_UNITS + (size_t)frag(fb, piece) + lane;
+  }
+  static constexpr size_t bytes(int64_t B, int F) {   // both buffers
+    return (size_t)2 * ((B + TILE_FACES - 1) / TILE_FACES) * steps(layout_e0_steps(kLayoutHX, F)) * STEP_UNITS * 16;
+  }
+};
+static_assert(LayerFrags::unit(88, 5, 17, 1, 1, 63) == 5 * LayerFrags::tile_units(88) + LayerFrags::in_tile(17, 1, 1, 63), "LayerFrags");
+// TrunkFrags: layer 2's output as the trunk-only launch hands it to the streamed tail (encoder_heads_f16x2_w8.hip TRUNK ->
+// encoder_heads_f16x2_tailws.hip), [32-face block][K16 step][piece][lane], whole 64-face tiles: 1 KiB per face.
+struct TrunkFrags {
+  static constexpr int STEPS = kStages[ST_E3].k8;                                         // layer 2's 256 outputs = E3's K steps
+  static constexpr int BLOCK_UNITS = STEPS * PIECES * 64, TILE_UNITS = 2 * BLOCK_UNITS;
+  static NLML_HOST_DEVICE constexpr int frag(int block, int step, int piece) { return ((block * STEPS + step) * PIECES + piece) * 64; }   // within a tile
+  static NLML_HOST_DEVICE constexpr size_t unit(int64_t block, int step, int piece, int lane) {
+    return (size_t)block * BLOCK_UNITS + frag(0, step, piece) + lane;
+  }
+  static constexpr size_t bytes(int64_t B) { return (size_t)((B + TILE_FACES - 1) / TILE_FACES) * TILE_UNITS * 16; }
+};
+
 // (v0, v1) -> packed f16 pairs hi = f16(v), lo = f16(v - hi) in THREE instructions: v_cvt_pk_f16_f32, then one mixed-precision
 // fma per element (-hi * 1.0 + v evaluated in f32 -- exact -- and rounded once to f16 into the low / high half).  Bit-identical
 // to the plain C form (five conversions, two subtractions, a pack) on 4 M values incl. subnormal, overflowing and non-finite ones
@@ -319,27 +354,40 @@ __device__ __forceinline__ void store_lds(const f32x16 (&acc)[NB][NFB], char* ou
 // re-fetched after every global store of the kernel (the blob pointer is not provably distinct from the output pointers) -- as
 // VECTOR loads with a full memory latency in front of every address that depends on them: ~600 exposed cycles in front of each
 // prefetch group of the head stages.  The offsets are arithmetic in layer 0's step count (the only size that depends on F):
-// stage s starts at  W0[s] + W1[s] * k16_e0  (16-byte units), exactly as pack.cpp lays the blob out (it checks this formula
-// against the header it writes); only k16_e0 and the eleven power-of-two scales are data, read once at kernel entry into SGPRs.
-struct StageOff { int w0, w1; };   // w_off = w0 + w1 * k16_e0
-constexpr int stage_job_w16_const(int s) { return s == ST_E0 ? 0 : kStages[s].k8 * kStages[s].nb * 64 * PIECES; }
-constexpr int stage_job_w16_k(int s) { return s == ST_E0 ? kStages[s].nb * 64 * PIECES : 0; }
-constexpr StageOff stage_w_off(int s) {
-  StageOff o{(int)(sizeof(Header) / 16), 0};
-  for (int t = 0; t < s; ++t) {
-    o.w0 += kStages[t].jobs * (stage_job_w16_const(t) + kStages[t].nb * 8);
-    o.w1 += kStages[t].jobs * stage_job_w16_k(t);
+// layout.h's functions over kLayoutHX with k16_e0 at run time and everything else a constant -- the definition pack.cpp fills the header
+// from; only k16_e0 and the eleven power-of-two scales are data, read once at kernel entry into SGPRs.
+// They are affine in k16_e0, so each is tabulated at compile time as a constant and a coefficient (the function at 0, its step from 0 to
+// 1; checked below at other counts): handed the run-time k16_e0 directly, the same sums reach the back end in another shape and
+// the eight-wave kernel's listing moves (profiles/k2_layout_one_definition.md).
+struct Affine { uint32_t c, m; };   // c + m * k16_e0
+struct HxAffine { Affine job_w16[NUM_STAGES], w_off[NUM_STAGES], b_off[NUM_STAGES]; };
+constexpr HxAffine hx_affine() {
+  HxAffine a{};
+  for (int s = 0; s < NUM_STAGES; ++s) {
+    a.job_w16[s] = {layout_job_w16(kLayoutHX, s, 0u), layout_job_w16(kLayoutHX, s, 1u) - layout_job_w16(kLayoutHX, s, 0u)};
+    a.w_off[s] = {layout_w_off(kLayoutHX, s, 0u), layout_w_off(kLayoutHX, s, 1u) - layout_w_off(kLayoutHX, s, 0u)};
+    a.b_off[s] = {layout_b_off(kLayoutHX, s, 0u), layout_b_off(kLayoutHX, s, 1u) - layout_b_off(kLayoutHX, s, 0u)};
   }
-  return o;
+  return a;
 }
+constexpr HxAffine kHxAffine = hx_affine();
 
 struct HdrRegs {
   uint32_t k8_e0;
   float inv_scale[NUM_STAGES];
-  __device__ __forceinline__ uint32_t job_w16(int s) const { return stage_job_w16_const(s) + stage_job_w16_k(s) * k8_e0; }
-  __device__ __forceinline__ uint32_t w_off(int s) const { return stage_w_off(s).w0 + stage_w_off(s).w1 * k8_e0; }
-  __device__ __forceinline__ uint32_t b_off(int s) const { return w_off(s) + kStages[s].jobs * job_w16(s); }
+  __device__ __forceinline__ uint32_t job_w16(int s) const { return kHxAffine.job_w16[s].c + kHxAffine.job_w16[s].m * k8_e0; }
+  __device__ __forceinline__ uint32_t w_off(int s) const { return kHxAffine.w_off[s].c + kHxAffine.w_off[s].m * k8_e0; }
+  __device__ __forceinline__ uint32_t b_off(int s) const { return kHxAffine.b_off[s].c + kHxAffine.b_off[s].m * k8_e0; }
 };
+
+constexpr bool hdr_regs_are_the_layout(uint32_t k) {   // the functions are affine in k16_e0: c and m hold at any k
+  for (int s = 0; s < NUM_STAGES; ++s)
+    if (layout_job_w16(kLayoutHX, s, k) != kHxAffine.job_w16[s].c + kHxAffine.job_w16[s].m * k ||
+        layout_w_off(kLayoutHX, s, k) != kHxAffine.w_off[s].c + kHxAffine.w_off[s].m * k ||
+        layout_b_off(kLayoutHX, s, k) != kHxAffine.b_off[s].c + kHxAffine.b_off[s].m * k) return false;
+  return true;
+}
+static_assert(hdr_regs_are_the_layout(88u) && hdr_regs_are_the_layout(4u), "HdrRegs evaluates the layout functions as c + m * k16_e0");
 
 __device__ __forceinline__ HdrRegs load_hdr(const Header* hdr) {
   HdrRegs r;
@@ -663,7 +711,11 @@ __device__ __forceinline__ void tail_helper_w8(const Ctx& c) {
   }
 }
 
-template <bool ONEFB = false, int RESCUE_UP_TO = 64, bool H1W8 = false>
+// HEADS = false: layers E3, E4, E5 only -- the function ends behind the barrier after E5's store, the latent image in LDS and the f32
+// latent in global memory (the layer-per-launch path's tail_encoder_kernel, whose heads are a launch of their own).  The one body of
+// E3..E5 stays HERE and is not a function of its own: called as one, the eight-wave kernel's f32 latent stores are formed differently
+// and its listing moves (profiles/k2_layout_one_definition.md).
+template <bool ONEFB = false, int RESCUE_UP_TO = 64, bool H1W8 = false, bool HEADS = true>
 __device__ __forceinline__ void tail_stages(const Ctx& c, const Args& a, int64_t row0, f32x16 (&acc3)[1][TailE3<ONEFB>::NFB],
                                             h8 (&wr3)[ring_slots(1, TailE3<ONEFB>::NFB)][1][2], int fbsel = 0) {
   static_assert(!H1W8 || (!ONEFB && RESCUE_UP_TO == 0), "H1 over eight waves: the strict eight-wave kernel's 64-face tail only");
@@ -714,6 +766,7 @@ __device__ __forceinline__ void tail_stages(const Ctx& c, const Args& a, int64_t
   }
   __syncthreads();
   HXS(12);
+  if constexpr (!HEADS) return;
   // ---- heads.  Fused kernel (64 faces in the workgroup): ONE HEAD AT A TIME over both face blocks (heads_by_head below);
   // small-batch tail (ONEFB, 32 faces): the three heads together, the jobs a wave owns in lock step (gloop_run).
   if constexpr (!ONEFB) {

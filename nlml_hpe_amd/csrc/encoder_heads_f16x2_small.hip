@@ -13,7 +13,7 @@
 // same activation split, per output the same K-ascending sequence of the same three MFMAs -- the results are
 // bit-identical to the fused kernel's (tests/test_gpu_parity.py), so everything pinned there holds here.
 //
-// Workspace: two ping-pong buffers of ntiles x max(k16_e0, 64) K-steps x 4 KiB
+// Workspace: two ping-pong buffers of ntiles x max(k16_e0, 64) K-steps x 4 KiB (hx::LayerFrags, encoder_heads_f16x2_dev.h)
 //   fragment (tile, step, face block fb, piece, lane) = 8 f16 = activations k = 16*step + 8*(lane>>5) .. +7 of face
 //   64*tile + 32*fb + (lane&31).
 #include <hip/hip_runtime.h>
@@ -31,7 +31,7 @@ namespace hxs {
 
 using hx::h4;
 using hx::h8;
-constexpr int STEP_UNITS = 2 * 2 * 64;   // h8 units per (tile, K step): 2 face blocks x 2 pieces x 64 lanes = 4 KiB
+using hx::LayerFrags;   // the workspace's geometry; `buf_steps` below = LayerFrags::steps(k16_e0)
 
 // -DHXS_RS1=<n>: ring depth of the split-throughout layer kernels in the one-wave-per-workgroup launches (tools/README.md)
 #ifndef HXS_RS1
@@ -113,9 +113,9 @@ __global__ __launch_bounds__(256) void prepass_kernel(const float* __restrict__ 
         lo[e] = (_Float16)(v[i][e] - (float)hv);
       }
       if (live) {
-        h8* d = ws + ((size_t)tile * buf_steps + (c >> 1)) * STEP_UNITS + (size_t)(fb * 2) * 64 + f + 32 * (c & 1);
+        h8* d = ws + LayerFrags::unit(buf_steps, tile, c >> 1, fb, 0, 0) + f + 32 * (c & 1);   // + the lane that reads it
         d[0] = hi;
-        d[64] = lo;
+        d[LayerFrags::frag(0, 1)] = lo;
       }
     }
   }
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void layer_kernel(LayerArgs a) {
   // bias in accumulator-register order (layout.h), scaled like the weights
   load_bias<NBW, NFB>(acc, blob4 + hdr->b_off[st] + (size_t)job * (NBS * 8) + nb0 * 8, h);
   const h8* w = blob8 + hdr->w_off[st] + (size_t)job * hdr->job_w16[st] + (size_t)nb0 * 128 + lane;   // + step*NBS*128
-  const h8* xi = a.xin + (size_t)tile * a.buf_steps * STEP_UNITS + lane;                              // + step*256
+  const h8* xi = a.xin + LayerFrags::unit(a.buf_steps, tile, 0, 0, 0, 0) + lane;                      // + a K step's units per step
 
   constexpr int D = R - 1;
   h8 wr[R][NBW][2], xr[R][NFB][2];
@@ -170,11 +170,11 @@ __global__ __launch_bounds__(256) void layer_kernel(LayerArgs a) {
     for (int i = 0; i < NBW; ++i)
 #pragma unroll
       for (int p = 0; p < 2; ++p) wr[slot][i][p] = wp[(i * 2 + p) * 64];
-    const h8* xp = xi + (size_t)s * STEP_UNITS;
+    const h8* xp = xi + (size_t)s * LayerFrags::STEP_UNITS;
 #pragma unroll
     for (int fb = 0; fb < NFB; ++fb)
 #pragma unroll
-      for (int p = 0; p < 2; ++p) xr[slot][fb][p] = xp[((fb0 + fb) * 2 + p) * 64];
+      for (int p = 0; p < 2; ++p) xr[slot][fb][p] = xp[LayerFrags::frag(fb0 + fb, p)];
   };
   constexpr int NBS_ = SPLIT ? NBW : 1;
   f32x16 accS[NBS_][NFB];   // the two small products of every K step; added to acc at the end (layer 1: also at its K midpoint,
@@ -281,24 +281,25 @@ __global__ __launch_bounds__(256) void layer_kernel(LayerArgs a) {
           hi[e] = hv;
           lo[e] = (_Float16)(v - (float)hv);
         }
-        h8* frag = a.xout + ((size_t)tile * a.buf_steps + (n >> 4)) * STEP_UNITS + (size_t)((fb0 + fb) * 2) * 64 + f + 32 * ((n >> 3) & 1);
+        h8* frag = a.xout + LayerFrags::unit(a.buf_steps, tile, n >> 4, fb0 + fb, 0, 0) + f + 32 * ((n >> 3) & 1);
         _Float16* d = reinterpret_cast<_Float16*>(frag) + (n & 7);
         *reinterpret_cast<h4*>(d) = hi;
-        *reinterpret_cast<h4*>(d + 64 * 8) = lo;
+        *reinterpret_cast<h4*>(d + LayerFrags::frag(0, 1) * 8) = lo;
       }
 }
 
 // ---- the network's tail (E3, E4, E5 and the three heads: 8 of the 11 layers, 7 % of the FLOP) as ONE launch: a
 // workgroup per 32-FACE BLOCK copies its half of E2's output fragments into the H3 LDS image and runs the fused
 // kernel's tail_stages() on that block (two workgroups per tile: half the sequential stages of the 64-face form).
-// E2's output of face block fb of a tile (256 columns = 16 K steps; `src`: the tile's fragments) -> the H3 LDS image:
+// E2's output of face block fb of a tile (256 columns = 16 K steps; `xin`: the workspace buffer that holds it) -> the H3 LDS image:
 // fragment (step, fb, piece, lane) -> image row 32*fb + (lane & 31), columns 16*step + 8*(lane >> 5) .. +7 of plane `piece`
-__device__ __forceinline__ void h3_image_from_frags(char* lds, const h8* __restrict__ src, int fb, int tid) {
+__device__ __forceinline__ void h3_image_from_frags(char* lds, const h8* __restrict__ xin, int buf_steps, int64_t tile, int fb, int tid) {
+  const h8* src = xin + LayerFrags::unit(buf_steps, tile, 0, 0, 0, 0);   // the tile's fragments
   for (int i = tid; i < 16 * 128; i += 256) {
     const int l = i & 63, piece = (i >> 6) & 1, step = i >> 7;
     const int face = 32 * fb + (l & 31), k = 16 * step + 8 * (l >> 5);
     *reinterpret_cast<h8*>(lds + hx::O_H3 + piece * hx::P_H3 + (face * hx::S_H3 + k) * 2) =
-        src[(size_t)step * STEP_UNITS + (fb * 2 + piece) * 64 + l];
+        src[LayerFrags::in_tile(step, fb, piece, l)];
   }
 }
 
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(256, 1) void tail_kernel(hx::Args a, const h8* __re
   f32x16 acc3[1][1];
   h8 wr3[hx::ring_slots(1, 1)][1][2];
   hx::tail_pre_e3<true>(c, acc3, wr3);                        // E3's bias and first weights fly while the image is copied
-  h3_image_from_frags(lds, xin + (size_t)tile * buf_steps * STEP_UNITS, fbsel, tid);
+  h3_image_from_frags(lds, xin, buf_steps, tile, fbsel, tid);
   __syncthreads();
   hx::tail_stages<true, RESCUE_UP_TO>(c, a, row0, acc3, wr3, fbsel);
 }
@@ -347,43 +348,15 @@ __global__ __launch_bounds__(256, 1) void tail_encoder_kernel(Args a, const h8* 
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
   const int tid = threadIdx.x;
   const Ctx c = make_ctx(a.blob, lds, tid);
-  const int wv = c.wv;
   const int64_t tile = blockIdx.x >> 1, row0 = tile * TILE_FACES;
-  const int fb = blockIdx.x & 1, face0 = 32 * fb;
-  if (row0 + face0 >= a.B) return;                            // no live face in this block (whole workgroup leaves)
+  const int fb = blockIdx.x & 1;
+  if (row0 + 32 * fb >= a.B) return;                          // no live face in this block (whole workgroup leaves)
   f32x16 acc3[1][1];
   h8 wr3[ring_slots(1, 1)][1][2];
   tail_pre_e3<true>(c, acc3, wr3);                            // E3's bias and first weights fly while the image is copied
-  hxs::h3_image_from_frags(lds, xin + (size_t)tile * buf_steps * hxs::STEP_UNITS, fb, tid);
+  hxs::h3_image_from_frags(lds, xin, buf_steps, tile, fb, tid);
   __syncthreads();
-  const bool do4 = wv < 2, do5 = wv == 0;                     // E4: neuron block wv (waves 0, 1); E5: wave 0
-  f32x16 acc4[1][1], acc5[2][1];
-  h8 wr4[6][1][2], wr5[6][2][2];
-  // ---- E3: 256 -> 128, ReLU
-  job_run<1, 1, ST_E3>(c, wv, acc3, wr3, O_H3, P_H3, S_H3, 0, face0);
-  job_store<1, 1, ACT_RELU>(c, acc3, O_H4, P_H4, S_H4, 32 * wv, face0, c.hdr.inv_scale[ST_E3], fetch_hook<2, 1, 1, ST_E4>(c, wv & 1, acc4, wr4));
-  __syncthreads();
-  // ---- E4: 128 -> 64, Tanh (every wave fetches, also the ones that do not run the stage: encoder_heads_f16x2_dev.h)
-  if (do4) job_run<1, 1, ST_E4>(c, wv & 1, acc4, wr4, O_H4, P_H4, S_H4, 0, face0);
-  job_pre<2, 1, ST_E5>(c, 0, acc5, wr5);
-  if (do4) job_store<1, 1, ACT_TANH>(c, acc4, O_H5, P_H5, S_H5, 32 * (wv & 1), face0, c.hdr.inv_scale[ST_E4]);
-  __syncthreads();
-  // ---- E5: 64 -> 9, latent n = 3g+c on row 16g+c (2 blocks), other rows exact zeros
-  if (do5) {
-    job_run<2, 1, ST_E5>(c, 0, acc5, wr5, O_H5, P_H5, S_H5, 0, face0);
-    const float inv = c.hdr.inv_scale[ST_E5];
-    if (a.latent && row0 + face0 + c.f < a.B) {               // f32 latent straight from the accumulators
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int rowi = 32 * nb + (q & 3) + 8 * (q >> 2) + 4 * c.h, g = rowi >> 4, cc = rowi & 15;
-          if (g < 3 && cc < 3) a.latent[(row0 + face0 + c.f) * NLML_LATENT + 3 * g + cc] = acc5[nb][0][q] * inv;
-        }
-    }
-    job_store<2, 1, ACT_NONE, S_LAT>(c, acc5, O_LAT, P_LAT, S_LAT, 0, face0, inv);
-  }
-  __syncthreads();
+  tail_stages<true, 0, false, /*HEADS=*/false>(c, a, row0, acc3, wr3, fb);   // E3, E4, E5: the fused tail's own lines
   latent_block_copy<true>(lds, latws, tile, fb, tid);
 }
 
@@ -428,8 +401,6 @@ __global__ __launch_bounds__(256, 1) void head_kernel(Args a, const char* __rest
 
 }  // namespace hx
 namespace hxs {
-static int e0_k16(int F) { return (F + 2 * hx::XS_COLS - 1) / (2 * hx::XS_COLS) * (2 * hx::XS_STEPS); }   // as pack.cpp
-
 // A layer's launch with NB blocks per wave: the kernel without a second accumulator set (ring R), split throughout (ring RS), or split
 // from a.split_from on (ring R)
 template <int NB, int R, int RS, int NFB = 2>
@@ -443,9 +414,7 @@ static void launch_layer(const LayerArgs& a, bool use_split, dim3 grid, dim3 blo
 
 size_t small_workspace_bytes(int64_t B, int F) {
   if (B <= 0 || F <= 0) return 0;
-  const int64_t ntiles = (B + 63) / 64;
-  const int steps = hxs::e0_k16(F) > 64 ? hxs::e0_k16(F) : 64;
-  return (size_t)2 * ntiles * steps * hxs::STEP_UNITS * 16;
+  return hx::LayerFrags::bytes(B, F);
 }
 
 int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
@@ -457,10 +426,10 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(NLML_E_BADARG, "small-batch path: workspace must be 16-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int ntiles = (int)((B + 63) / 64);
-  const int k16 = e0_k16(F);
-  const int buf_steps = k16 > 64 ? k16 : 64;
+  const int k16 = layout_e0_steps(kLayoutHX, F);
+  const int buf_steps = LayerFrags::steps(k16);
   h8* bufA = reinterpret_cast<h8*>(workspace);
-  h8* bufB = bufA + (size_t)ntiles * buf_steps * STEP_UNITS;
+  h8* bufB = bufA + ntiles * LayerFrags::tile_units(buf_steps);
 
   const K2Input rows = k2_input(x, ldx, raw, normalize, F);
   if (rows.vec4)

@@ -29,7 +29,7 @@
 // Bits: per accumulator the same bias, the same K-ascending MFMA sequence ((w_lo, x_hi), (w_hi, x_lo), (w_hi, x_hi) per K step, single
 // accumulators as in the fused tail), the same epilogue arithmetic => bit-identical to tail_stages() (tests: the fused kernel and the
 // layer-per-launch path against this one, every batch shape).  Input: layer 2's output as operand fragments, written by the trunk-only
-// instantiation of the eight-wave kernel: h3[32-face block][K16 step][piece][lane] x 16 bytes.
+// instantiation of the eight-wave kernel: hx::TrunkFrags, h3[32-face block][K16 step][piece][lane] x 16 bytes.
 #include <hip/hip_runtime.h>
 
 #include "../../include/nlml_hpe.h"
@@ -66,6 +66,23 @@ constexpr int tw_bias_off(int s) {                                              
   for (int t = ST_E3; t < s; ++t) o += tw_bias_n16(t) * 16;
   return o;
 }
+// Where stage s's bias lies in the blob, H.b_off(s), WRITTEN OUT as sums over the stages in front of it: taken from layout.h's functions
+// (as HdrRegs does) the offsets are constants one pass earlier, the copy loops of E4 and E5 below are merged into one block and the
+// whole kernel is laid out anew (profiles/k2_layout_one_definition.md).  The assertion ties these lines to the one definition.
+constexpr uint32_t tw_b_off(int s, uint32_t k16_e0) {
+  int c = (int)(sizeof(Header) / 16), m = 0;
+  for (int t = 0; t < s; ++t) {
+    c += kStages[t].jobs * ((t == ST_E0 ? 0 : kStages[t].k8 * kStages[t].nb * 64 * PIECES) + kStages[t].nb * 8);
+    m += kStages[t].jobs * (t == ST_E0 ? kStages[t].nb * 64 * PIECES : 0);
+  }
+  return c + m * k16_e0 + kStages[s].jobs * ((s == ST_E0 ? 0 : kStages[s].k8 * kStages[s].nb * 64 * PIECES) + (s == ST_E0 ? kStages[s].nb * 64 * PIECES : 0) * k16_e0);
+}
+constexpr bool tw_b_off_is_layouts() {
+  for (int s = 0; s < NUM_STAGES; ++s)
+    if (tw_b_off(s, 0u) != layout_b_off(kLayoutHX, s, 0u) || tw_b_off(s, 88u) != layout_b_off(kLayoutHX, s, 88u)) return false;
+  return true;
+}
+static_assert(tw_b_off_is_layouts(), "the written-out bias offsets are layout.h's");
 constexpr int TW_O_BIAS = 2 * TW_SLOT;
 constexpr int TW_O_LAT = TW_O_BIAS + ((tw_bias_off(NUM_STAGES) + 511) / 512) * 512;
 constexpr int TW_LAT_WAVE = 3 * 2 * 256;
@@ -79,10 +96,10 @@ static_assert(TW_LDS <= 163840, "LDS map");
 //   per head g: H0 (four jobs) | H1 job 0 | H1 job 1 | H1 job 2 | H1 job 3 (a job's two blocks = the two chains) | H2 jobs (0,1) | H2 jobs (2,3) |
 //   H3 (both jobs) | H4
 constexpr int TW_HEAD_UNITS = 9, TW_UNITS = 4 + 3 * TW_HEAD_UNITS;
+constexpr uint32_t tw_job_w16(int s) { return layout_job_w16(kLayoutHX, s, 0u); }   // a tail job's 16-byte units (s > ST_E0: no k16_e0 in it)
 __device__ __forceinline__ void tw_unit(const HdrRegs& H, int idx, uint32_t& off, uint32_t& n16) {
-  constexpr uint32_t J3 = stage_job_w16_const(ST_E3), J4 = stage_job_w16_const(ST_E4), J5 = stage_job_w16_const(ST_E5);
-  constexpr uint32_t K0 = stage_job_w16_const(ST_H0), K1 = stage_job_w16_const(ST_H1), K2 = stage_job_w16_const(ST_H2);
-  constexpr uint32_t K3 = stage_job_w16_const(ST_H3), K4 = stage_job_w16_const(ST_H4);
+  constexpr uint32_t J3 = tw_job_w16(ST_E3), J4 = tw_job_w16(ST_E4), J5 = tw_job_w16(ST_E5);
+  constexpr uint32_t K0 = tw_job_w16(ST_H0), K1 = tw_job_w16(ST_H1), K2 = tw_job_w16(ST_H2), K3 = tw_job_w16(ST_H3), K4 = tw_job_w16(ST_H4);
   static_assert(2 * J3 * 16 == TW_SLOT && 2 * J4 * 16 <= TW_SLOT && J5 * 16 <= TW_SLOT && 4 * K0 * 16 <= TW_SLOT && K1 * 16 <= TW_SLOT &&
                     2 * K2 * 16 == TW_SLOT && 2 * K3 * 16 <= TW_SLOT && K4 * 16 <= TW_SLOT,
                 "a unit fits a buffer");
@@ -226,18 +243,18 @@ __global__ __launch_bounds__(512) void tail_ws_kernel(TwArgs a) {
     f32x4* const bl = reinterpret_cast<f32x4*>(lds + TW_O_BIAS);
 #pragma unroll
     for (int s = ST_E3; s < NUM_STAGES; ++s) {
-      const f32x4* src = blob4 + H.b_off(s);
+      const f32x4* src = blob4 + tw_b_off(s, H.k8_e0);
       for (int i = tid; i < tw_bias_n16(s); i += 512) bl[tw_bias_off(s) / 16 + i] = src[i];
     }
   }
   // this block's h3 (layer 2's output) as operand fragments: 16 K steps x (hi, lo)
-  h8 x3[16][2];
+  h8 x3[TrunkFrags::STEPS][2];
   {
-    const u4* src = a.h3 + (size_t)fbg * (16 * 2 * 64) + lane;
+    const u4* src = a.h3 + TrunkFrags::unit(fbg, 0, 0, 0) + lane;
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks)
+    for (int ks = 0; ks < TrunkFrags::STEPS; ++ks)
 #pragma unroll
-      for (int p = 0; p < 2; ++p) x3[ks][p] = __builtin_bit_cast(h8, src[(ks * 2 + p) * 64]);
+      for (int p = 0; p < 2; ++p) x3[ks][p] = __builtin_bit_cast(h8, src[TrunkFrags::frag(0, ks, p)]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -283,7 +300,7 @@ __global__ __launch_bounds__(512) void tail_ws_kernel(TwArgs a) {
   constexpr std::integral_constant<int, ACT_RELU> RELU{};
   constexpr std::integral_constant<int, ACT_TANH> TANH{};
   const float inv3 = H.inv_scale[ST_E3], inv4 = H.inv_scale[ST_E4], inv5 = H.inv_scale[ST_E5];
-  constexpr int JB3 = (int)(stage_job_w16_const(ST_E3) * 16), JB4 = (int)(stage_job_w16_const(ST_E4) * 16);
+  constexpr int JB3 = (int)(tw_job_w16(ST_E3) * 16), JB4 = (int)(tw_job_w16(ST_E4) * 16);
 
   // ---- E3: 256 -> 128, ReLU (two jobs per unit)
   h8 x4[8][2];
@@ -359,7 +376,7 @@ __global__ __launch_bounds__(512) void tail_ws_kernel(TwArgs a) {
         xin[0][pc] = __builtin_bit_cast(h8, u4{h == 0 ? t[0] : 0u, h == 0 ? t[1] : 0u, 0u, 0u});
       }
       LdsC* const b = bias0 + tw_bias_off(ST_H0) + (4 * g) * 128;
-      constexpr int JB = (int)(stage_job_w16_const(ST_H0) * 16);
+      constexpr int JB = (int)(tw_job_w16(ST_H0) * 16);
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         tw_job2<1>(acc, wl + (2 * jj) * JB, wl + (2 * jj + 1) * JB, 2048, b + (2 * jj) * 128, b + (2 * jj + 1) * 128, xin);
@@ -384,7 +401,7 @@ __global__ __launch_bounds__(512) void tail_ws_kernel(TwArgs a) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {  // H2_g: 256 -> 128, ReLU; two jobs per unit
       TW_BEGIN(u0 + 5 + u);
-      constexpr int JB = (int)(stage_job_w16_const(ST_H2) * 16);
+      constexpr int JB = (int)(tw_job_w16(ST_H2) * 16);
       LdsC* const b = bias0 + tw_bias_off(ST_H2) + (4 * g + 2 * u) * 128;
       tw_job2p<16>(acc, wl, wl + JB, 2048, b, b + 128, xb);
       TW_MID();
@@ -396,7 +413,7 @@ __global__ __launch_bounds__(512) void tail_ws_kernel(TwArgs a) {
     {  // H3_g: 128 -> 64, ReLU; both jobs
       TW_BEGIN(u0 + 7);
       LdsC* const b = bias0 + tw_bias_off(ST_H3) + (2 * g) * 128;
-      tw_job2p<8>(acc, wl, wl + (int)(stage_job_w16_const(ST_H3) * 16), 2048, b, b + 128, xc);
+      tw_job2p<8>(acc, wl, wl + (int)(tw_job_w16(ST_H3) * 16), 2048, b, b + 128, xc);
       TW_MID();
       emit(RELU, acc[0], i3, xd[0], xd[1]);
       emit(RELU, acc[1], i3, xd[2], xd[3]);

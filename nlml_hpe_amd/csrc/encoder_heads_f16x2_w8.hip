@@ -74,7 +74,7 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
   constexpr int NB = 2, NFB = 2;
   constexpr int WSTEP = 4 * 2 * 64;                 // a layer-0 job has four blocks x two pieces per K step
   const int F = a.F;
-  const int nslab = (int)c.hdr.k8_e0 / XS_STEPS;   // even (pack.cpp)
+  const int nslab = (int)c.hdr.k8_e0 / XS_STEPS;   // even (layout.h, layout_e0_steps)
 
   const int srow = tid >> 3, scol = (tid & 7) * 4;
   int64_t r = row0 + srow;
@@ -259,7 +259,7 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
 #endif
 
 // TRUNK = true (round 5, second half): the launch ends with layer 2 -- its output goes to a.h3ws as MFMA operand fragments
-// ([32-face block][K16 step][piece][lane] x 16 bytes: 1 KB per face) and the rest of the network runs as its own launch with the
+// (TrunkFrags, encoder_heads_f16x2_dev.h: [32-face block][K16 step][piece][lane] x 16 bytes, 1 KB per face) and the rest of the network runs as its own launch with the
 // weights streaming through LDS ONCE per 256 faces (encoder_heads_f16x2_tailws.hip).  All eight waves work to the end of this launch.
 template <bool VEC4, bool NORM, bool TRUNK = false>
 __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
     W8S(10);
     if constexpr (TRUNK) {   // h3 = relu(E2) straight from the accumulators to the hand-over buffer (no LDS image, no barrier)
       typedef unsigned u4_ __attribute__((ext_vector_type(4)));
-      u4_* const dst = reinterpret_cast<u4_*>(a.h3ws) + (size_t)blockIdx.x * (2 * 16 * 2 * 64) + c.lane;
+      u4_* const dst = reinterpret_cast<u4_*>(a.h3ws) + (size_t)blockIdx.x * TrunkFrags::TILE_UNITS + c.lane;   // the tile's first unit, this lane
 #pragma unroll
       for (int fb = 0; fb < 2; ++fb) {
         h8 fr[2][2];
@@ -363,7 +363,9 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
         for (int p = 0; p < 2; ++p)
 #pragma unroll
           for (int pc = 0; pc < 2; ++pc)
-            dst[((fb * 16 + 4 * jw + 2 * nbh + p) * 2 + pc) * 64] = __builtin_bit_cast(u4_, fr[p][pc]);
+            // TrunkFrags::frag(fb, 4 * jw + 2 * nbh + p, pc) written out: with the step summed first the stores' addresses are formed in
+            // another order and the listing moves (profiles/k2_layout_one_definition.md)
+            dst[((fb * TrunkFrags::STEPS + 4 * jw + 2 * nbh + p) * PIECES + pc) * 64] = __builtin_bit_cast(u4_, fr[p][pc]);
       }
       return;
     }
@@ -393,7 +395,7 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
 // ---- the strict-fast forward as trunk launch + streamed tail launch (+ the f32 re-evaluation launch) -------------------------------
 size_t tailws_workspace_bytes(int64_t B, int F) {
   if (B <= 0 || F <= 0) return 0;
-  return (size_t)((B + TILE_FACES - 1) / TILE_FACES) * (2 * 16 * 2 * 1024);   // 1 KB per face of whole 64-face tiles
+  return hx::TrunkFrags::bytes(B);
 }
 
 int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,

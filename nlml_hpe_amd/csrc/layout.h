@@ -28,6 +28,7 @@
 // Blob = header (256 B) | stage 0 weights | stage 0 bias | stage 1 ... | tail pad.
 // Header words (uint32): see Header below.  All offsets are in units of 16 bytes from blob start.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace nlml {
@@ -70,7 +71,7 @@ struct Header {
   uint32_t version;
   uint32_t F;          // encoder input width
   uint32_t mode;       // NLML_MODE_*
-  uint32_t k8_e0;      // K steps of layer 0: ceil(F/64)*8 (K zero-padded to whole pairs of 32-column x slabs)
+  uint32_t k8_e0;      // K steps of layer 0: layout_e0_steps() (K zero-padded to whole pairs of x slabs)
   uint32_t total16;    // blob size in 16-byte units (incl. tail pad)
   uint32_t w_off[NUM_STAGES];  // weights of stage, 16-byte units
   uint32_t b_off[NUM_STAGES];  // bias of stage, 16-byte units
@@ -213,5 +214,58 @@ static_assert(O_HB + 2 * P_HB <= O_LAT, "LDS map");
 static_assert(O_HD + 2 * P_HD <= O_LAT, "LDS map");
 
 }  // namespace hx
+
+// ------------------------------------------------------------------------------------------
+// The blob's layout arithmetic, ONCE: the packer sizes the blob and fills the header's k8_e0 / w_off / b_off / job_w16 / total16 from these
+// functions, and the split-f16 kernels compute the same offsets from the header's k8_e0 alone instead of reading them
+// (encoder_heads_f16x2_dev.h HdrRegs).  A mode family is its stage table, the 16-byte pieces per weight fragment, the K step width
+// and the x slab's columns; T is the type the units are counted in (uint32_t as the header stores them, size_t for a buffer's size).
+#if defined(__HIPCC__)
+#define NLML_HOST_DEVICE __host__ __device__
+#else
+#define NLML_HOST_DEVICE
+#endif
+
+struct BlobLayout {
+  const StageDesc* stages;
+  int pieces;     // 16-byte pieces per (K step, neuron block, lane): 1, or hi and lo
+  int kstep;      // k values per K step
+  int xs_cols;    // columns of an x slab
+};
+constexpr BlobLayout kLayoutF32 = {kStages, 1, 8, XS_COLS};
+constexpr BlobLayout kLayoutBF16 = {bf::kStages, 1, 16, bf::XS_COLS};
+constexpr BlobLayout kLayoutHX = {hx::kStages, hx::PIECES, 16, hx::XS_COLS};
+constexpr int BLOB_TAIL_PAD16 = 4096;   // 64 KiB: the K loops prefetch up to 7 steps (<= 8 KiB) past a job's end
+
+// K steps of layer 0: K is padded (zero weights) to whole PAIRS of x slabs, so the kernels' slab loops have no partial-slab case and
+// their two staging register sets alternate statically
+NLML_HOST_DEVICE constexpr int layout_e0_steps(const BlobLayout& L, int F) {
+  return (F + 2 * L.xs_cols - 1) / (2 * L.xs_cols) * (2 * L.xs_cols / L.kstep);
+}
+// 16-byte units of one job's weights in stage s: 16 bytes per lane (and piece) for every K step and neuron block
+template <class T = uint32_t>
+NLML_HOST_DEVICE constexpr T layout_job_w16(const BlobLayout& L, int s, T k_e0) {
+  return (s == ST_E0 ? k_e0 : (T)L.stages[s].k8) * (T)(L.stages[s].nb * 64 * L.pieces);
+}
+// where stage s's weights start (s = NUM_STAGES: where the tail pad starts); a job's bias is 2 halves x 16 floats per neuron block
+template <class T = uint32_t>
+NLML_HOST_DEVICE constexpr T layout_w_off(const BlobLayout& L, int s, T k_e0) {
+  T o = sizeof(Header) / 16;
+  for (int t = 0; t < s; ++t) o += (T)L.stages[t].jobs * (layout_job_w16<T>(L, t, k_e0) + (T)(L.stages[t].nb * 8));
+  return o;
+}
+template <class T = uint32_t>
+NLML_HOST_DEVICE constexpr T layout_b_off(const BlobLayout& L, int s, T k_e0) {
+  return layout_w_off<T>(L, s, k_e0) + (T)L.stages[s].jobs * layout_job_w16<T>(L, s, k_e0);
+}
+template <class T = uint32_t>
+NLML_HOST_DEVICE constexpr T layout_total16(const BlobLayout& L, T k_e0) {
+  return layout_w_off<T>(L, NUM_STAGES, k_e0) + (T)BLOB_TAIL_PAD16;
+}
+// NLML_MODE_F16X2S: the NLML_MODE_F16X2 image, 256 bytes, then a complete NLML_MODE_F32 image -- what the re-evaluation launch of
+// the strict-fast mode reads (faces whose activations leave f16's range, when a tile has many: encoder_heads.hip)
+constexpr size_t layout_strict_f32_image16(int F) {
+  return layout_total16<size_t>(kLayoutHX, (size_t)layout_e0_steps(kLayoutHX, F)) + 16;
+}
 
 }  // namespace nlml

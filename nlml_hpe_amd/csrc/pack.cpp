@@ -43,23 +43,10 @@ inline int row_of(const JobSrc& j, int i) {
 
 static bool split_f16(int mode) { return mode == NLML_MODE_F16X2 || mode == NLML_MODE_F16X2S; }
 
-// Layer 0's K is padded (zero weights) to whole PAIRS of x slabs (2 x XS_COLS columns), so the kernel's
-// slab loop has no partial-slab case and its two staging register sets alternate statically.
-static int e0_k8(int F) { return (F + 2 * XS_COLS - 1) / (2 * XS_COLS) * (2 * XS_STEPS); }
-// bf16 mode: K steps of 16, x slabs of 64 columns, slab pairs => K padded to 128 columns
-static int e0_k16(int F) { return (F + 2 * bf::XS_COLS - 1) / (2 * bf::XS_COLS) * (2 * bf::XS_STEPS); }
-
-// split-f16 mode: K steps of 16, x slabs of 32 columns, slab pairs => K padded to 64 columns
-static int e0_k16x2(int F) { return (F + 2 * hx::XS_COLS - 1) / (2 * hx::XS_COLS) * (2 * hx::XS_STEPS); }
-
-static const StageDesc& stage_of(int mode, int s) {
-  return mode == NLML_MODE_BF16 ? bf::kStages[s] : (split_f16(mode) ? hx::kStages[s] : kStages[s]);
+// the blob layout of a mode (layout.h)
+static const BlobLayout& layout_of(int mode) {
+  return mode == NLML_MODE_BF16 ? kLayoutBF16 : (split_f16(mode) ? kLayoutHX : kLayoutF32);
 }
-static int e0_steps(int mode, int F) {
-  return mode == NLML_MODE_BF16 ? e0_k16(F) : (split_f16(mode) ? e0_k16x2(F) : e0_k8(F));
-}
-static int pieces_of(int mode) { return split_f16(mode) ? hx::PIECES : 1; }
-
 
 // round-to-nearest-even f32 -> f16 bits and back (host side of the split; subnormals kept, overflow -> inf)
 static uint16_t to_f16(float f) {
@@ -100,30 +87,22 @@ static uint16_t to_bf16(float f) {
 }
 
 size_t blob_bytes_for(int F, int mode) {
-  size_t units = sizeof(Header) / 16;
-  for (int s = 0; s < NUM_STAGES; ++s) {
-    const StageDesc& d = stage_of(mode, s);
-    int k8 = (s == ST_E0) ? e0_steps(mode, F) : d.k8;
-    units += (size_t)d.jobs * k8 * d.nb * 64 * pieces_of(mode);      // weights: 16 bytes per lane (and piece)
-    units += (size_t)d.jobs * d.nb * 2 * 4;        // bias: 2 halves x 16 floats
-  }
-  units += 4096;  // 64 KiB tail pad: the K loops prefetch up to 7 steps (<= 8 KiB) past a job's end
-  // NLML_MODE_F16X2S: the NLML_MODE_F16X2 image, 256 bytes, then a complete NLML_MODE_F32 image -- what the re-evaluation launch of
-  // the strict-fast mode reads (faces whose activations leave f16's range, when a tile has many: encoder_heads.hip).  The mode of a
-  // blob is still read off its size.
-  if (mode == NLML_MODE_F16X2S) units += 16 + blob_bytes_for(F, NLML_MODE_F32) / 16;
+  const BlobLayout& L = layout_of(mode);
+  size_t units = layout_total16<size_t>(L, (size_t)layout_e0_steps(L, F));
+  // NLML_MODE_F16X2S carries an f32 image behind the split-f16 one (layout.h).  The mode of a blob is still read off its size.
+  if (mode == NLML_MODE_F16X2S) units = layout_strict_f32_image16(F) + blob_bytes_for(F, NLML_MODE_F32) / 16;
   return units * 16;
 }
 
-size_t strict_f32_image_offset(int F) { return blob_bytes_for(F, NLML_MODE_F16X2) + 256; }
+size_t strict_f32_image_offset(int F) { return layout_strict_f32_image16(F) * 16; }
 
 int pack_blob(int F, int mode, const float* const enc_w[6], const float* const enc_b[6],
               const float* const head_w[3][5], const float* const head_b[3][5],
               void* blob, size_t blob_bytes) {
   if (F <= 0 || !blob) return fail(NLML_E_BADARG, "pack: bad F or null blob");
   const bool bf16 = mode == NLML_MODE_BF16, f16x2 = split_f16(mode);
-  const int kw = (bf16 || f16x2) ? 16 : 8;        // K step width
-  const int pieces = pieces_of(mode);
+  const BlobLayout& L = layout_of(mode);
+  const int kw = L.kstep, pieces = L.pieces;
   const int per_half = kw / 2;         // k values per lane half
   const size_t need = blob_bytes_for(F, mode);
   if (blob_bytes < need) return fail(NLML_E_BADARG, "pack: blob buffer too small");
@@ -140,19 +119,20 @@ int pack_blob(int F, int mode, const float* const enc_w[6], const float* const e
   hdr->version = BLOB_VERSION;
   hdr->F = (uint32_t)F;
   hdr->mode = (uint32_t)mode;
-  hdr->k8_e0 = (uint32_t)e0_steps(mode, F);
+  const uint32_t k_e0 = (uint32_t)layout_e0_steps(L, F);
+  hdr->k8_e0 = k_e0;
 
   const int encN[6] = {1024, 512, 256, 128, 64, 9};
   const int encK[6] = {F, 1024, 512, 256, 128, 64};
   const int headN[5] = {128, 256, 128, 64, 1};
   const int headK[5] = {3, 128, 256, 128, 64};
 
-  size_t cur = sizeof(Header) / 16;  // 16-byte units
   for (int s = 0; s < NUM_STAGES; ++s) {
-    const StageDesc& d = stage_of(mode, s);
-    const int k8 = (s == ST_E0) ? e0_steps(mode, F) : d.k8;
-    const size_t job_w16 = (size_t)k8 * d.nb * 64 * pieces;
-    hdr->w_off[s] = (uint32_t)cur;
+    const StageDesc& d = L.stages[s];
+    const int k8 = (s == ST_E0) ? (int)k_e0 : d.k8;
+    const size_t cur = hdr->w_off[s] = layout_w_off(L, s, k_e0);   // 16-byte units
+    const size_t job_w16 = hdr->job_w16[s] = layout_job_w16(L, s, k_e0);
+    const size_t b_off = hdr->b_off[s] = layout_b_off(L, s, k_e0);
     // split-f16 mode: one power-of-two scale per stage puts the largest |w| in [128, 256), so the lo pieces of all
     // but the tiniest weights are normal f16 numbers; bias is scaled alike, the kernel multiplies by inv_scale.
     float scale = 1.0f;
@@ -176,9 +156,6 @@ int pack_blob(int F, int mode, const float* const enc_w[6], const float* const e
       }
     }
     hdr->inv_scale[s] = 1.0f / scale;
-    hdr->job_w16[s] = (uint32_t)job_w16;
-    const size_t b_off = cur + (size_t)d.jobs * job_w16;
-    hdr->b_off[s] = (uint32_t)b_off;
 
     for (int j = 0; j < d.jobs; ++j) {
       JobSrc src{};
@@ -226,27 +203,11 @@ int pack_blob(int F, int mode, const float* const enc_w[6], const float* const e
             b[(nb * 2 + h) * 16 + q] = n >= 0 ? src.b[n] * scale : 0.0f;
           }
     }
-    cur = b_off + (size_t)d.jobs * d.nb * 8;
   }
   hdr->total16 = (uint32_t)(need / 16);
   if (mode == NLML_MODE_F16X2S) {   // the f32 image behind the split-f16 one
     const size_t off = strict_f32_image_offset(F);
     if (int rc = pack_blob(F, NLML_MODE_F32, enc_w, enc_b, head_w, head_b, reinterpret_cast<char*>(blob) + off, blob_bytes - off)) return rc;
-  }
-  if (f16x2) {   // the split-f16 kernels compute these offsets from k16_e0 instead of reading them (encoder_heads_f16x2_dev.h)
-    for (int s = 0; s < NUM_STAGES; ++s) {
-      const uint32_t k = hdr->k8_e0;
-      const uint32_t jw = (s == ST_E0) ? (uint32_t)hx::kStages[s].nb * 64 * hx::PIECES * k
-                                       : (uint32_t)hx::kStages[s].k8 * hx::kStages[s].nb * 64 * hx::PIECES;
-      uint32_t w = sizeof(Header) / 16;
-      for (int t = 0; t < s; ++t) {
-        const uint32_t jt = (t == ST_E0) ? (uint32_t)hx::kStages[t].nb * 64 * hx::PIECES * k
-                                         : (uint32_t)hx::kStages[t].k8 * hx::kStages[t].nb * 64 * hx::PIECES;
-        w += hx::kStages[t].jobs * (jt + hx::kStages[t].nb * 8);
-      }
-      if (hdr->w_off[s] != w || hdr->job_w16[s] != jw || hdr->b_off[s] != w + hx::kStages[s].jobs * jw)
-        return fail(NLML_E_BADARG, "pack: blob layout differs from the split-f16 kernels' offset formula");
-    }
   }
   return 0;
 }

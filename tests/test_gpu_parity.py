@@ -1675,6 +1675,18 @@ def test_streamed_tail_path_with_the_shipped_heads_and_a_padded_row_stride(head_
     assert torch.equal(small[0], o) and torch.equal(small[1], l)
 
 
+def test_streamed_tail_path_at_another_input_width(head_sds, device):
+    """F = 136: layer 0 has 12 K steps of 16 instead of 1,404's 88, and every offset the streamed tail computes for its units and its
+    bias table moves with that count.  65 faces = one full tile and a tile of one face; pose and latent against the fused kernel, bit for bit."""
+    F, B = 136, 65
+    sd = synth.encoder_state_dict(F, seed=0)
+    blob = _blob_hx(sd, head_sds, device, "f16x2s")
+    x = torch.from_numpy(synth.features(B, F, seed=31)).to(device)
+    want = ops.encoder_heads_fwd(x, blob, F, return_latent=True)
+    o, l, _ = _wide_call("nlml_encoder_heads_fwd_streamed", x, B, blob, device, extra=(F, B, F), want_valid=False)
+    assert torch.equal(want[0], o) and torch.equal(want[1], l)
+
+
 def test_streamed_tail_path_refuses_what_it_does_not_take(head_sds, device):
     """Strict-fast blob only, 16-byte aligned rows with F % 4 == 0, a workspace of the documented size: anything else is NLML_E_BADARG."""
     from nlml_hpe_amd import _lib
