@@ -263,12 +263,44 @@ int nlml_landmarks_to_pose_streamed(const float* raw, int64_t B, int normalize,
                                     const void* blob, size_t blob_bytes, float* out, float* latent, uint8_t* valid,
                                     void* workspace, size_t ws_bytes, void* stream);
 
+/* The same forward in NLML_MODE_F16X2S with FOUR TILES PER WORKGROUP in ONE launch (+ the f32 re-evaluation launch): a workgroup runs
+ * the eight-wave kernel's layers 0-2 over four 64-face tiles one after the other, parks each tile's layer-2 output in its own slice of
+ * `workspace` (the _streamed form's fragments, 1 KB per face; written and read back by that workgroup alone), then runs the _streamed
+ * form's tail once over its 256 faces (csrc/encoder_heads_f16x2_w8.hip, encoder_heads_f16x2_w8q_kernel).  No workgroup waits for another.
+ * Bit-identical to nlml_encoder_heads_fwd / nlml_landmarks_to_pose with the same blob; any B >= 0; the _streamed forms' input layout,
+ * workspace (nlml_encoder_heads_workspace_bytes(B, F) covers it: the hand-over is the same 1 KB per face of whole 64-face tiles) and
+ * refusals (NLML_E_BADARG for a blob of another mode, a small or misaligned workspace, rows that cannot be read 16 bytes at a time).
+ * Measurements and what picks it: DESIGN.md section 3.
+ */
+int nlml_encoder_heads_fwd_quad(const float* x, int64_t ldx, int64_t B, int F,
+                                const void* blob, size_t blob_bytes, float* out, float* latent, uint8_t* valid,
+                                void* workspace, size_t ws_bytes, void* stream);
+int nlml_landmarks_to_pose_quad(const float* raw, int64_t B, int normalize,
+                                const void* blob, size_t blob_bytes, float* out, float* latent, uint8_t* valid,
+                                void* workspace, size_t ws_bytes, void* stream);
+/* The _ws entry points' split of a strict-fast batch: *quad_faces = the leading faces that go through the four-tile kernel on a device
+ * of `cus` compute units -- whole rounds of one 256-face workgroup per unit, ((B / 64) / (4 cus)) * cus * 256 -- the others go through
+ * the fused kernel.  Host arithmetic, no HIP call.  B < 0, cus <= 0 or a NULL quad_faces: NLML_E_BADARG (and *quad_faces = 0).
+ * nlml_k2_quad_faces: what the _ws entry points would send through the four-tile kernel of a strict-fast batch of B faces with 16-byte
+ * readable rows on the calling thread's current device, under this process's environment (NLML_K2_QUAD_MIN, NLML_K2_STREAMED_MIN: below),
+ * and in *ws_bytes (may be NULL) the workspace that part needs -- what a host asks to learn whether a workspace is worth allocating. */
+int nlml_k2_quad_split(int64_t B, int cus, int64_t* quad_faces);
+int nlml_k2_quad_faces(int64_t B, int64_t* quad_faces, size_t* ws_bytes);
+
 /* THE FORWARD WITH A WORKSPACE: picks the fastest of the paths above for the batch size and the blob's mode (split-f16 modes: the
  * layer-per-launch path up to 4,096 faces; the fused kernel otherwise and for the other modes, which ignore the workspace; the
- * trunk + streamed-tail path only when the environment asks for it, NLML_K2_STREAMED_MIN=<faces>).  Same bits whichever path runs.  For hosts that
+ * trunk + streamed-tail path only when the environment asks for it, NLML_K2_STREAMED_MIN=<faces>).  A strict-fast batch with rows readable
+ * 16 bytes at a time is split (nlml_k2_quad_split with the device's compute-unit count, asked once per device): the leading whole rounds
+ * through the four-tile kernel, the rest through the fused kernel on offset pointers in the same stream, one re-evaluation launch over
+ * all B -- if the workspace holds the quad part's hand-over (1 KB per face); with a smaller workspace the call does what it did without
+ * the path, so it never fails for want of workspace where the fused kernel would run.  NLML_K2_QUAD_MIN=<faces> (read once): negative
+ * switches the path off; otherwise the rule becomes "B >= faces: the whole batch through the four-tile kernel" (then a small workspace
+ * IS refused).  NLML_K2_STREAMED_MIN wins where both apply.  Same bits whichever path runs.  For hosts that
  * want one call for every batch size; the packaged host layer makes the same choice in Python (nlml_hpe_amd/model.py, `small_batch_max`)
- * and calls the plain / _small forms, which is also what bench.py times.
- * `workspace`: at least nlml_encoder_heads_workspace_bytes(B, F) bytes (>= the _small and _streamed paths' needs), 16-byte aligned.
+ * and calls the plain / _small forms, and the _ws form where nlml_k2_quad_faces says a quad part exists -- which is what bench.py times.
+ * The plain entry points (nlml_encoder_heads_fwd, nlml_landmarks_to_pose) have no workspace argument, cannot take the four-tile path and
+ * stay on the fused kernel.
+ * `workspace`: at least nlml_encoder_heads_workspace_bytes(B, F) bytes (>= the _small, _streamed and _quad paths' needs), 16-byte aligned.
  */
 size_t nlml_encoder_heads_workspace_bytes(int64_t B, int F);
 int nlml_encoder_heads_fwd_ws(const float* x, int64_t ldx, int64_t B, int F,

@@ -24,7 +24,7 @@ _FWD_WS = [C.c_void_p, C.c_size_t]
 
 
 def _k2_forwards():
-    for form, ws in (("", []), ("_small", _FWD_WS), ("_streamed", _FWD_WS), ("_ws", _FWD_WS)):
+    for form, ws in (("", []), ("_small", _FWD_WS), ("_streamed", _FWD_WS), ("_quad", _FWD_WS), ("_ws", _FWD_WS)):
         yield "nlml_encoder_heads_fwd" + form, (C.c_int, _FWD_X + _FWD_OUT + ws + [C.c_void_p])
         yield "nlml_landmarks_to_pose" + form, (C.c_int, _FWD_RAW + _FWD_OUT + ws + [C.c_void_p])
 
@@ -68,6 +68,8 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_encoder_heads_small_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "nlml_encoder_heads_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "nlml_k2_quad_split": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    "nlml_k2_quad_faces": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
     "nlml_tucker_gradient_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "nlml_video_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

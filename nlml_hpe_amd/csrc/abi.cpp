@@ -1,5 +1,6 @@
 // abi.cpp -- the extern "C" surface declared in include/nlml_hpe.h: argument checks, then the
-// launchers in the .hip files.  No allocation, no synchronisation, no global mutable state.
+// launchers in the .hip files.  No allocation, no synchronisation, no global mutable state beyond values read once and kept (the
+// NLML_K2_* environment variables, a device's compute-unit count).
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -23,6 +24,11 @@ int fail(int code, const char* msg) {
 int hip_launch_status() {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+}
+// the dispatcher's split of a strict-fast batch (abi_internal.h; nlml_k2_quad_split)
+int64_t k2_quad_faces(int64_t B, int cus) {
+  if (B <= 0 || cus <= 0) return 0;
+  return (B / TILE_FACES) / (4 * (int64_t)cus) * cus * (4 * TILE_FACES);
 }
 }  // namespace nlml
 
@@ -173,10 +179,48 @@ static int64_t streamed_min() {
   return v;
 }
 
+// The four-tile kernel (encoder_heads_f16x2_w8.hip, encoder_heads_f16x2_w8q_kernel: a workgroup runs the trunk over four tiles and the
+// streamed tail once) pays where every compute unit gets a whole workgroup of it: AUTO sends whole rounds of one workgroup per unit
+// through it and the rest of the batch through the fused kernel (k2_quad_faces), if the caller's workspace holds the quad part's
+// hand-over.  NLML_K2_QUAD_MIN=<faces>: negative switches the path off, otherwise batches from that size on go through it whole.
+// NLML_K2_QUAD_CUS=<n> stands in for the device's compute-unit count (tests: a split at a small batch).
+static int64_t env_i64(const char* name, int64_t unset) {
+  const char* e = getenv(name);
+  return e && e[0] ? (int64_t)atoll(e) : unset;
+}
+static const int64_t kQuadMinUnset = INT64_MIN;
+static int64_t quad_min() {
+  static const int64_t v = env_i64("NLML_K2_QUAD_MIN", kQuadMinUnset);
+  return v;
+}
+static int device_cus() {   // of the calling thread's current device, asked once per device
+  static const int64_t forced = env_i64("NLML_K2_QUAD_CUS", 0);
+  if (forced > 0) return (int)forced;
+  constexpr int kMaxDev = 64;
+  static int cus[kMaxDev];   // 0: not asked yet (a race writes the same value twice)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 0;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = -1;
+    cus[dev] = n;
+  }
+  return cus[dev] > 0 ? cus[dev] : 0;
+}
+
+
+// The part of a strict-fast batch of B faces with 16-byte readable rows that AUTO sends through the four-tile kernel on the current device
+static int64_t auto_quad_faces(int64_t B) {
+  if (B <= 0) return 0;
+  if (B > kSmallMax && streamed_min() >= 0 && B >= streamed_min()) return 0;   // the streamed path was asked for: it wins
+  if (quad_min() != kQuadMinUnset) return quad_min() >= 0 && B >= quad_min() ? B : 0;
+  return B > kSmallMax ? k2_quad_faces(B, device_cus()) : 0;                   // (the layer-per-launch path's sizes stay its own)
+}
+
 // The call forms: the fused kernel of the blob's mode; the split-f16 modes' layer-per-launch path (small batches); the strict-fast
-// mode's trunk + streamed tail (encoder_heads_f16x2_w8.hip TRUNK, encoder_heads_f16x2_tailws.hip); AUTO = the fastest of the three for
-// the batch size and the blob's mode, through a caller-provided workspace.
-enum K2Form { K2_FUSED, K2_SMALL, K2_STREAMED, K2_AUTO };
+// mode's trunk + streamed tail (encoder_heads_f16x2_w8.hip TRUNK, encoder_heads_f16x2_tailws.hip); the strict-fast mode's four-tile
+// kernel over the whole batch; AUTO = the fastest of them for the batch size and the blob's mode, through a caller-provided workspace.
+enum K2Form { K2_FUSED, K2_SMALL, K2_STREAMED, K2_QUAD, K2_AUTO };
 
 // landmarks: the input is raw [B,468,3] (x, ldx unused), else the feature rows x / ldx (raw null).  workspace / ws_bytes are read by the
 // forms that need one.
@@ -192,17 +236,26 @@ static int k2_forward(K2Form form, bool landmarks, const float* x, int64_t ldx, 
   if (int rc = check_blob_args(B, F, blob, blob_bytes, out, &mode)) return rc;
   if (form == K2_SMALL && !split_f16(mode)) return fail(NLML_E_BADARG, "small-batch path: NLML_MODE_F16X2 / NLML_MODE_F16X2S blob only");
   if (form == K2_STREAMED && mode != NLML_MODE_F16X2S) return fail(NLML_E_BADARG, "streamed-tail path: NLML_MODE_F16X2S blob only");
+  if (form == K2_QUAD && mode != NLML_MODE_F16X2S) return fail(NLML_E_BADARG, "quad path: NLML_MODE_F16X2S blob only");
   if (no_input) return fail(NLML_E_BADARG, no_input);
   const int split = mode == NLML_MODE_F16X2S;
+  int64_t quad_faces = B;   // K2_QUAD: the whole batch
   if (form == K2_AUTO) {
-    if (split_f16(mode) && B <= kSmallMax) form = K2_SMALL;
-    else if (split && streamed_min() >= 0 && B >= streamed_min() && k2_input(x, ldx, raw, normalize, F).vec4) form = K2_STREAMED;
+    const bool wide = split && k2_input(x, ldx, raw, normalize, F).vec4;   // what the streamed and the quad path take
+    quad_faces = wide ? auto_quad_faces(B) : 0;
+    // whole rounds only if the workspace takes them -- never a failure the fused kernel would not have; asked for by the environment, always
+    const bool fits = workspace && ws_bytes >= quad_workspace_bytes(quad_faces) && !(reinterpret_cast<uintptr_t>(workspace) & 15);
+    if (quad_faces > 0 && (fits || quad_min() != kQuadMinUnset)) form = K2_QUAD;
+    else if (split_f16(mode) && B <= kSmallMax) form = K2_SMALL;
+    else if (wide && streamed_min() >= 0 && B >= streamed_min()) form = K2_STREAMED;
     else form = K2_FUSED;
   }
   if (form == K2_SMALL)
     return launch_encoder_heads_f16x2_small(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, split, stream);
   if (form == K2_STREAMED)
     return launch_encoder_heads_f16x2_tailws(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, stream);
+  if (form == K2_QUAD)
+    return launch_encoder_heads_f16x2_w8_mixed(x, ldx, raw, normalize, B, F, blob, out, latent, valid, quad_faces, workspace, ws_bytes, stream);
   if (mode == NLML_MODE_BF16) return launch_encoder_heads_bf16(x, ldx, raw, normalize, B, F, blob, out, latent, valid, stream);
   if (split_f16(mode)) return launch_encoder_heads_f16x2(x, ldx, raw, normalize, B, F, blob, out, latent, valid, split, stream);
   return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, blob, out, latent, valid, nullptr, nullptr, stream);
@@ -247,6 +300,34 @@ int nlml_encoder_heads_fwd_streamed(const float* x, int64_t ldx, int64_t B, int 
 int nlml_landmarks_to_pose_streamed(const float* raw, int64_t B, int normalize, const void* blob, size_t blob_bytes,
                                     float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
   return k2_forward(K2_STREAMED, true, nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
+}
+
+int nlml_encoder_heads_fwd_quad(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
+                                float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
+  return k2_forward(K2_QUAD, false, x, ldx, nullptr, 0, B, F, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
+}
+
+int nlml_landmarks_to_pose_quad(const float* raw, int64_t B, int normalize, const void* blob, size_t blob_bytes,
+                                float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes, void* stream) {
+  return k2_forward(K2_QUAD, true, nullptr, 0, raw, normalize, B, NLML_F_REFERENCE, blob, blob_bytes, out, latent, valid, workspace, ws_bytes, stream);
+}
+
+int nlml_k2_quad_split(int64_t B, int cus, int64_t* quad_faces) {
+  if (!quad_faces) return fail(NLML_E_BADARG, "k2_quad_split: null quad_faces");
+  *quad_faces = 0;
+  if (B < 0 || cus <= 0) return fail(NLML_E_BADARG, "k2_quad_split: negative B or cus <= 0");
+  *quad_faces = k2_quad_faces(B, cus);
+  return 0;
+}
+
+int nlml_k2_quad_faces(int64_t B, int64_t* quad_faces, size_t* ws_bytes) {
+  if (quad_faces) *quad_faces = 0;
+  if (ws_bytes) *ws_bytes = 0;
+  if (!quad_faces) return fail(NLML_E_BADARG, "k2_quad_faces: null quad_faces");
+  if (B < 0) return fail(NLML_E_BADARG, "k2_quad_faces: negative B");
+  *quad_faces = auto_quad_faces(B);
+  if (ws_bytes) *ws_bytes = quad_workspace_bytes(*quad_faces);
+  return 0;
 }
 
 size_t nlml_encoder_heads_workspace_bytes(int64_t B, int F) {

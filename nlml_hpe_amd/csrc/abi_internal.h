@@ -84,6 +84,17 @@ size_t tailws_workspace_bytes(int64_t B, int F);
 int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
                                       const void* blob, float* out, float* latent, uint8_t* valid, void* workspace,
                                       size_t ws_bytes, void* stream);
+// the same forward with FOUR tiles per workgroup and the streamed tail inside the launch (encoder_heads_f16x2_w8.hip,
+// encoder_heads_f16x2_w8q_kernel; + the re-evaluation launch): bit-identical to the fused kernel.  The first quad_faces faces (a multiple
+// of 256, or all B) go that way and the others through the fused kernel, one re-evaluation launch over all B.
+// The workspace holds the quad part's hand-over, quad_workspace_bytes(quad_faces) (1 KiB per face of whole 64-face tiles).
+size_t quad_workspace_bytes(int64_t quad_faces);
+int launch_encoder_heads_f16x2_w8_mixed(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
+                                        const void* blob, float* out, float* latent, uint8_t* valid, int64_t quad_faces,
+                                        void* workspace, size_t ws_bytes, void* stream);
+// The dispatcher's split (abi.cpp; exported as nlml_k2_quad_split): how many of B faces go through the four-tile kernel on a device of
+// `cus` compute units -- whole rounds of one workgroup per unit, ((B / 64) / (4 cus)) * cus workgroups of 256 faces; 0 for cus <= 0
+int64_t k2_quad_faces(int64_t B, int cus);
 // encoder_heads_f16x2_tailws.hip: h3 = layer 2's output as operand fragments, nfb 32-face blocks of it -> poses (and the latent)
 int launch_tail_ws(const void* blob, const void* h3, int64_t nfb, int64_t B, float* out, float* latent, void* stream);
 // encoder_heads_f16x2_small.hip (split-f16 mode, big layers as separate launches + one tail launch, for small batches)

@@ -22,6 +22,7 @@
 #include "abi_internal.h"
 #include "ipd_norm.h"
 #include "encoder_heads_f16x2_dev.h"
+#include "encoder_heads_f16x2_tailws_dev.h"
 #include "layout.h"
 
 // -DW8_D0_HI=<n> / -DW8_D0_LO=<n>: K steps the hi / lo weight pieces of layer 0's ring are requested ahead (stage_e0_pass_w8; same bits)
@@ -261,10 +262,14 @@ __device__ __forceinline__ void stage_e0_pass_w8(const Ctx& c, const Args& a, in
 // TRUNK = true (round 5, second half): the launch ends with layer 2 -- its output goes to a.h3ws as MFMA operand fragments
 // (TrunkFrags, encoder_heads_f16x2_dev.h: [32-face block][K16 step][piece][lane] x 16 bytes, 1 KB per face) and the rest of the network runs as its own launch with the
 // weights streaming through LDS ONCE per 256 faces (encoder_heads_f16x2_tailws.hip).  All eight waves work to the end of this launch.
-template <bool VEC4, bool NORM, bool TRUNK = false>
-__global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
-  __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
-
+// One 64-face tile through the eight-wave kernel, run by a whole 512-thread workgroup that owns `lds` (LDS_BYTES, nothing in them
+// live): the body of encoder_heads_f16x2_w8_kernel (tile = its workgroup's index) and, TRUNK, of each of the four rounds of
+// encoder_heads_f16x2_w8q_kernel below.  TRUNK: the tile's fragments go to unit tile * TrunkFrags::TILE_UNITS of a.h3ws.
+// ArgsT: how the kernel's arguments reach the body -- `Args` (a copy: the one-tile kernels, whose listings then stay what they were before
+// the body was a function: same spill counts, +-1 instruction; by reference 18 spilled registers instead of 15) or `const Args&` (the
+// four-tile kernel: by value hipcc spills 45 registers there, by reference 32).  Figures: profiles/k2_quad_resources.md.
+template <bool VEC4, bool NORM, bool TRUNK, class ArgsT>
+__device__ __forceinline__ void w8_tile(ArgsT a, char* const lds, const int64_t tile) {
   const int tid = threadIdx.x;
   Ctx c;   // make_ctx(a.blob, lds, tid) written out: through the call this kernel's prologue is scheduled differently (profiles/k2_scaffold_ab.md)
   c.blob8 = reinterpret_cast<const h8*>(a.blob);
@@ -276,7 +281,7 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
   c.h = c.lane >> 5;
   c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);       // 0..7
   const int jw = c.wv >> 1, nbh = c.wv & 1;              // the job this wave shares with its partner, and its half of the job's blocks
-  const int64_t row0 = (int64_t)blockIdx.x * TILE_FACES;
+  const int64_t row0 = tile * TILE_FACES;
 
   {  // E0 (two passes of 512 neurons, split accumulators) interleaved with the two K halves of E1
     constexpr int WSTEP1 = 4 * 2 * 64;
@@ -354,7 +359,7 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
     W8S(10);
     if constexpr (TRUNK) {   // h3 = relu(E2) straight from the accumulators to the hand-over buffer (no LDS image, no barrier)
       typedef unsigned u4_ __attribute__((ext_vector_type(4)));
-      u4_* const dst = reinterpret_cast<u4_*>(a.h3ws) + (size_t)blockIdx.x * TrunkFrags::TILE_UNITS + c.lane;   // the tile's first unit, this lane
+      u4_* const dst = reinterpret_cast<u4_*>(a.h3ws) + (size_t)tile * TrunkFrags::TILE_UNITS + c.lane;   // the tile's first unit, this lane
 #pragma unroll
       for (int fb = 0; fb < 2; ++fb) {
         h8 fr[2][2];
@@ -390,6 +395,47 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
 #endif
 }
 
+template <bool VEC4, bool NORM, bool TRUNK = false>
+__global__ __launch_bounds__(512) void encoder_heads_f16x2_w8_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
+  w8_tile<VEC4, NORM, TRUNK, const Args>(a, lds, (int64_t)blockIdx.x);
+}
+
+// FOUR tiles per workgroup, the streamed tail once: workgroup g runs the trunk (w8_tile, TRUNK) over tiles 4g .. 4g + 3 one after the
+// other, parking each tile's layer-2 output as TrunkFrags in ITS OWN slice of a.h3ws (blocks 8g .. 8g + 7: written and read back by this
+// workgroup alone, on one CU, out of the L2 it was just written to), then runs tail_ws_body over those eight 32-face blocks -- the
+// tail's 1.06 MB of weights enter the CU once per 256 faces instead of once per 64, as in the trunk + streamed-tail pair of launches,
+// without that pair's second launch and its read of all the h3 from HBM by every CU at once.  No workgroup waits for another.  Per
+// accumulator the trunk's and the streamed tail's own instructions => the fused kernel's bits (tests/test_k2_quad.py).
+//   * between two tiles one barrier: the next tile parks layer 1's accumulators and stages x where waves still in this tile's layer 2
+//     read h2;
+//   * between the trunk and the tail every wave waits for its own h3 stores (vmcnt(0)), releases them at workgroup scope, passes the
+//     barrier and acquires: producer and consumer waves share this CU's vector L1 (write-through, one copy of a line), so workgroup
+//     scope is the whole hand-over; the barrier also ends the trunk's use of LDS, which the tail overwrites from byte 0;
+//   * a tile at or beyond the batch's end is skipped (workgroup-uniform); its blocks of a.h3ws are neither written nor read: the tail's
+//     waves beyond nfb compute block nfb - 1 again -- a block of this same, last workgroup -- and store nothing.
+// Measured at 65,536 faces (profiles/k2_quad_prof.md, k2_quad_ab.md): 797.0 us against the fused kernel's 810-814 (trunk launch 706.5 +
+// tail launch 93.8), 83.4 M L1 -> L2 requests against 88.5 M; the hand-over does not stay in the L2 (8 MB per XCD against 4 MB): +0.11 GB
+// HBM-side.  Same box, alternating: +1.2 ... +3.2 % on one visit, +0.4 % (inside the spread) on another, bench.py +2.0 / +0.4 %: the kernel
+// is power-limited and how much of the saved traffic shows depends on the box.  Dispatch (abi.cpp, K2_AUTO): whole rounds of one
+// workgroup per compute unit go through this kernel, the rest of the batch through the fused kernel; NLML_K2_QUAD_MIN moves the rule.
+template <bool VEC4, bool NORM>
+__global__ __launch_bounds__(512) void encoder_heads_f16x2_w8q_kernel(Args a, TwArgs t) {
+  constexpr int QLDS = LDS_BYTES > TW_LDS ? LDS_BYTES : TW_LDS;
+  __shared__ __attribute__((aligned(1024))) char lds[QLDS];
+  const int64_t tile0 = (int64_t)blockIdx.x * 4, ntiles = t.nfb >> 1;
+#pragma unroll 1
+  for (int i = 0; i < 4; ++i) {
+    if (tile0 + i < ntiles) w8_tile<VEC4, NORM, true, const Args&>(a, lds, tile0 + i);
+    __syncthreads();
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  tail_ws_body(t, (int64_t)blockIdx.x * 8, lds);
+}
+
 }  // namespace hx
 
 // ---- the strict-fast forward as trunk launch + streamed tail launch (+ the f32 re-evaluation launch) -------------------------------
@@ -418,17 +464,60 @@ int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* 
   return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
 }
 
-int launch_encoder_heads_f16x2_w8(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                  const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
-  if (B == 0) return 0;
-  const K2Input in = k2_input(x, ldx, raw, normalize, F);
+
+// the fused kernel alone over B faces of `in`'s rows (no re-evaluation launch behind it)
+static int launch_w8_fused_kernel(const K2Input& in, int64_t B, int F, const void* blob, float* out, float* latent, uint8_t* valid,
+                                  void* stream) {
   const hx::Args a = k2_args<hx::Args>(in, B, F, blob, out, latent, valid);
   const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   k2_with_variant(in, [&](auto V, auto N) {
     hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<decltype(V)::value, decltype(N)::value>), grid, block, 0, st, a);
   });
-  if (int rc = hip_launch_status()) return rc;
+  return hip_launch_status();
+}
+
+int launch_encoder_heads_f16x2_w8(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
+                                  const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
+  if (B == 0) return 0;
+  if (int rc = launch_w8_fused_kernel(k2_input(x, ldx, raw, normalize, F), B, F, blob, out, latent, valid, stream)) return rc;
+  return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
+}
+
+// ---- the strict-fast forward with four tiles per workgroup and the streamed tail inside the launch (+ the f32 re-evaluation launch) ----
+// The first quad_faces faces (a multiple of 256, or all B of them) go through encoder_heads_f16x2_w8q_kernel, the others through the
+// fused kernel on offset pointers in the same stream; one re-evaluation launch over all B follows.
+size_t quad_workspace_bytes(int64_t quad_faces) { return quad_faces <= 0 ? 0 : hx::TrunkFrags::bytes(quad_faces); }
+
+int launch_encoder_heads_f16x2_w8_mixed(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
+                                        const void* blob, float* out, float* latent, uint8_t* valid, int64_t quad_faces,
+                                        void* workspace, size_t ws_bytes, void* stream) {
+  if (B == 0) return 0;
+  if (quad_faces < 0 || quad_faces > B || (quad_faces < B && quad_faces % (4 * TILE_FACES)))
+    return fail(NLML_E_BADARG, "quad path: the quad part is whole workgroups of 256 faces, or the whole batch");
+  K2Input in = k2_input(x, ldx, raw, normalize, F);
+  if (quad_faces > 0) {
+    if (!workspace || ws_bytes < quad_workspace_bytes(quad_faces)) return fail(NLML_E_BADARG, "quad path: workspace too small");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(NLML_E_BADARG, "quad path: workspace must be 16-byte aligned");
+    if (!in.vec4) return fail(NLML_E_BADARG, "quad path: x must be 16-byte aligned with F and ldx multiples of 4");
+    hx::Args a = k2_args<hx::Args>(in, quad_faces, F, blob, out, latent, valid);
+    a.h3ws = workspace;
+    const int64_t ntiles = (quad_faces + TILE_FACES - 1) / TILE_FACES;
+    hx::TwArgs t;
+    t.blob = blob; t.h3 = reinterpret_cast<const hx::u4*>(workspace); t.out = out; t.latent = latent; t.B = quad_faces; t.nfb = 2 * ntiles;
+    const dim3 grid((unsigned)((ntiles + 3) / 4)), block(512);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (a.norm) hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8q_kernel<true, true>), grid, block, 0, st, a, t);
+    else hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8q_kernel<true, false>), grid, block, 0, st, a, t);
+    if (int rc = hip_launch_status()) return rc;
+  }
+  if (quad_faces < B) {   // (ld % 4 == 0 wherever there is a quad part: the remainder's rows are as aligned as the batch's)
+    K2Input rest = in;
+    rest.src = in.src + quad_faces * in.ld;
+    if (int rc = launch_w8_fused_kernel(rest, B - quad_faces, F, blob, out + quad_faces * 3,
+                                        latent ? latent + quad_faces * NLML_LATENT : nullptr, valid ? valid + quad_faces : nullptr, stream))
+      return rc;
+  }
   return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
 }
 

@@ -161,7 +161,25 @@ K2Out k2_forward(const at::Tensor& in_, bool landmarks, const at::Tensor& blob, 
   float* const out = r.pose.data_ptr<float>();
   const size_t blob_bytes = (size_t)blob.numel();
   OnDevice dev(in);
-  if (landmarks) {
+  // No workspace given: where the _ws dispatcher would send a part of the batch through the four-tile strict-fast kernel (a strict-fast
+  // blob, rows readable 16 bytes at a time, nlml_k2_quad_faces for this device), give it that part's scratch from torch's allocator
+  // (stream-ordered: freed at return, reused only behind this launch) -- ops._k2_forward's rule.
+  at::Tensor quad_ws;
+  if (!ws && B > 0 && F > 0 && F % 4 == 0 && blob_bytes == nlml_encoder_heads_packed_bytes((int)F, NLML_MODE_F16X2S) &&
+      (landmarks || B == 1 || in.stride(0) % 4 == 0) && reinterpret_cast<uintptr_t>(in.data_ptr<float>()) % 16 == 0) {
+    int64_t quad_faces = 0;
+    size_t quad_bytes = 0;
+    check(nlml_k2_quad_faces(B, &quad_faces, &quad_bytes), "nlml_k2_quad_faces");
+    if (quad_faces > 0) quad_ws = at::empty({(int64_t)quad_bytes}, in.options().dtype(at::kByte));
+  }
+  if (quad_ws.defined()) {
+    if (landmarks)
+      check(nlml_landmarks_to_pose_ws(in.data_ptr<float>(), B, normalize ? 1 : 0, blob.data_ptr(), blob_bytes, out, nullptr, valid,
+                                      quad_ws.data_ptr(), (size_t)quad_ws.numel(), dev.stream), "nlml_landmarks_to_pose_ws");
+    else
+      check(nlml_encoder_heads_fwd_ws(in.data_ptr<float>(), B > 1 ? in.stride(0) : F, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr,
+                                      valid, quad_ws.data_ptr(), (size_t)quad_ws.numel(), dev.stream), "nlml_encoder_heads_fwd_ws");
+  } else if (landmarks) {
     const int norm = normalize ? 1 : 0;
     if (ws)
       check(nlml_landmarks_to_pose_small(in.data_ptr<float>(), B, norm, blob.data_ptr(), blob_bytes, out, nullptr, valid, ws->data_ptr(),

@@ -151,12 +151,12 @@ def rotate_landmarks(lm: torch.Tensor, rot: torch.Tensor, return_f64: bool = Fal
 _k2_ws: dict = {}
 
 
-def _k2_workspace(form: str, B: int, F: int, device, floor_faces: int = 0) -> torch.Tensor:
+def _k2_workspace(form: str, B: int, F: int, device, floor_faces: int = 0, need_bytes: int = 0) -> torch.Tensor:
     """Scratch of the K2 call forms that need one (its contents never matter).  Buffers are cached per form, device and stream and
     NEVER released or replaced: a captured hipGraph keeps replaying into the pointer it was captured with, so growing means
     adding a larger buffer next to the old one.  floor_faces: a new buffer holds at least that many faces of the reference width."""
     size_of = _lib.lib().nlml_encoder_heads_small_workspace_bytes if form == "small" else _lib.lib().nlml_encoder_heads_workspace_bytes
-    need = max(16, size_of(B, F))
+    need = max(16, need_bytes or size_of(B, F))        # need_bytes: the caller knows what this call takes (the "ws" form's quad part)
     # one pool per (device, stream): launches on different streams may overlap and must not share scratch
     pool = _k2_ws.setdefault((form, str(device), _stream_ptr(device)), [])
     for ws in pool:
@@ -172,9 +172,28 @@ def _small_workspace(B: int, F: int, device) -> torch.Tensor:
     return _k2_workspace("small", B, F, device, floor_faces=4096)
 
 
+def _k2_quad_part(B: int, F: int, src: torch.Tensor, blob: torch.Tensor) -> int:
+    """Bytes of workspace with which nlml_*_ws sends a part of this batch through the four-tile strict-fast kernel
+    (csrc/encoder_heads_f16x2_w8.hip), 0 if it would not: strict-fast blob, rows readable 16 bytes at a time, and the dispatcher's own
+    split for `src`'s device (nlml_k2_quad_faces: whole rounds of one 256-face workgroup per compute unit, or what NLML_K2_QUAD_MIN
+    says)."""
+    import ctypes as C
+    L = _lib.lib()
+    if B <= 0 or blob.numel() != L.nlml_encoder_heads_packed_bytes(F, _lib.MODE_F16X2S):
+        return 0
+    ld = src.stride(0) if (src.dim() == 2 and B > 1) else F
+    if F % 4 or ld % 4 or src.data_ptr() % 16:
+        return 0
+    n, need = C.c_int64(0), C.c_size_t(0)
+    with torch.cuda.device(src.device):
+        rc = L.nlml_k2_quad_faces(B, C.byref(n), C.byref(need))
+    return int(need.value) if rc == 0 and n.value > 0 else 0
+
+
 def _k2_forward(form: str, x, raw, blob: torch.Tensor, F: int, normalize, return_latent: bool, return_valid: bool, workspace=None):
     """x f32[B,F] (raw None) or raw f32[B,468,3] (x None) -> out f32[B,3][, latent f32[B,9]][, valid bool[B]] through the C entry
-    point of the call form: "" (the fused kernel), "small" or "streamed" (both through a workspace, pooled unless given)."""
+    point of the call form: "" (the fused kernel -- or, where _k2_quad_part says so, the _ws entry point with the pooled workspace),
+    "small", "streamed" or "quad" (all through a workspace, pooled unless given)."""
     if raw is None:
         _need_cuda(x, "x", torch.float32)
         _need_cuda(blob, "blob", torch.uint8)
@@ -193,10 +212,13 @@ def _k2_forward(form: str, x, raw, blob: torch.Tensor, F: int, normalize, return
         head = (src.data_ptr(), B, int(bool(normalize)))
     dev = src.device
     tail = ()
+    quad_bytes = 0 if form else _k2_quad_part(B, F, src, blob)
+    if quad_bytes:
+        form = "ws"        # the dispatcher splits the batch: whole rounds through the four-tile kernel, the rest through the fused one
     if form:
         symbol += "_" + form
         if workspace is None:
-            workspace = _small_workspace(B, F, dev) if form == "small" else _k2_workspace(form, B, F, dev)
+            workspace = _small_workspace(B, F, dev) if form == "small" else _k2_workspace(form, B, F, dev, need_bytes=quad_bytes)
         tail = (workspace.data_ptr(), workspace.numel())
     out = torch.empty((B, 3), dtype=torch.float32, device=dev)
     latent = torch.empty((B, LATENT), dtype=torch.float32, device=dev) if return_latent else None
@@ -434,6 +456,22 @@ def landmarks_to_pose_streamed(raw: torch.Tensor, blob: torch.Tensor, normalize:
     (nlml_landmarks_to_pose_streamed): bit-identical to the fused kernel, measured 1.4-2.2 % faster at 65,536 faces; nothing calls it by default
     (DESIGN.md section 3).  The hand-over buffer (1 KB per face) is cached per device and stream like the layer-per-launch path's scratch."""
     return _k2_forward("streamed", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
+
+
+def landmarks_to_pose_quad(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
+                           return_valid: bool = False, workspace: torch.Tensor | None = None):
+    """landmarks_to_pose (strict-fast blob only) through the four-tile kernel whatever the batch size (nlml_landmarks_to_pose_quad: a
+    workgroup runs layers 0-2 over four tiles, then the streamed tail once; + the f32 re-evaluation launch): bit-identical to the fused
+    kernel.  landmarks_to_pose itself takes this path for whole rounds of 256 faces per compute unit.  The
+    hand-over buffer (1 KB per face) is cached per device and stream like the streamed path's."""
+    return _k2_forward("quad", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
+
+
+def encoder_heads_fwd_quad(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
+                           return_valid: bool = False, workspace: torch.Tensor | None = None):
+    """encoder_heads_fwd (strict-fast blob only, rows 16-byte aligned) through the four-tile kernel whatever the batch size
+    (nlml_encoder_heads_fwd_quad); see landmarks_to_pose_quad."""
+    return _k2_forward("quad", x, None, blob, F, None, return_latent, return_valid, workspace)
 
 
 # ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------

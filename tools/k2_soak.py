@@ -1,6 +1,7 @@
 """Randomised soak of the K2 implementations that must agree bit for bit (GPU box): for <minutes> minutes draw a batch size (weighted towards
 partial tiles and tile-count edges), a seed and a normalisation flag, and compare
-  strict-fast: fused eight-wave kernel, twice (determinism)  ==  layer-per-launch path  ==  trunk + streamed-tail path  (pose, latent, validity)
+  strict-fast: fused eight-wave kernel, twice (determinism)  ==  layer-per-launch path  ==  trunk + streamed-tail path  ==  four-tile kernel
+               (pose, latent, validity; at 65,536 faces ops.landmarks_to_pose itself takes the four-tile kernel: the streamed path is the other opinion)
   opt-in fast: fused four-wave kernel, twice                 ==  layer-per-launch path
   bf16 / f32 : fused kernel, twice (determinism)
 and, every tenth draw, the full 65,536-face batch three times (four tiles per CU: anything one tile leaves behind for the next shows up here).
@@ -59,6 +60,8 @@ while time.time() < t_end:
         again = ops.landmarks_to_pose(raw, blob["f16x2s"], norm, return_latent=True, return_valid=True)
         if not same(ref, again): print("DIFFERENT (strict fused, run to run)", tag); sys.exit(1)
     if not same(ref, streamed(raw, B, norm)): print("DIFFERENT (strict fused vs trunk + streamed tail)", tag); sys.exit(1)
+    if not same(ref, ops.landmarks_to_pose_quad(raw, blob["f16x2s"], norm, return_latent=True, return_valid=True)):
+        print("DIFFERENT (strict fused vs four-tile kernel)", tag); sys.exit(1)
     if not big:
         if B <= 16384:
             if not same(ref, ops.landmarks_to_pose_small(raw, blob["f16x2s"], norm, return_latent=True, return_valid=True)):
