@@ -281,11 +281,22 @@ int nlml_landmarks_to_pose_quad(const float* raw, int64_t B, int normalize,
 /* The _ws entry points' split of a strict-fast batch: *quad_faces = the leading faces that go through the four-tile kernel on a device
  * of `cus` compute units -- whole rounds of one 256-face workgroup per unit, ((B / 64) / (4 cus)) * cus * 256 -- the others go through
  * the fused kernel.  Host arithmetic, no HIP call.  B < 0, cus <= 0 or a NULL quad_faces: NLML_E_BADARG (and *quad_faces = 0).
- * nlml_k2_quad_faces: what the _ws entry points would send through the four-tile kernel of a strict-fast batch of B faces with 16-byte
- * readable rows on the calling thread's current device, under this process's environment (NLML_K2_QUAD_MIN, NLML_K2_STREAMED_MIN: below),
- * and in *ws_bytes (may be NULL) the workspace that part needs -- what a host asks to learn whether a workspace is worth allocating. */
+ */
 int nlml_k2_quad_split(int64_t B, int cus, int64_t* quad_faces);
+/* The part of a batch of B rows that nlml_encoder_heads_fwd_ws / nlml_landmarks_to_pose_ws send through the four-tile kernel on the
+ * calling thread's current device when the workspace holds it, and the bytes of workspace that part needs.  rows / ld: x and ldx, or raw
+ * and 1404 (B == 1: ld = F); rows is looked at for its alignment only and never read.  blob_bytes names the blob's mode as in the
+ * forwards; a size that is no strict-fast blob of width F gives 0 faces and rc 0 (the forward itself refuses a bad blob).
+ * ws_bytes may be NULL.  B < 0, F <= 0 or quad_faces NULL: NLML_E_BADARG, outputs zeroed.
+ * The dispatcher's own rule (one function in csrc/abi.cpp), under this process's environment (NLML_K2_QUAD_MIN, NLML_K2_STREAMED_MIN:
+ * below; NLML_K2_QUAD_CUS=<n> stands in for the device's compute-unit count, and then no HIP call is made) -- what a host asks to learn
+ * whether a workspace is worth allocating. */
+int nlml_k2_quad_part(const float* rows, int64_t ld, int64_t B, int F, size_t blob_bytes, int64_t* quad_faces, size_t* ws_bytes);
+/* nlml_k2_quad_part for 16-byte aligned rows of the reference width and a strict-fast blob: the same function, evaluated for that input. */
 int nlml_k2_quad_faces(int64_t B, int64_t* quad_faces, size_t* ws_bytes);
+/* Largest batch the _ws dispatcher sends through the layer-per-launch path for a blob of `mode`; 0 for a mode without that path or an
+ * unknown mode. */
+int64_t nlml_k2_small_batch_max(int mode);
 
 /* THE FORWARD WITH A WORKSPACE: picks the fastest of the paths above for the batch size and the blob's mode (split-f16 modes: the
  * layer-per-launch path up to 4,096 faces; the fused kernel otherwise and for the other modes, which ignore the workspace; the
@@ -296,8 +307,9 @@ int nlml_k2_quad_faces(int64_t B, int64_t* quad_faces, size_t* ws_bytes);
  * the path, so it never fails for want of workspace where the fused kernel would run.  NLML_K2_QUAD_MIN=<faces> (read once): negative
  * switches the path off; otherwise the rule becomes "B >= faces: the whole batch through the four-tile kernel" (then a small workspace
  * IS refused).  NLML_K2_STREAMED_MIN wins where both apply.  Same bits whichever path runs.  For hosts that
- * want one call for every batch size; the packaged host layer makes the same choice in Python (nlml_hpe_amd/model.py, `small_batch_max`)
- * and calls the plain / _small forms, and the _ws form where nlml_k2_quad_faces says a quad part exists -- which is what bench.py times.
+ * want one call for every batch size; the packaged host layer asks the library instead of choosing for itself: the _small forms up to
+ * nlml_k2_small_batch_max(mode) faces (nlml_hpe_amd/model.py), the _ws form where nlml_k2_quad_part says a quad part exists, the plain
+ * forms otherwise -- which is what bench.py times.
  * The plain entry points (nlml_encoder_heads_fwd, nlml_landmarks_to_pose) have no workspace argument, cannot take the four-tile path and
  * stay on the fused kernel.
  * `workspace`: at least nlml_encoder_heads_workspace_bytes(B, F) bytes (>= the _small, _streamed and _quad paths' needs), 16-byte aligned.

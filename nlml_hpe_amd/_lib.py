@@ -69,7 +69,10 @@ SYMBOLS = {
     "nlml_encoder_heads_small_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "nlml_encoder_heads_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "nlml_k2_quad_split": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    # rows, ld, B, F, blob_bytes, quad_faces, ws_bytes
+    "nlml_k2_quad_part": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
     "nlml_k2_quad_faces": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
+    "nlml_k2_small_batch_max": (C.c_int64, [C.c_int]),
     "nlml_tucker_gradient_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "nlml_video_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -169,7 +169,11 @@ static int check_blob_args(int64_t B, int F, const void* blob, size_t blob_bytes
 
 // ---- the K2 forward: one core behind the eight entry points --------------------------------------------------------------------
 // (crossovers measured with tools/k2_crossover.py and bench.py extra.k2_batch_sweep)
-static const int64_t kSmallMax = 4096;     // split-f16 modes: up to here the layer-per-launch path over 64-face tiles
+// Split-f16 modes: up to here the layer-per-launch path over 64-face tiles, above it the fused kernel wins.  NLML_MODE_F16X2: 5,120 faces
+// 0.140 against 0.159 ms layered.  NLML_MODE_F16X2S: with the eight-wave fused kernel the same crossover (5,120 faces: 0.152 against 0.159 ms
+// layered; 4,096: 0.152 against 0.123; round 3's four-wave kernel lost up to 8,192).  The one place the figure is written: hosts ask
+// nlml_k2_small_batch_max.
+static const int64_t kSmallMax = 4096;
 // The trunk + streamed-tail path (encoder_heads_f16x2_tailws.hip) is bit-identical to the fused kernel and measured 1.4-2.2 % faster at 65,536
 // faces (0.801 against 0.815 ms, same box, alternating) -- inside the box-to-box spread, for a 64 MB workspace and a
 // second big launch -- so the dispatcher does not pick it by itself.  NLML_K2_STREAMED_MIN=<faces> routes batches from that size
@@ -208,7 +212,6 @@ static int device_cus() {   // of the calling thread's current device, asked onc
   return cus[dev] > 0 ? cus[dev] : 0;
 }
 
-
 // The part of a strict-fast batch of B faces with 16-byte readable rows that AUTO sends through the four-tile kernel on the current device
 static int64_t auto_quad_faces(int64_t B) {
   if (B <= 0) return 0;
@@ -216,6 +219,10 @@ static int64_t auto_quad_faces(int64_t B) {
   if (quad_min() != kQuadMinUnset) return quad_min() >= 0 && B >= quad_min() ? B : 0;
   return B > kSmallMax ? k2_quad_faces(B, device_cus()) : 0;                   // (the layer-per-launch path's sizes stay its own)
 }
+// What the streamed and the quad path take: a strict-fast blob and rows that may be read 16 bytes at a time
+static bool k2_wide(bool strict_fast, const K2Input& in) { return strict_fast && in.vec4; }
+// The same part for a given input and blob: AUTO's rule for the four-tile kernel, whole.  k2_forward and the hosts (nlml_k2_quad_part) ask here.
+static int64_t auto_quad_part(bool strict_fast, const K2Input& in, int64_t B) { return k2_wide(strict_fast, in) ? auto_quad_faces(B) : 0; }
 
 // The call forms: the fused kernel of the blob's mode; the split-f16 modes' layer-per-launch path (small batches); the strict-fast
 // mode's trunk + streamed tail (encoder_heads_f16x2_w8.hip TRUNK, encoder_heads_f16x2_tailws.hip); the strict-fast mode's four-tile
@@ -241,13 +248,13 @@ static int k2_forward(K2Form form, bool landmarks, const float* x, int64_t ldx, 
   const int split = mode == NLML_MODE_F16X2S;
   int64_t quad_faces = B;   // K2_QUAD: the whole batch
   if (form == K2_AUTO) {
-    const bool wide = split && k2_input(x, ldx, raw, normalize, F).vec4;   // what the streamed and the quad path take
-    quad_faces = wide ? auto_quad_faces(B) : 0;
+    const K2Input in = k2_input(x, ldx, raw, normalize, F);
+    quad_faces = auto_quad_part(split, in, B);
     // whole rounds only if the workspace takes them -- never a failure the fused kernel would not have; asked for by the environment, always
     const bool fits = workspace && ws_bytes >= quad_workspace_bytes(quad_faces) && !(reinterpret_cast<uintptr_t>(workspace) & 15);
     if (quad_faces > 0 && (fits || quad_min() != kQuadMinUnset)) form = K2_QUAD;
     else if (split_f16(mode) && B <= kSmallMax) form = K2_SMALL;
-    else if (wide && streamed_min() >= 0 && B >= streamed_min()) form = K2_STREAMED;
+    else if (k2_wide(split, in) && streamed_min() >= 0 && B >= streamed_min()) form = K2_STREAMED;
     else form = K2_FUSED;
   }
   if (form == K2_SMALL)
@@ -320,15 +327,32 @@ int nlml_k2_quad_split(int64_t B, int cus, int64_t* quad_faces) {
   return 0;
 }
 
-int nlml_k2_quad_faces(int64_t B, int64_t* quad_faces, size_t* ws_bytes) {
+// nlml_k2_quad_part / nlml_k2_quad_faces (who: the one that was called)
+static int k2_quad_part(const char* who, const float* rows, int64_t ld, int64_t B, int F, size_t blob_bytes, int64_t* quad_faces,
+                        size_t* ws_bytes) {
   if (quad_faces) *quad_faces = 0;
   if (ws_bytes) *ws_bytes = 0;
-  if (!quad_faces) return fail(NLML_E_BADARG, "k2_quad_faces: null quad_faces");
-  if (B < 0) return fail(NLML_E_BADARG, "k2_quad_faces: negative B");
-  *quad_faces = auto_quad_faces(B);
+  if (B < 0 || F <= 0 || !quad_faces) {
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "%s: negative B, F <= 0 or null quad_faces", who);
+    return fail(NLML_E_BADARG, msg);
+  }
+  *quad_faces = auto_quad_part(blob_bytes == blob_bytes_for(F, NLML_MODE_F16X2S), k2_input(rows, ld, nullptr, 0, F), B);
   if (ws_bytes) *ws_bytes = quad_workspace_bytes(*quad_faces);
   return 0;
 }
+
+int nlml_k2_quad_part(const float* rows, int64_t ld, int64_t B, int F, size_t blob_bytes, int64_t* quad_faces, size_t* ws_bytes) {
+  return k2_quad_part("k2_quad_part", rows, ld, B, F, blob_bytes, quad_faces, ws_bytes);
+}
+
+// the same rule for aligned rows of the reference width and a strict-fast blob
+int nlml_k2_quad_faces(int64_t B, int64_t* quad_faces, size_t* ws_bytes) {
+  return k2_quad_part("k2_quad_faces", nullptr, NLML_F_REFERENCE, B, NLML_F_REFERENCE, blob_bytes_for(NLML_F_REFERENCE, NLML_MODE_F16X2S), quad_faces,
+                      ws_bytes);
+}
+
+int64_t nlml_k2_small_batch_max(int mode) { return split_f16(mode) ? kSmallMax : 0; }
 
 size_t nlml_encoder_heads_workspace_bytes(int64_t B, int F) {
   const size_t a = small_workspace_bytes(B, F), b = tailws_workspace_bytes(B, F);

@@ -160,42 +160,35 @@ K2Out k2_forward(const at::Tensor& in_, bool landmarks, const at::Tensor& blob, 
   uint8_t* const valid = want_valid ? r.valid.data_ptr<uint8_t>() : nullptr;
   float* const out = r.pose.data_ptr<float>();
   const size_t blob_bytes = (size_t)blob.numel();
+  const float* const src = in.data_ptr<float>();
+  const int64_t ldx = B > 1 ? in.stride(0) : F;   // of feature rows
+  const int norm = normalize ? 1 : 0;
   OnDevice dev(in);
-  // No workspace given: where the _ws dispatcher would send a part of the batch through the four-tile strict-fast kernel (a strict-fast
-  // blob, rows readable 16 bytes at a time, nlml_k2_quad_faces for this device), give it that part's scratch from torch's allocator
-  // (stream-ordered: freed at return, reused only behind this launch) -- ops._k2_forward's rule.
+  // No workspace given: where the library says its _ws dispatcher would send a part of this batch through the four-tile strict-fast
+  // kernel, give it that part's scratch from torch's allocator (stream-ordered: freed at return, reused only behind this launch).
   at::Tensor quad_ws;
-  if (!ws && B > 0 && F > 0 && F % 4 == 0 && blob_bytes == nlml_encoder_heads_packed_bytes((int)F, NLML_MODE_F16X2S) &&
-      (landmarks || B == 1 || in.stride(0) % 4 == 0) && reinterpret_cast<uintptr_t>(in.data_ptr<float>()) % 16 == 0) {
-    int64_t quad_faces = 0;
-    size_t quad_bytes = 0;
-    check(nlml_k2_quad_faces(B, &quad_faces, &quad_bytes), "nlml_k2_quad_faces");
-    if (quad_faces > 0) quad_ws = at::empty({(int64_t)quad_bytes}, in.options().dtype(at::kByte));
-  }
-  if (quad_ws.defined()) {
-    if (landmarks)
-      check(nlml_landmarks_to_pose_ws(in.data_ptr<float>(), B, normalize ? 1 : 0, blob.data_ptr(), blob_bytes, out, nullptr, valid,
-                                      quad_ws.data_ptr(), (size_t)quad_ws.numel(), dev.stream), "nlml_landmarks_to_pose_ws");
-    else
-      check(nlml_encoder_heads_fwd_ws(in.data_ptr<float>(), B > 1 ? in.stride(0) : F, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr,
-                                      valid, quad_ws.data_ptr(), (size_t)quad_ws.numel(), dev.stream), "nlml_encoder_heads_fwd_ws");
-  } else if (landmarks) {
-    const int norm = normalize ? 1 : 0;
-    if (ws)
-      check(nlml_landmarks_to_pose_small(in.data_ptr<float>(), B, norm, blob.data_ptr(), blob_bytes, out, nullptr, valid, ws->data_ptr(),
-                                         (size_t)ws->numel(), dev.stream), "nlml_landmarks_to_pose_small");
-    else
-      check(nlml_landmarks_to_pose(in.data_ptr<float>(), B, norm, blob.data_ptr(), blob_bytes, out, nullptr, valid, dev.stream),
-            "nlml_landmarks_to_pose");
+  int64_t quad_faces = 0;
+  size_t quad_bytes = 0;
+  if (!ws && nlml_k2_quad_part(src, landmarks ? F_REF : ldx, B, (int)F, blob_bytes, &quad_faces, &quad_bytes) == 0 && quad_faces > 0)
+    quad_ws = at::empty({(int64_t)quad_bytes}, in.options().dtype(at::kByte));
+  // the entry point, chosen once: plain, _small through the caller's workspace, or _ws through the quad part's
+  static const char* const names[2][3] = {{"nlml_encoder_heads_fwd", "nlml_encoder_heads_fwd_small", "nlml_encoder_heads_fwd_ws"},
+                                          {"nlml_landmarks_to_pose", "nlml_landmarks_to_pose_small", "nlml_landmarks_to_pose_ws"}};
+  const int form = quad_ws.defined() ? 2 : ws ? 1 : 0;
+  const at::Tensor* const scratch = form == 2 ? &quad_ws : ws;
+  void* const wsp = scratch ? scratch->data_ptr() : nullptr;
+  const size_t wsn = scratch ? (size_t)scratch->numel() : 0;
+  int rc;
+  if (landmarks) {
+    const auto with_ws = form == 2 ? nlml_landmarks_to_pose_ws : nlml_landmarks_to_pose_small;
+    rc = form ? with_ws(src, B, norm, blob.data_ptr(), blob_bytes, out, nullptr, valid, wsp, wsn, dev.stream)
+              : nlml_landmarks_to_pose(src, B, norm, blob.data_ptr(), blob_bytes, out, nullptr, valid, dev.stream);
   } else {
-    const int64_t ldx = B > 1 ? in.stride(0) : F;
-    if (ws)
-      check(nlml_encoder_heads_fwd_small(in.data_ptr<float>(), ldx, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr, valid,
-                                         ws->data_ptr(), (size_t)ws->numel(), dev.stream), "nlml_encoder_heads_fwd_small");
-    else
-      check(nlml_encoder_heads_fwd(in.data_ptr<float>(), ldx, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr, valid, dev.stream),
-            "nlml_encoder_heads_fwd");
+    const auto with_ws = form == 2 ? nlml_encoder_heads_fwd_ws : nlml_encoder_heads_fwd_small;
+    rc = form ? with_ws(src, ldx, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr, valid, wsp, wsn, dev.stream)
+              : nlml_encoder_heads_fwd(src, ldx, B, (int)F, blob.data_ptr(), blob_bytes, out, nullptr, valid, dev.stream);
   }
+  check(rc, names[landmarks][form]);
   return r;
 }
 

@@ -84,16 +84,11 @@ class HIPPoseModel:
         return fwd(x.to(self.device, torch.float32), self.blob, self.input_size,
                    return_latent=return_latent, return_valid=return_valid)
 
-    SMALL_BATCH_MAX = 4096          # NLML_MODE_F16X2: above this the fused kernel wins (5,120 faces: 0.140 against 0.159 ms)
-    SMALL_BATCH_MAX_STRICT = 4096   # NLML_MODE_F16X2S: with the eight-wave fused kernel the same crossover (5,120 faces: 0.152 against 0.159 ms
-                                    # layered; 4,096: 0.152 against 0.123; round 3's four-wave kernel lost up to 8,192)
-
     @classmethod
     def small_batch_max(cls, mode) -> int:
-        """Largest batch the layer-per-launch path takes in `mode` (0 for the modes that have no such path); measured crossovers,
-        tools/k2_crossover.py."""
-        mode = _lib.mode_from_name(mode)
-        return {_lib.MODE_F16X2: cls.SMALL_BATCH_MAX, _lib.MODE_F16X2S: cls.SMALL_BATCH_MAX_STRICT}.get(mode, 0)
+        """Largest batch the layer-per-launch path takes in `mode` (0 for the modes that have no such path): the library's own
+        crossover (nlml_k2_small_batch_max; csrc/abi.cpp has the measurements, tools/k2_crossover.py takes them)."""
+        return _lib.lib().nlml_k2_small_batch_max(_lib.mode_from_name(mode))
 
     def _small(self, B: int) -> bool:
         """Split-f16 modes, up to small_batch_max(mode) faces: the layer-per-launch path (same bits as the fused kernel, 0.06-0.13 ms

@@ -7,6 +7,9 @@ a CPU tensor raises.
 """
 from __future__ import annotations
 
+import ctypes as C
+import os
+
 import torch
 
 from . import _lib
@@ -168,25 +171,18 @@ def _k2_workspace(form: str, B: int, F: int, device, floor_faces: int = 0, need_
 
 
 def _small_workspace(B: int, F: int, device) -> torch.Tensor:
-    """The layer-per-launch path's scratch; the first buffer is sized for 4,096 faces of the reference width (46 MB)."""
-    return _k2_workspace("small", B, F, device, floor_faces=4096)
+    """The layer-per-launch path's scratch; the first buffer is sized for the largest batch that path takes at the reference width
+    (46 MB)."""
+    return _k2_workspace("small", B, F, device, floor_faces=_lib.lib().nlml_k2_small_batch_max(_lib.MODE_F16X2S))
 
 
-def _k2_quad_part(B: int, F: int, src: torch.Tensor, blob: torch.Tensor) -> int:
+def _k2_quad_part(rows: tuple, blob: torch.Tensor, device) -> int:
     """Bytes of workspace with which nlml_*_ws sends a part of this batch through the four-tile strict-fast kernel
-    (csrc/encoder_heads_f16x2_w8.hip), 0 if it would not: strict-fast blob, rows readable 16 bytes at a time, and the dispatcher's own
-    split for `src`'s device (nlml_k2_quad_faces: whole rounds of one 256-face workgroup per compute unit, or what NLML_K2_QUAD_MIN
-    says)."""
-    import ctypes as C
-    L = _lib.lib()
-    if B <= 0 or blob.numel() != L.nlml_encoder_heads_packed_bytes(F, _lib.MODE_F16X2S):
-        return 0
-    ld = src.stride(0) if (src.dim() == 2 and B > 1) else F
-    if F % 4 or ld % 4 or src.data_ptr() % 16:
-        return 0
+    (csrc/encoder_heads_f16x2_w8.hip) on `device`, 0 if it would not.  The library's own rule (nlml_k2_quad_part); rows: the
+    (pointer, row stride, B, F) it takes."""
     n, need = C.c_int64(0), C.c_size_t(0)
-    with torch.cuda.device(src.device):
-        rc = L.nlml_k2_quad_faces(B, C.byref(n), C.byref(need))
+    with torch.cuda.device(device):
+        rc = _lib.lib().nlml_k2_quad_part(*rows, blob.numel(), C.byref(n), C.byref(need))
     return int(need.value) if rc == 0 and n.value > 0 else 0
 
 
@@ -203,16 +199,16 @@ def _k2_forward(form: str, x, raw, blob: torch.Tensor, F: int, normalize, return
             x = x.contiguous()
         src, name, symbol = x, "x", "nlml_encoder_heads_fwd"
         B = x.shape[0]
-        head = (x.data_ptr(), x.stride(0) if B > 1 else F, B, F)
+        head = rows = (x.data_ptr(), x.stride(0) if B > 1 else F, B, F)
     else:
         _need_cuda(raw, "raw", torch.float32)
         _need_cuda(blob, "blob", torch.uint8)
         src, name, symbol = _raw_rows(raw), "raw", "nlml_landmarks_to_pose"
         B = src.shape[0]
-        head = (src.data_ptr(), B, int(bool(normalize)))
+        head, rows = (src.data_ptr(), B, int(bool(normalize))), (src.data_ptr(), F, B, F)
     dev = src.device
     tail = ()
-    quad_bytes = 0 if form else _k2_quad_part(B, F, src, blob)
+    quad_bytes = 0 if form else _k2_quad_part(rows, blob, dev)
     if quad_bytes:
         form = "ws"        # the dispatcher splits the batch: whole rounds through the four-tile kernel, the rest through the fused one
     if form:
@@ -266,6 +262,44 @@ def landmarks_to_pose(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = T
                       return_valid: bool = False):
     """Fused K1+K2: raw f32[B,468,3] -> radians f32[B,3]; normalised features never reach HBM."""
     return _k2_forward("", None, raw, blob, F_REF, normalize, return_latent, return_valid)
+
+
+def encoder_heads_fwd_small(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
+                            return_valid: bool = False, workspace: torch.Tensor | None = None):
+    """encoder_heads_fwd for small batches (split-f16 blob only): one launch per big layer (five launches; seven with a strict blob: its
+    tail is two launches and the f32 re-evaluation launch follows) spread over the whole chip, bit-identical results."""
+    return _k2_forward("small", x, None, blob, F, None, return_latent, return_valid, workspace)
+
+
+def landmarks_to_pose_small(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
+                            return_valid: bool = False, workspace: torch.Tensor | None = None):
+    """landmarks_to_pose for small batches (split-f16 blob only): one launch per big layer (five launches; seven with a strict blob) spread
+    over the whole chip, bit-identical results."""
+    return _k2_forward("small", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
+
+
+def landmarks_to_pose_streamed(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
+                               return_valid: bool = False, workspace: torch.Tensor | None = None):
+    """landmarks_to_pose (strict-fast blob only) as trunk launch + streamed tail launch + the f32 re-evaluation launch
+    (nlml_landmarks_to_pose_streamed): bit-identical to the fused kernel, measured 1.4-2.2 % faster at 65,536 faces; nothing calls it by default
+    (DESIGN.md section 3).  The hand-over buffer (1 KB per face) is cached per device and stream like the layer-per-launch path's scratch."""
+    return _k2_forward("streamed", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
+
+
+def landmarks_to_pose_quad(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
+                           return_valid: bool = False, workspace: torch.Tensor | None = None):
+    """landmarks_to_pose (strict-fast blob only) through the four-tile kernel whatever the batch size (nlml_landmarks_to_pose_quad: a
+    workgroup runs layers 0-2 over four tiles, then the streamed tail once; + the f32 re-evaluation launch): bit-identical to the fused
+    kernel.  landmarks_to_pose itself takes this path for whole rounds of 256 faces per compute unit (DESIGN.md section 3).  The
+    hand-over buffer (1 KB per face) is cached per device and stream like the streamed path's."""
+    return _k2_forward("quad", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
+
+
+def encoder_heads_fwd_quad(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
+                           return_valid: bool = False, workspace: torch.Tensor | None = None):
+    """encoder_heads_fwd (strict-fast blob only, rows 16-byte aligned) through the four-tile kernel whatever the batch size
+    (nlml_encoder_heads_fwd_quad); see landmarks_to_pose_quad."""
+    return _k2_forward("quad", x, None, blob, F, None, return_latent, return_valid, workspace)
 
 
 # ---- the TD path (K3 objective, K3g gradient, device Powell): one operand preamble behind the three public wrappers ----------------
@@ -347,32 +381,6 @@ def tucker_gradient(Wm: torch.Tensor, x: torch.Tensor, params: torch.Tensor, cos
     return (err, grad) if return_err else grad
 
 
-# ---------------------------------------------------------------------------------------------
-# torch.ops.nlml_hpe.* (SURVEY.md 8b "Underlying op") come from COMPILED code: csrc/torch_ops.cpp, a TORCH_LIBRARY shim over the same
-# C ABI (shape / dtype checks, torch's allocator, the operand device's current stream), built next to this file as
-# libnlml_torch_ops.so by csrc/Makefile.  GPU backend only: a CPU tensor has no kernel to dispatch to and raises.  A missing library
-# raises here -- the ops are part of the boundary.
-import os as _os
-
-TORCH_OPS_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "libnlml_torch_ops.so")
-
-
-def _load_torch_ops():
-    if not _os.path.exists(TORCH_OPS_PATH):
-        raise _lib.NlmlError(f"{TORCH_OPS_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                             "(make -C nlml_hpe_amd/csrc); torch.ops.nlml_hpe.* are registered from it")
-    _lib.lib()                                  # the C ABI library the shim links against, checked symbol by symbol first
-    torch.ops.load_library(TORCH_OPS_PATH)
-    # the registered ops; *_small take an explicit workspace, landmarks_to_pose_valid is the video tick's forward (pose + face mask)
-    for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
-                 "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
-                 "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks"):
-        getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
-
-
-_load_torch_ops()
-
-
 def tucker_powell(Wm: torch.Tensor, x: torch.Tensor, cos_params: torch.Tensor, x0: torch.Tensor | None = None, order="reference"):
     """Batched Test() (TD_Tester.py:162-199): one Powell minimisation per row of x, on device.  order as in tucker_objective:
     "reference" (default, the parity mode) walks scipy's own trajectory on the reference's objective bits; "fast" (opt-in, ~3x the
@@ -436,44 +444,6 @@ def mode5_product(core: torch.Tensor, U_feat: torch.Tensor) -> torch.Tensor:
     return W.reshape(lead + (M,))
 
 
-def encoder_heads_fwd_small(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
-                            return_valid: bool = False, workspace: torch.Tensor | None = None):
-    """encoder_heads_fwd for small batches (split-f16 blob only): one launch per big layer (five launches; seven with a strict blob: its
-    tail is two launches and the f32 re-evaluation launch follows) spread over the whole chip, bit-identical results."""
-    return _k2_forward("small", x, None, blob, F, None, return_latent, return_valid, workspace)
-
-
-def landmarks_to_pose_small(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
-                            return_valid: bool = False, workspace: torch.Tensor | None = None):
-    """landmarks_to_pose for small batches (split-f16 blob only): one launch per big layer (five launches; seven with a strict blob) spread
-    over the whole chip, bit-identical results."""
-    return _k2_forward("small", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
-
-
-def landmarks_to_pose_streamed(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
-                               return_valid: bool = False, workspace: torch.Tensor | None = None):
-    """landmarks_to_pose (strict-fast blob only) as trunk launch + streamed tail launch + the f32 re-evaluation launch
-    (nlml_landmarks_to_pose_streamed): bit-identical to the fused kernel, measured 1.4-2.2 % faster at 65,536 faces; nothing calls it by default
-    (DESIGN.md section 3).  The hand-over buffer (1 KB per face) is cached per device and stream like the layer-per-launch path's scratch."""
-    return _k2_forward("streamed", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
-
-
-def landmarks_to_pose_quad(raw: torch.Tensor, blob: torch.Tensor, normalize: bool = True, return_latent: bool = False,
-                           return_valid: bool = False, workspace: torch.Tensor | None = None):
-    """landmarks_to_pose (strict-fast blob only) through the four-tile kernel whatever the batch size (nlml_landmarks_to_pose_quad: a
-    workgroup runs layers 0-2 over four tiles, then the streamed tail once; + the f32 re-evaluation launch): bit-identical to the fused
-    kernel.  landmarks_to_pose itself takes this path for whole rounds of 256 faces per compute unit (DESIGN.md section 3).  The
-    hand-over buffer (1 KB per face) is cached per device and stream like the streamed path's."""
-    return _k2_forward("quad", None, raw, blob, F_REF, normalize, return_latent, return_valid, workspace)
-
-
-def encoder_heads_fwd_quad(x: torch.Tensor, blob: torch.Tensor, F: int, return_latent: bool = False,
-                           return_valid: bool = False, workspace: torch.Tensor | None = None):
-    """encoder_heads_fwd (strict-fast blob only, rows 16-byte aligned) through the four-tile kernel whatever the batch size
-    (nlml_encoder_heads_fwd_quad); see landmarks_to_pose_quad."""
-    return _k2_forward("quad", x, None, blob, F, None, return_latent, return_valid, workspace)
-
-
 # ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------
 _eval_ws: dict = {}
 
@@ -491,7 +461,6 @@ def _eval_workspace(B: int, K: int, device) -> torch.Tensor:
 
 def _eval_intervals(intervals):
     """[(axis, low, high), ...] -> (h_intervals f64[K,2], h_axes i32[K]) as ctypes arrays, K."""
-    import ctypes as C
     iv = [(int(a), float(lo), float(hi)) for a, lo, hi in intervals]
     K = len(iv)
     h_iv = (C.c_double * max(1, 2 * K))(*[v for _, lo, hi in iv for v in (lo, hi)])
@@ -524,7 +493,6 @@ def pose_eval(pose: torch.Tensor, gt: torch.Tensor, valid: torch.Tensor | None =
         valid = valid.contiguous()
         valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
     pose, gt = pose.contiguous(), gt.contiguous()
-    import ctypes as C
     h_lo = (C.c_double * 3)(*([-float("inf")] * 3 if lo is None else [float(v) for v in lo]))
     h_hi = (C.c_double * 3)(*([float("inf")] * 3 if hi is None else [float(v) for v in hi]))
     h_iv, h_ax, K = _eval_intervals(intervals)
@@ -563,3 +531,27 @@ def pose_eval_merge(records: torch.Tensor, K: int):
         _lib.check(_lib.lib().nlml_pose_eval_merge(records.data_ptr(), records.shape[0], int(K), record.data_ptr(), result.data_ptr(),
                                                    stream), "nlml_pose_eval_merge")
     return record, result
+
+
+# ---------------------------------------------------------------------------------------------
+# torch.ops.nlml_hpe.* (SURVEY.md 8b "Underlying op") come from COMPILED code: csrc/torch_ops.cpp, a TORCH_LIBRARY shim over the same
+# C ABI (shape / dtype checks, torch's allocator, the operand device's current stream), built next to this file as
+# libnlml_torch_ops.so by csrc/Makefile.  GPU backend only: a CPU tensor has no kernel to dispatch to and raises.  A missing library
+# raises here -- the ops are part of the boundary.
+TORCH_OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libnlml_torch_ops.so")
+
+
+def _load_torch_ops():
+    if not os.path.exists(TORCH_OPS_PATH):
+        raise _lib.NlmlError(f"{TORCH_OPS_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                             "(make -C nlml_hpe_amd/csrc); torch.ops.nlml_hpe.* are registered from it")
+    _lib.lib()                                  # the C ABI library the shim links against, checked symbol by symbol first
+    torch.ops.load_library(TORCH_OPS_PATH)
+    # the registered ops; *_small take an explicit workspace, landmarks_to_pose_valid is the video tick's forward (pose + face mask)
+    for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
+                 "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
+                 "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks"):
+        getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
+
+
+_load_torch_ops()

@@ -272,6 +272,84 @@ def test_mixed_launch_quad_part_and_fused_remainder_in_one_call(repo_root, devic
     assert r["ops_same"] == "True"
 
 
+# ---- 6b. the hosts ask the library (nlml_k2_quad_part): what they then call, seen in ops' pooled workspaces
+_CHILD_HOSTS = r"""
+import os, sys
+sys.path.insert(0, %(root)r)
+import torch
+from nlml_hpe_amd import _lib, ops, synth, weights
+dev = torch.device("cuda:0")
+heads = weights.load_head_state_dicts(os.path.join(%(root)r, "models"))
+sd = synth.encoder_state_dict(1404, seed=0)
+strict = torch.from_numpy(weights.pack_blob(sd, heads, _lib.MODE_F16X2S)).to(dev)
+L = _lib.lib()
+B, F = 4708, 1404
+def plain(symbol, head, blob):
+    out = torch.full((B, 3), float("nan"), dtype=torch.float32, device=dev)
+    lat = torch.full((B, 9), float("nan"), dtype=torch.float32, device=dev)
+    val = torch.full((B,), 7, dtype=torch.uint8, device=dev)
+    rc = getattr(L, symbol)(*head, blob.data_ptr(), blob.numel(), out.data_ptr(), lat.data_ptr(), val.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0, L.nlml_last_error()
+    return out, lat, val
+def same(a, b):
+    return all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for x, y in zip(a, b))
+def ws_pools():
+    return [t.numel() for k, v in ops._k2_ws.items() if k[0] == "ws" for t in v]
+if sys.argv[1] == "eligible":
+    raw = torch.from_numpy(synth.raw_landmarks(B, seed=4)).to(dev)
+    raw[B // 2] = 0.0
+    want = plain("nlml_landmarks_to_pose", (raw.data_ptr(), B, 1), strict)
+    o = ops.landmarks_to_pose(raw, strict, True, return_latent=True, return_valid=True)
+    print("RESULT eligible", same(want, (o[0], o[1], o[2].to(torch.uint8))), [k[0] for k in ops._k2_ws], [len(v) for v in ops._k2_ws.values()], ws_pools())
+else:
+    feats = torch.from_numpy(synth.features(B, F, seed=12)).to(dev)
+    feats[B // 2] = 0.0
+    off = torch.zeros((B * F + 4,), dtype=torch.float32, device=dev)
+    x_off = off[1:1 + B * F].view(B, F)                  # rows starting one float into an aligned buffer
+    x_off.copy_(feats)
+    pad = torch.zeros((B, F + 2), dtype=torch.float32, device=dev)
+    x_pad = pad[:, :F]                                   # row stride F + 2
+    x_pad.copy_(feats)
+    fast = torch.from_numpy(weights.pack_blob(sd, heads, _lib.MODE_F16X2)).to(dev)
+    assert off.data_ptr() %% 16 == 0 and x_off.data_ptr() %% 16 == 4 and x_pad.stride(0) == F + 2 and feats.data_ptr() %% 16 == 0
+    for name, x, ld, blob in (("offset", x_off, F, strict), ("stride", x_pad, F + 2, strict), ("fast-blob", feats, F, fast)):
+        want = plain("nlml_encoder_heads_fwd", (x.data_ptr(), ld, B, F), blob)
+        o = ops.encoder_heads_fwd(x, blob, F, return_latent=True, return_valid=True)
+        t = torch.ops.nlml_hpe.encoder_heads_fwd(x, blob, F)
+        torch.cuda.synchronize()
+        print("RESULT", name, same(want, (o[0], o[1], o[2].to(torch.uint8))), torch.equal(t.view(torch.uint8), want[0].view(torch.uint8)),
+              [k[0] for k in ops._k2_ws])
+"""
+
+
+def _child_hosts(repo_root, which):
+    env = {k: v for k, v in os.environ.items() if k not in ("NLML_K2_QUAD_MIN", "NLML_K2_QUAD_CUS", "NLML_K2_STREAMED_MIN")}
+    env["NLML_K2_QUAD_CUS"] = "2"
+    r = subprocess.run([sys.executable, "-c", _CHILD_HOSTS % {"root": repo_root}, which], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return [l.split(None, 2)[1:] for l in r.stdout.splitlines() if l.startswith("RESULT")]
+
+
+@pytest.mark.gpu
+def test_ops_takes_the_ws_form_with_the_quad_parts_workspace_for_eligible_rows(repo_root, device):
+    """4,708 faces on a "two-unit device" (the mixed-launch test's split): ops.landmarks_to_pose on aligned raw rows pools exactly one
+    workspace, under the "ws" form, of the quad part's 72 tiles, and computes the plain C call's bits."""
+    (name, rest), = _child_hosts(repo_root, "eligible")
+    assert name == "eligible" and rest == f"True ['ws'] [1] [{72 * 65536}]", rest
+
+
+@pytest.mark.gpu
+def test_hosts_make_the_plain_call_for_rows_and_blobs_the_rule_excludes(repo_root, device):
+    """The same batch as feature rows one float into an aligned buffer, with row stride F + 2, and aligned with a fast-mode blob:
+    ops.encoder_heads_fwd (pose, latent, mask) and torch.ops.nlml_hpe.encoder_heads_fwd (pose) equal nlml_encoder_heads_fwd on the same
+    rows bit for bit, and ops pools no workspace."""
+    got = _child_hosts(repo_root, "ineligible")
+    assert [g[0] for g in got] == ["offset", "stride", "fast-blob"]
+    for name, rest in got:
+        assert rest == "True True []", f"{name}: {rest}"
+
+
 @pytest.mark.gpu
 def test_default_route_at_the_benchmark_size(blob, device):
     """65,536 faces: what bench.py times.  On a 256-unit device ops.landmarks_to_pose takes the four-tile kernel for the whole batch

@@ -1,4 +1,4 @@
-"""Fused kernel against the layer-per-launch path at 3,072 ... 16,384 faces, both split-f16 modes (the crossovers behind\nHIPPoseModel.small_batch_max).  Development aid."""
+"""Fused kernel against the layer-per-launch path at 3,072 ... 16,384 faces, both split-f16 modes (the crossover that goes into\nkSmallMax in nlml_hpe_amd/csrc/abi.cpp, which nlml_k2_small_batch_max and so HIPPoseModel.small_batch_max return).  Development aid."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
