@@ -68,6 +68,49 @@ def encoder_heads(x: np.ndarray, params, order: int = 2, want_latent=False, want
     return res[0] if len(res) == 1 else tuple(res)
 
 
+def tucker_fvec(params, cosp):
+    """f64[N,3,3] holding the f32 f-vectors (f_y, f_p, f_r) of every parameter row, from oracle.tucker.f_vectors (numpy's cos)."""
+    from . import tucker as TK
+    params = np.asarray(params, dtype=np.float64)
+    Py, Pp, Pr = np.asarray(cosp, dtype=np.float64).reshape(3, 3, 4)
+    with np.errstate(all="ignore"):
+        return np.array([np.stack(TK.f_vectors(p, Py, Pp, Pr)) for p in params], dtype=np.float64).reshape(len(params), 3, 3)
+
+
+def tucker_objective_fast(Wm, x, params, cosp, x_index=None, ldx=None, want_xhat=False, variant=0, fvec=None):
+    """The matrix-core ("fast") order of the TD objective for any identity rank R (oracle_tucker_objective_fast): Wm f32[27R,1404],
+    params f64[N,3+R], x f32[M,1404] -- or, with ldx, a buffer of rows of that stride -- evaluation n on row x_index[n] (row n without).
+    fvec f64[N,3,3]: tucker_fvec(params, cosp) unless given.  variant != 0: the deliberately wrong orders listed at the C function."""
+    Wm = np.ascontiguousarray(Wm, dtype=np.float32).reshape(-1, 1404)
+    R, rem = divmod(Wm.shape[0], 27)
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    N = params.shape[0]
+    if rem or not 1 <= R <= 16 or params.shape != (N, 3 + R):
+        raise ValueError(f"Wm {Wm.shape} / params {params.shape}: expected [27R,1404] and [N,3+R] with R in 1..16")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if ldx is None:
+        x = x.reshape(-1, 1404)
+        ldx, rows = 1404, x.shape[0]
+    else:
+        rows = x.size // ldx
+        if ldx < 1404 or x.size != rows * ldx:
+            raise ValueError("x: expected whole rows of stride ldx >= 1404")
+    if x_index is not None:
+        x_index = np.ascontiguousarray(x_index, dtype=np.int32)
+        if x_index.shape != (N,) or (N and (x_index.min() < 0 or x_index.max() >= rows)):
+            raise IndexError("x_index: expected [N] of row numbers")
+    elif rows < N:
+        raise ValueError(f"x has {rows} rows but params has {N}")
+    fvec = np.ascontiguousarray(tucker_fvec(params, cosp) if fvec is None else fvec, dtype=np.float64)
+    if fvec.shape != (N, 3, 3):
+        raise ValueError("fvec: expected [N,3,3]")
+    err = np.empty(N)
+    xh = np.empty((N, 1404)) if want_xhat else None
+    lib().oracle_tucker_objective_fast(_p(Wm), C.c_int(R), _p(x), C.c_int64(ldx), _p(x_index) if x_index is not None else None,
+                                       _p(params), _p(fvec), C.c_int64(N), _p(err), _p(xh) if want_xhat else None, C.c_int(int(variant)))
+    return (err, xh) if want_xhat else err
+
+
 def tucker_objective(Wm, x, params, cosp, want_xhat=False, device_order=False, reference_order=False):
     """reference_order: np.einsum's own (i,j,k,l)-outer sum of separately rounded products and numpy's pairwise np.sum --
     bit-identical to the reference's objective (FX4); device_order: the fast kernel's reduction tree."""

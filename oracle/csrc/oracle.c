@@ -219,6 +219,77 @@ void oracle_tucker_objective_reforder(const float* Wm, const float* x, const dou
   }
 }
 
+/* The MATRIX-CORE ("fast") order for any identity rank R, written from the prose of nlml_hpe_amd/csrc/tucker_common.h (its header
+ * comment) and tucker_rank.h; no kernel header is included.
+ *   Wm f32[27 R,1404]; x f32 rows of stride ldx (>= 1404; the pad columns are never read); x_index i32[N] or NULL: evaluation n reads
+ *   row x_index[n] (row n without); params f64[N,3+R]; fvec f64[N,3,3] holding f32 values (f_y, f_p, f_r: an INPUT, so that libm does
+ *   not enter here and the caller decides whose cos it is); err f64[N]; xhat f64[N,1404] or NULL.
+ *   c[q]      = ((u_i * f_y[j]) * f_p[k]) * f_r[l], q = ((i*3+j)*3+k)*3+l < 27 R, every product rounded on its own;
+ *   x_hat[m]  = one fma(c[q], (double)Wm[q][m], acc) chain, q ascending from +0.0 (what one matrix-core output accumulates; the zero
+ *               coefficient rows that pad 27 R to a multiple of 4 multiply a finite Wm entry and add +0.0 or -0.0 to a chain that is
+ *               not -0.0: no change, and they are left out here);
+ *   err       = residual_device_order.
+ * variant 0 is that order.  The others are deliberately WRONG orders with which tests/test_td_fast_order_host.py shows that its inputs
+ * tell them apart: 1 q descending; 2 multiply and add rounded separately instead of fused; 3 the residual summed left to right over
+ * m (x_hat is the model's); 4 wave 7's four repeated columns 1228..1231 counted twice (x_hat is the model's); 5 the coefficient
+ * rounded to f32 before the product. */
+void oracle_tucker_objective_fast(const float* Wm, int R, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
+                                  const double* fvec, int64_t N, double* err, double* xhat, int variant) {
+  const int Q = 27 * R, npar = 3 + R;
+#pragma omp parallel for schedule(static)
+  for (int64_t n = 0; n < N; ++n) {
+    const double* p = params + n * npar;
+    const double* f = fvec + n * 9;
+    const float* xrow = x + (x_index ? (int64_t)x_index[n] : n) * ldx;
+    double c[27 * 16];
+    for (int q = 0; q < Q; ++q) {
+      c[q] = ((p[3 + q / 27] * f[(q / 9) % 3]) * f[3 + (q / 3) % 3]) * f[6 + q % 3];
+      if (variant == 5) c[q] = (double)(float)c[q];
+    }
+    double accv[1404];
+    for (int m = 0; m < 1404; ++m) accv[m] = 0.0;
+    for (int s = 0; s < Q; ++s) {   /* row by row: each column's chain still takes its q in this order */
+      const int q = variant == 1 ? Q - 1 - s : s;
+      const float* w = Wm + (size_t)q * 1404;
+      if (variant == 2)
+        for (int m = 0; m < 1404; ++m) { const double t = c[q] * (double)w[m]; accv[m] = t + accv[m]; }   /* (-ffp-contract=off: two roundings) */
+      else
+        for (int m = 0; m < 1404; ++m) accv[m] = fma(c[q], (double)w[m], accv[m]);
+    }
+    if (xhat) memcpy(xhat + n * 1404, accv, sizeof accv);
+    if (variant == 3) {
+      double s = 0.0;
+      for (int m = 0; m < 1404; ++m) { const double r = (double)xrow[m] - accv[m]; s = fma(r, r, s); }
+      err[n] = 0.5 * s;
+    } else if (variant == 4) {
+      /* the model's tree, but wave 7 also sums its first four columns: lanes 0 (mb 0..3) of the segment from 1228.  Same chain
+       * positions, so only those four extra terms differ. */
+      double red[8];
+      for (int w = 0; w < 8; ++w) {
+        const int base = w < 7 ? 176 * w : 1404 - 176;
+        double v[16], t[16];
+        for (int cl = 0; cl < 16; ++cl) {
+          double s = 0.0;
+          for (int mb = 0; mb < 11; ++mb) {
+            const int lc = mb < 8 ? 64 * (mb >> 2) + 4 * cl + (mb & 3) : 128 + 3 * cl + (mb - 8);
+            const double r = (double)xrow[base + lc] - accv[base + lc];
+            s = fma(r, r, s);
+          }
+          v[cl] = s;
+        }
+        for (int off = 1; off < 16; off <<= 1) {
+          for (int cl = 0; cl < 16; ++cl) t[cl] = v[cl] + v[cl ^ off];
+          memcpy(v, t, sizeof v);
+        }
+        red[w] = v[0];
+      }
+      err[n] = 0.5 * (((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7])));
+    } else {
+      err[n] = residual_device_order(xrow, accv);
+    }
+  }
+}
+
 void oracle_tucker_objective(const float* Wm, const float* x, const double* params, const double* cosp,
                              int64_t N, double* err, double* xhat, int device_order) {
 #pragma omp parallel for schedule(static)

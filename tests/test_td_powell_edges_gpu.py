@@ -8,7 +8,9 @@ bit for bit (powell_cases.same_bits: any NaN equals any NaN); there is no tolera
                         2, 3, 4 live, tucker_round16 (5, 16); reference order: every pass size and partition;
   3  sparse live masks  real faces at chosen machine slots, NaN faces (gone after 1 + 3 n evaluations) in all others;
   4  the C entry point  ldx != 1404 with NaN in the pad columns, each optional output NULL, nothing written past row N - 1;
-  5  far starts         x0 = (3e4, -2e4, 1e5, 0...): cr_cos.h's double-double reduction at k ~ 1.9e5 inside the kernel;
+  5  far starts         x0 = (3e4, -2e4, 1e5, 0...): cr_cos.h's double-double reduction at k ~ 1.9e5 inside the kernel (host replays:
+                        reference order here, fast order in tests/test_td_fast_order_gpu.py, which also replays ordinary fast-order runs
+                        on the host's matrix-core objective at ranks 1, 3, 5, 8);
   6  wide batch         645 faces = 40 workgroups + 5: fun == the objective at the returned x, and reversal.
 
 Deliberately NOT pinned: status 3 (maxiter) -- unreachable with the fixed limits maxiter = maxfev = 1000 n, since an iteration costs
@@ -271,7 +273,8 @@ def test_far_start_replays_on_the_host(R, dev):
 @pytest.mark.parametrize("R", [3, 5])
 def test_far_start_in_fast_order(R, dev):
     """The same start on the matrix cores: fun is the fast-order objective at the returned x; at rank 5 nlml_tucker_powell_ex and
-    nlml_tucker_powell_r agree."""
+    nlml_tucker_powell_r agree.  (The host replay of the rank-5 run on the matrix-core objective, oracle_tucker_objective_fast, is
+    tests/test_td_fast_order_gpu.py::test_fast_powell_at_rank_five_replays_from_a_far_start.)"""
     x0 = PC.bad_starts(R)["far_start"][None]
     X = PC.base_face(dev.art, R)[None]
     got = dev.run(R, "fast", X, x0=x0)
