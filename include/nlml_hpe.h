@@ -536,6 +536,51 @@ int nlml_pose_eval_merge(const double* records, int64_t n, int n_intervals, doub
 int nlml_cosine_table(const float* angles_rad, int64_t n, const double* cos_params, int R, double* out, void* stream);
 int nlml_mode5_product(const float* core, const float* U_feat, int Q, int R5, int M, float* W, void* stream);
 
+/* K7: the device primitives of the Tucker decomposition of the rotation training tensor (TD_main.py:181; the driver is
+ * nlml_hpe_amd/tucker_decompose.py).  The tensor X is f32[I,ny,np,nr,M], row-major; A is its mode-1 unfolding f32[I,K], K = ny np nr M.
+ * Every sum and every Gram is f64, factors are f64 [n,R] row-major (column r = the r-th vector).  No floating-point atomics: partial
+ * sums go to the caller's workspace and are added in a fixed order that depends on the shape alone, so two calls give the same bits.
+ * All offsets are 64-bit.  Checks, in this order, each NLML_E_BADARG with a message and before any GPU call: a NULL required buffer;
+ * an extent < 1 or beyond its limit; a product of extents beyond 64-bit byte offsets; a pointer that is not aligned to its element
+ * (4 bytes f32, 8 bytes f64 and workspace); a workspace shorter than the *_workspace_bytes query (which returns 0 for a shape the
+ * entry point refuses).
+ *
+ * nlml_mode_gram (K7a)  G f64[I,I] = A A^T on the f64 matrix cores, upper-triangle tiles then mirrored: G is symmetric bit for bit.
+ *   1 <= I <= NLML_GRAM_I_MAX, K >= 1.  K is cut into slices of at least NLML_GRAM_KCHUNK columns (more when the tiles
+ *   alone fill the device), added in ascending order.
+ * nlml_pose_grams (K7b)  Gy f64[ny,ny], Gp f64[np,np], Gr f64[nr,nr]: the Grams of the mode-2, -3 and -4 unfoldings in one pass
+ *   over X; a NULL output is skipped (at least one must be given).  ny, np, nr in 1..NLML_POSE_BINS_MAX and
+ *   ny np nr <= NLML_POSE_GRAMS_MAX_CELLS (all cells by 32 columns stay in LDS).
+ * nlml_project_identity (K7c)  out f32[R,K] = U^T A, U f64[I,R], 1 <= R <= NLML_TUCKER_RANK_MAX; i-ascending f64 fma chain, one
+ *   rounding to f32.
+ * nlml_project_pose (K7d)  out f32[I,ny',np',nr',M] = X x_2 Uy^T x_3 Up^T x_4 Ur^T, Uy f64[ny,ry] etc.; a NULL factor leaves its
+ *   mode as it is (n' = n, its rank argument is ignored), else n' = its rank in 1..NLML_POSE_RANK_MAX.  f64 fma chains nested
+ *   roll inside pitch inside yaw, each ascending; one rounding to f32.  With all three NULL, out is X copied bit for bit.
+ *
+ * The *_ex forms take or give a tensor in f64 where the flag (a_f64, x_f64, out_f64) is nonzero -- same shapes, same sums, 8-byte
+ * alignment, and no rounding of an f64 output.  The decomposition keeps its projected tensors that way between two steps: a factor
+ * computed from an f32-rounded projection sits 2^-24 from the exact one, far outside the f64 Grams' own error.  The plain forms are
+ * the *_ex forms with every flag 0.  nlml_pose_grams_workspace_bytes serves both element types. */
+#define NLML_GRAM_I_MAX      4096
+#define NLML_GRAM_KCHUNK     4096
+#define NLML_POSE_BINS_MAX        32
+#define NLML_POSE_GRAMS_MAX_CELLS 768
+#define NLML_POSE_RANK_MAX        3
+size_t nlml_mode_gram_workspace_bytes(int64_t I, int64_t K);
+int nlml_mode_gram(const float* A, int64_t I, int64_t K, double* G, void* workspace, size_t workspace_bytes, void* stream);
+size_t nlml_pose_grams_workspace_bytes(int64_t I, int ny, int np, int nr, int64_t M);
+int nlml_pose_grams(const float* X, int64_t I, int ny, int np, int nr, int64_t M, double* Gy, double* Gp, double* Gr,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int nlml_project_identity(const float* A, int64_t I, int64_t K, const double* U, int R, float* out, void* stream);
+int nlml_project_pose(const float* X, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up, int rp,
+                      const double* Ur, int rr, float* out, void* stream);
+int nlml_mode_gram_ex(const void* A, int a_f64, int64_t I, int64_t K, double* G, void* workspace, size_t workspace_bytes, void* stream);
+int nlml_pose_grams_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, double* Gy, double* Gp, double* Gr,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int nlml_project_identity_ex(const float* A, int64_t I, int64_t K, const double* U, int R, void* out, int out_f64, void* stream);
+int nlml_project_pose_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
+                         int rp, const double* Ur, int rr, void* out, int out_f64, void* stream);
+
 /* Host-side stepping of the same Powell state machine (no GPU involved): the caller evaluates
  * the objective.  Used to check the restated control flow against scipy on the CPU.
  *   h_state: caller-allocated buffer of nlml_powell_state_bytes() bytes.

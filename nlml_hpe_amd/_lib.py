@@ -87,6 +87,23 @@ SYMBOLS = {
     "nlml_pose_eval_merge": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlml_cosine_table": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nlml_mode5_product": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # K7 (Tucker decomposition): A, I, K, G, ws, ws_bytes | X, I, ny, np, nr, M, Gy, Gp, Gr, ws, ws_bytes | A, I, K, U, R, out |
+    # X, I, ny, np, nr, M, (U, rank) x 3, out; + stream
+    "nlml_mode_gram_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "nlml_mode_gram": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_pose_grams_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "nlml_pose_grams": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_project_identity": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "nlml_project_pose": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_void_p, C.c_int] * 3
+                          + [C.c_void_p, C.c_void_p]),
+    # the same with an f64 tensor in or out where the flag after its pointer is nonzero
+    "nlml_mode_gram_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_pose_grams_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_project_identity_ex": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nlml_project_pose_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_void_p, C.c_int] * 3
+                             + [C.c_void_p, C.c_int, C.c_void_p]),
     "nlml_powell_state_bytes": (C.c_size_t, []),
     "nlml_powell_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "nlml_powell_step": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
@@ -114,6 +131,11 @@ ROT_INTRINSIC = 0          # NLML_ROT_INTRINSIC: stages pitch, yaw, roll
 ROT_EXTRINSIC = 1          # NLML_ROT_EXTRINSIC: stages roll, yaw, pitch, the matrices transposed by the caller
 ROT_ORDER_NAMES = {"intrinsic": ROT_INTRINSIC, "extrinsic": ROT_EXTRINSIC}
 TUCKER_RANK_MIN, TUCKER_RANK_MAX = 1, 16  # NLML_TUCKER_RANK_MIN / NLML_TUCKER_RANK_MAX: identity ranks of the *_r entry points
+MODE_GRAM_I_MAX = 4096             # NLML_GRAM_I_MAX
+MODE_GRAM_KCHUNK = 4096            # NLML_GRAM_KCHUNK: the least columns of a K slice of nlml_mode_gram
+POSE_BINS_MAX = 32                 # NLML_POSE_BINS_MAX
+POSE_GRAMS_MAX_CELLS = 768         # NLML_POSE_GRAMS_MAX_CELLS
+POSE_RANK_MAX = 3                  # NLML_POSE_RANK_MAX
 POSE_EVAL_MAX_INTERVALS = 64       # NLML_POSE_EVAL_MAX_INTERVALS
 POSE_EVAL_FACES_PER_RECORD = 2048  # NLML_POSE_EVAL_FACES_PER_RECORD
 

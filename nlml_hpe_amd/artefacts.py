@@ -5,7 +5,8 @@
                          columns = the optimised cosine rows of outputs/features/Trained_data.npz
   core_to_W              W = core x_5 U_feat (TD_main.py:232-238), the tensor TD_Tester.objective contracts
 
-Training itself (the MLP fits, the Tucker decomposition, TD_Trainer) stays out of scope.
+The Tucker decomposition that produces W in the first place is nlml_hpe_amd/tucker_decompose.py (on the device); its ``thin_core``
+gives core_to_W a real (core, U_feat) pair.  The MLP fits and TD_Trainer's cosine fit stay out of scope.
 """
 from __future__ import annotations
 

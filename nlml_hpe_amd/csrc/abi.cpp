@@ -398,6 +398,102 @@ int nlml_mode5_product(const float* core, const float* U_feat, int Q, int R5, in
   return launch_mode5_product(core, U_feat, Q, R5, M, W, stream);
 }
 
+// ---- K7: the Tucker decomposition's primitives (tucker_decompose.hip) ----------------------------------
+static int k7_refuse(const char* who, const char* what) {
+  char msg[160];
+  std::snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return fail(NLML_E_BADARG, msg);
+}
+static bool k7_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// I x K within 64-bit byte offsets of f64 partials (I <= 4096 keeps every product below 2^63)
+static bool k7_matrix_ok(int64_t I, int64_t K) { return I >= 1 && I <= NLML_GRAM_I_MAX && K >= 1 && K <= INT64_MAX / (8 * NLML_GRAM_I_MAX); }
+static bool k7_bins_ok(int ny, int np, int nr) {
+  return ny >= 1 && np >= 1 && nr >= 1 && ny <= NLML_POSE_BINS_MAX && np <= NLML_POSE_BINS_MAX && nr <= NLML_POSE_BINS_MAX;
+}
+// I x (ny np nr) x M elements within 64-bit byte offsets
+static bool k7_tensor_ok(int64_t I, int ny, int np, int nr, int64_t M) {
+  int64_t n = 0;
+  return I >= 1 && M >= 1 && !__builtin_mul_overflow(I, (int64_t)ny * np * nr, &n) && !__builtin_mul_overflow(n, M, &n) && n <= INT64_MAX / 8;
+}
+
+size_t nlml_mode_gram_workspace_bytes(int64_t I, int64_t K) { return k7_matrix_ok(I, K) ? mode_gram_workspace_bytes(I, K) : 0; }
+
+int nlml_mode_gram(const float* A, int64_t I, int64_t K, double* G, void* workspace, size_t workspace_bytes, void* stream) {
+  return nlml_mode_gram_ex(A, 0, I, K, G, workspace, workspace_bytes, stream);
+}
+
+int nlml_mode_gram_ex(const void* A, int a_f64, int64_t I, int64_t K, double* G, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "mode_gram";
+  if (!A || !G || !workspace) return k7_refuse(who, "null buffer (A, G, workspace)");
+  if (I < 1 || I > NLML_GRAM_I_MAX) return k7_refuse(who, "I outside 1..NLML_GRAM_I_MAX (4096)");
+  if (!k7_matrix_ok(I, K)) return k7_refuse(who, "K < 1 or too large for 64-bit byte offsets");
+  if (!k7_aligned(A, a_f64 ? 8 : 4) || !k7_aligned(G, 8) || !k7_aligned(workspace, 8))
+    return k7_refuse(who, "A must be aligned to its element (4 bytes f32, 8 bytes f64), G and the workspace 8-byte aligned");
+  if (workspace_bytes < mode_gram_workspace_bytes(I, K)) return k7_refuse(who, "workspace too small (nlml_mode_gram_workspace_bytes)");
+  return launch_mode_gram(A, a_f64 != 0, I, K, G, workspace, stream);
+}
+
+static bool k7_pose_grams_ok(int64_t I, int ny, int np, int nr, int64_t M) {
+  return k7_bins_ok(ny, np, nr) && ny * np * nr <= NLML_POSE_GRAMS_MAX_CELLS && k7_tensor_ok(I, ny, np, nr, M);
+}
+size_t nlml_pose_grams_workspace_bytes(int64_t I, int ny, int np, int nr, int64_t M) {
+  return k7_pose_grams_ok(I, ny, np, nr, M) ? pose_grams_workspace_bytes(I, ny, np, nr, M) : 0;
+}
+
+int nlml_pose_grams(const float* X, int64_t I, int ny, int np, int nr, int64_t M, double* Gy, double* Gp, double* Gr, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  return nlml_pose_grams_ex(X, 0, I, ny, np, nr, M, Gy, Gp, Gr, workspace, workspace_bytes, stream);
+}
+
+int nlml_pose_grams_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, double* Gy, double* Gp, double* Gr,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "pose_grams";
+  if (!X || !workspace || (!Gy && !Gp && !Gr)) return k7_refuse(who, "null buffer (X, workspace, and at least one of Gy, Gp, Gr)");
+  if (I < 1 || M < 1) return k7_refuse(who, "I < 1 or M < 1");
+  if (!k7_bins_ok(ny, np, nr)) return k7_refuse(who, "ny, np, nr outside 1..NLML_POSE_BINS_MAX (32)");
+  if (ny * np * nr > NLML_POSE_GRAMS_MAX_CELLS) return k7_refuse(who, "ny np nr beyond NLML_POSE_GRAMS_MAX_CELLS (768): the slab does not fit in LDS");
+  if (!k7_tensor_ok(I, ny, np, nr, M)) return k7_refuse(who, "tensor too large for 64-bit byte offsets");
+  if (!k7_aligned(X, x_f64 ? 8 : 4) || !k7_aligned(Gy, 8) || !k7_aligned(Gp, 8) || !k7_aligned(Gr, 8) || !k7_aligned(workspace, 8))
+    return k7_refuse(who, "X must be aligned to its element (4 bytes f32, 8 bytes f64), the Grams and the workspace 8-byte aligned");
+  if (workspace_bytes < pose_grams_workspace_bytes(I, ny, np, nr, M)) return k7_refuse(who, "workspace too small (nlml_pose_grams_workspace_bytes)");
+  return launch_pose_grams(X, x_f64 != 0, I, ny, np, nr, M, Gy, Gp, Gr, workspace, stream);
+}
+
+int nlml_project_identity(const float* A, int64_t I, int64_t K, const double* U, int R, float* out, void* stream) {
+  return nlml_project_identity_ex(A, I, K, U, R, out, 0, stream);
+}
+
+int nlml_project_identity_ex(const float* A, int64_t I, int64_t K, const double* U, int R, void* out, int out_f64, void* stream) {
+  const char* who = "project_identity";
+  if (!A || !U || !out) return k7_refuse(who, "null buffer (A, U, out)");
+  if (I < 1 || K < 1) return k7_refuse(who, "I < 1 or K < 1");
+  if (R < NLML_TUCKER_RANK_MIN || R > NLML_TUCKER_RANK_MAX) return k7_refuse(who, "R outside 1..NLML_TUCKER_RANK_MAX (16)");
+  int64_t n = 0;
+  if (__builtin_mul_overflow(I, K, &n) || n > INT64_MAX / 8) return k7_refuse(who, "A too large for 64-bit byte offsets");
+  if (!k7_aligned(A, 4) || !k7_aligned(out, out_f64 ? 8 : 4) || !k7_aligned(U, 8))
+    return k7_refuse(who, "A and out must be aligned to their element (4 bytes f32, 8 bytes f64), U 8-byte aligned");
+  return launch_project_identity(A, I, K, U, R, out, out_f64 != 0, stream);
+}
+
+int nlml_project_pose(const float* X, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up, int rp,
+                      const double* Ur, int rr, float* out, void* stream) {
+  return nlml_project_pose_ex(X, 0, I, ny, np, nr, M, Uy, ry, Up, rp, Ur, rr, out, 0, stream);
+}
+
+int nlml_project_pose_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
+                         int rp, const double* Ur, int rr, void* out, int out_f64, void* stream) {
+  const char* who = "project_pose";
+  if (!X || !out) return k7_refuse(who, "null buffer (X, out)");
+  if (I < 1 || M < 1) return k7_refuse(who, "I < 1 or M < 1");
+  if (!k7_bins_ok(ny, np, nr)) return k7_refuse(who, "ny, np, nr outside 1..NLML_POSE_BINS_MAX (32)");
+  if ((Uy && (ry < 1 || ry > NLML_POSE_RANK_MAX)) || (Up && (rp < 1 || rp > NLML_POSE_RANK_MAX)) || (Ur && (rr < 1 || rr > NLML_POSE_RANK_MAX)))
+    return k7_refuse(who, "rank of a given factor outside 1..NLML_POSE_RANK_MAX (3)");
+  if (!k7_tensor_ok(I, ny, np, nr, M)) return k7_refuse(who, "tensor too large for 64-bit byte offsets");
+  if (!k7_aligned(X, x_f64 ? 8 : 4) || !k7_aligned(out, out_f64 ? 8 : 4) || !k7_aligned(Uy, 8) || !k7_aligned(Up, 8) || !k7_aligned(Ur, 8))
+    return k7_refuse(who, "X and out must be aligned to their element (4 bytes f32, 8 bytes f64), the factors 8-byte aligned");
+  return launch_project_pose(X, x_f64 != 0, I, ny, np, nr, M, Uy, ry, Up, rp, Ur, rr, out, out_f64 != 0, stream);
+}
+
 // ---- K5 evaluation ---------------------------------------------------------------------------------
 static bool eval_k_ok(int K) { return K >= 0 && K <= NLML_POSE_EVAL_MAX_INTERVALS; }
 static int64_t eval_records(int64_t B) { return (B + NLML_POSE_EVAL_FACES_PER_RECORD - 1) / NLML_POSE_EVAL_FACES_PER_RECORD; }

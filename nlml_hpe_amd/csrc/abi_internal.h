@@ -128,6 +128,17 @@ size_t tucker_gradient_workspace_bytes(int64_t N);
 int launch_tucker_gradient(const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
                            const double* cos_params, int64_t N, double* err, double* grad, int r_id, void* workspace, void* stream);
 
+// tucker_decompose.hip (K7a..K7d): the arguments are checked by the caller (abi.cpp); the workspace sizes are 0-free for checked shapes
+size_t mode_gram_workspace_bytes(int64_t I, int64_t K);
+// a_f64 / x_f64 / out_f64: that tensor is f64 instead of f32 (a projected tensor the decomposition keeps unrounded between two steps)
+int launch_mode_gram(const void* A, int a_f64, int64_t I, int64_t K, double* G, void* ws, void* stream);
+size_t pose_grams_workspace_bytes(int64_t I, int ny, int np, int nr, int64_t M);
+int launch_pose_grams(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, double* Gy, double* Gp, double* Gr, void* ws,
+                      void* stream);
+int launch_project_identity(const float* A, int64_t I, int64_t K, const double* U, int R, void* out, int out_f64, void* stream);
+int launch_project_pose(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
+                        int rp, const double* Ur, int rr, void* out, int out_f64, void* stream);
+
 // video_post.hip
 int launch_video_post(const float* pose_rad, const float* raw, const uint8_t* valid, int64_t S, double frame_w,
                       double frame_h, double alpha, double max_jump, double size, double* state, double* smoothed,

@@ -376,7 +376,97 @@ std::tuple<at::Tensor, at::Tensor> pose_eval_merge(const at::Tensor& records_, i
   return {record, result};
 }
 
+// ---- K7: the Tucker decomposition's primitives; workspaces come from torch's allocator ----------------------------------
+int64_t ws_doubles(size_t bytes) { return std::max<int64_t>(1, (int64_t)((bytes + 7) / 8)); }
+
+const at::Tensor need_tensor5(const at::Tensor& X_, const char* name) {
+  need(X_, name, at::kFloat);
+  TORCH_CHECK(X_.dim() == 5, name, ": expected [I,ny,np,nr,M], got ", X_.sizes());
+  TORCH_CHECK(X_.size(1) <= NLML_POSE_BINS_MAX && X_.size(2) <= NLML_POSE_BINS_MAX && X_.size(3) <= NLML_POSE_BINS_MAX, name,
+              ": at most ", NLML_POSE_BINS_MAX, " bins per pose mode, got ", X_.sizes());
+  return X_.contiguous();
+}
+
+// A f32[I,K] -> G f64[I,I] = A A^T
+at::Tensor mode_gram(const at::Tensor& A_) {
+  need(A_, "A", at::kFloat);
+  TORCH_CHECK(A_.dim() == 2, "A: expected [I,K], got ", A_.sizes());
+  const at::Tensor A = A_.contiguous();
+  const int64_t I = A.size(0), K = A.size(1);
+  const auto f64 = A.options().dtype(at::kDouble);
+  at::Tensor G = at::empty({I, I}, f64), ws = at::empty({ws_doubles(nlml_mode_gram_workspace_bytes(I, K))}, f64);
+  OnDevice dev(A);
+  check(nlml_mode_gram(A.data_ptr<float>(), I, K, G.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel() * 8, dev.stream), "nlml_mode_gram");
+  return G;
+}
+
+// X f32[I,ny,np,nr,M] -> (Gy f64[ny,ny], Gp f64[np,np], Gr f64[nr,nr])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pose_grams(const at::Tensor& X_) {
+  const at::Tensor X = need_tensor5(X_, "X");
+  const int64_t I = X.size(0), ny = X.size(1), np = X.size(2), nr = X.size(3), M = X.size(4);
+  const auto f64 = X.options().dtype(at::kDouble);
+  at::Tensor Gy = at::empty({ny, ny}, f64), Gp = at::empty({np, np}, f64), Gr = at::empty({nr, nr}, f64);
+  at::Tensor ws = at::empty({ws_doubles(nlml_pose_grams_workspace_bytes(I, (int)ny, (int)np, (int)nr, M))}, f64);
+  OnDevice dev(X);
+  check(nlml_pose_grams(X.data_ptr<float>(), I, (int)ny, (int)np, (int)nr, M, Gy.data_ptr<double>(), Gp.data_ptr<double>(),
+                        Gr.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel() * 8, dev.stream), "nlml_pose_grams");
+  return {Gy, Gp, Gr};
+}
+
+// A f32[I,K], U f64[I,R] -> f32[R,K] = U^T A
+at::Tensor project_identity(const at::Tensor& A_, const at::Tensor& U_) {
+  need(A_, "A", at::kFloat);
+  need(U_, "U", at::kDouble);
+  same_device(A_, U_, "U");
+  TORCH_CHECK(A_.dim() == 2 && U_.dim() == 2 && U_.size(0) == A_.size(0), "A [I,K] and U [I,R] disagree: ", A_.sizes(), ", ", U_.sizes());
+  TORCH_CHECK(U_.size(1) >= NLML_TUCKER_RANK_MIN && U_.size(1) <= NLML_TUCKER_RANK_MAX, "U: R outside 1..", NLML_TUCKER_RANK_MAX);
+  const at::Tensor A = A_.contiguous(), U = U_.contiguous();
+  at::Tensor out = at::empty({U.size(1), A.size(1)}, A.options());
+  OnDevice dev(A);
+  check(nlml_project_identity(A.data_ptr<float>(), A.size(0), A.size(1), U.data_ptr<double>(), (int)U.size(1), out.data_ptr<float>(),
+                              dev.stream), "nlml_project_identity");
+  return out;
+}
+
+// X f32[I,ny,np,nr,M], each factor f64[n,r] or None (the mode stays) -> f32[I,ny',np',nr',M]
+at::Tensor project_pose(const at::Tensor& X_, const std::optional<at::Tensor>& Uy_, const std::optional<at::Tensor>& Up_,
+                        const std::optional<at::Tensor>& Ur_) {
+  const at::Tensor X = need_tensor5(X_, "X");
+  const std::optional<at::Tensor>* const opt[] = {&Uy_, &Up_, &Ur_};
+  const char* const names[] = {"U_yaw", "U_pitch", "U_roll"};
+  at::Tensor U[3];
+  std::vector<int64_t> shape = {X.size(0), X.size(1), X.size(2), X.size(3), X.size(4)};
+  for (int k = 0; k < 3; ++k) {
+    if (!opt[k]->has_value()) continue;
+    const at::Tensor& u = **opt[k];
+    need(u, names[k], at::kDouble);
+    same_device(X, u, names[k]);
+    TORCH_CHECK(u.dim() == 2 && u.size(0) == X.size(1 + k), names[k], ": expected [", X.size(1 + k), ",r], got ", u.sizes());
+    TORCH_CHECK(u.size(1) >= 1 && u.size(1) <= NLML_POSE_RANK_MAX, names[k], ": rank outside 1..", NLML_POSE_RANK_MAX);
+    U[k] = u.contiguous();
+    shape[1 + k] = u.size(1);
+  }
+  at::Tensor out = at::empty(shape, X.options());
+  auto ptr = [&](int k) { return U[k].defined() ? U[k].data_ptr<double>() : nullptr; };
+  auto rank = [&](int k) { return U[k].defined() ? (int)U[k].size(1) : 0; };
+  OnDevice dev(X);
+  check(nlml_project_pose(X.data_ptr<float>(), X.size(0), (int)X.size(1), (int)X.size(2), (int)X.size(3), X.size(4), ptr(0), rank(0), ptr(1),
+                          rank(1), ptr(2), rank(2), out.data_ptr<float>(), dev.stream), "nlml_project_pose");
+  return out;
+}
+
 // ---- shapes only (Meta backend: tracing / fake tensors) -------------------------------------------------------------
+at::Tensor mode_gram_meta(const at::Tensor& A) { return at::empty({A.size(0), A.size(0)}, A.options().dtype(at::kDouble)); }
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pose_grams_meta(const at::Tensor& X) {
+  const auto f64 = X.options().dtype(at::kDouble);
+  return {at::empty({X.size(1), X.size(1)}, f64), at::empty({X.size(2), X.size(2)}, f64), at::empty({X.size(3), X.size(3)}, f64)};
+}
+at::Tensor project_identity_meta(const at::Tensor& A, const at::Tensor& U) { return at::empty({U.size(1), A.size(1)}, A.options()); }
+at::Tensor project_pose_meta(const at::Tensor& X, const std::optional<at::Tensor>& Uy, const std::optional<at::Tensor>& Up,
+                             const std::optional<at::Tensor>& Ur) {
+  return at::empty({X.size(0), Uy.has_value() ? Uy->size(1) : X.size(1), Up.has_value() ? Up->size(1) : X.size(2),
+                    Ur.has_value() ? Ur->size(1) : X.size(3), X.size(4)}, X.options());
+}
 at::Tensor normalize_ipd_meta(const at::Tensor& raw, bool) { return at::empty({raw.size(0), F_REF}, raw.options()); }
 at::Tensor normalize_centroid_meta(const at::Tensor& raw) { return at::empty({raw.size(0), F_REF}, raw.options()); }
 std::tuple<at::Tensor, at::Tensor> compose_rotation_tensor_meta(const at::Tensor& base, const at::Tensor& ry, const at::Tensor& rp,
@@ -440,6 +530,10 @@ TORCH_LIBRARY(nlml_hpe, m) {
   m.def("pose_eval(Tensor pose, Tensor? valid, Tensor gt, float[] lo, float[] hi, int decimals, float[] intervals, int[] axes) "
         "-> (Tensor, Tensor)");
   m.def("pose_eval_merge(Tensor records, int K) -> (Tensor, Tensor)");
+  m.def("mode_gram(Tensor A) -> Tensor");
+  m.def("pose_grams(Tensor X) -> (Tensor, Tensor, Tensor)");
+  m.def("project_identity(Tensor A, Tensor U) -> Tensor");
+  m.def("project_pose(Tensor X, Tensor? U_yaw, Tensor? U_pitch, Tensor? U_roll) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CUDA key
@@ -459,6 +553,10 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
   m.impl("cosine_table", &cosine_table);
   m.impl("pose_eval", &pose_eval);
   m.impl("pose_eval_merge", &pose_eval_merge);
+  m.impl("mode_gram", &mode_gram);
+  m.impl("pose_grams", &pose_grams);
+  m.impl("project_identity", &project_identity);
+  m.impl("project_pose", &project_pose);
 }
 
 TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
@@ -478,4 +576,8 @@ TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("cosine_table", &cosine_table_meta);
   m.impl("pose_eval", &pose_eval_meta);
   m.impl("pose_eval_merge", &pose_eval_merge_meta);
+  m.impl("mode_gram", &mode_gram_meta);
+  m.impl("pose_grams", &pose_grams_meta);
+  m.impl("project_identity", &project_identity_meta);
+  m.impl("project_pose", &project_pose_meta);
 }

@@ -444,6 +444,107 @@ def mode5_product(core: torch.Tensor, U_feat: torch.Tensor) -> torch.Tensor:
     return W.reshape(lead + (M,))
 
 
+# ---- K7: the Tucker decomposition's primitives (csrc/tucker_decompose.hip; the driver is nlml_hpe_amd/tucker_decompose.py) -----
+def _k7_workspace(nbytes: int, device) -> torch.Tensor:
+    return torch.empty((max(1, (nbytes + 7) // 8),), dtype=torch.float64, device=device)
+
+
+def _need_f32_or_f64(t: torch.Tensor, name: str) -> int:
+    """-> the entry points' f64 flag of a tensor that may be f32 (the tensor itself) or f64 (a projection kept unrounded)."""
+    _need_cuda(t, name, t.dtype if t.dtype == torch.float64 else torch.float32)
+    return int(t.dtype == torch.float64)
+
+
+def _out_f64(out_dtype) -> int:
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"out_dtype: expected torch.float32 or torch.float64, got {out_dtype}")
+    return int(out_dtype == torch.float64)
+
+
+def _tensor5(X: torch.Tensor, name: str = "X") -> torch.Tensor:
+    _need_f32_or_f64(X, name)
+    if X.dim() != 5 or min(X.shape) < 1 or max(X.shape[1:4]) > _lib.POSE_BINS_MAX:
+        raise ValueError(f"{name}: expected a non-empty [I,ny,np,nr,M] with at most {_lib.POSE_BINS_MAX} bins per pose mode, "
+                         f"got {tuple(X.shape)}")
+    return X.contiguous()
+
+
+def mode_gram(A: torch.Tensor) -> torch.Tensor:
+    """K7a: A f32[I,K] (or f64) -> G f64[I,I] = A A^T, f64 sums on the matrix cores; symmetric bit for bit, the same bits on every
+    call."""
+    a_f64 = _need_f32_or_f64(A, "A")
+    if A.dim() != 2 or not 1 <= A.shape[0] <= _lib.MODE_GRAM_I_MAX or A.shape[1] < 1:
+        raise ValueError(f"A: expected [I,K] with 1 <= I <= {_lib.MODE_GRAM_I_MAX} and K >= 1, got {tuple(A.shape)}")
+    A = A.contiguous()
+    I, K = A.shape
+    G = torch.empty((I, I), dtype=torch.float64, device=A.device)
+    ws = _k7_workspace(_lib.lib().nlml_mode_gram_workspace_bytes(I, K), A.device)
+    with _on_device_of(("A", A)) as stream:
+        _lib.check(_lib.lib().nlml_mode_gram_ex(A.data_ptr(), a_f64, I, K, G.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream),
+                   "nlml_mode_gram")
+    return G
+
+
+def pose_grams(X: torch.Tensor, which=(True, True, True)):
+    """K7b: X f32[I,ny,np,nr,M] (or f64) -> (Gy f64[ny,ny], Gp f64[np,np], Gr f64[nr,nr]), the Grams of the three pose-mode unfoldings in one
+    pass over X.  which: a False entry skips that Gram (None in its place)."""
+    X = _tensor5(X)
+    I, ny, np_, nr, M = X.shape
+    if ny * np_ * nr > _lib.POSE_GRAMS_MAX_CELLS:
+        raise ValueError(f"X: {ny} x {np_} x {nr} pose cells, at most {_lib.POSE_GRAMS_MAX_CELLS} fit the kernel's LDS slab")
+    which = tuple(bool(w) for w in which)
+    if len(which) != 3 or not any(which):
+        raise ValueError("which: three flags, at least one set")
+    G = [torch.empty((n, n), dtype=torch.float64, device=X.device) if w else None for n, w in zip((ny, np_, nr), which)]
+    ws = _k7_workspace(_lib.lib().nlml_pose_grams_workspace_bytes(I, ny, np_, nr, M), X.device)
+    with _on_device_of(("X", X)) as stream:
+        _lib.check(_lib.lib().nlml_pose_grams_ex(X.data_ptr(), int(X.dtype == torch.float64), I, ny, np_, nr, M,
+                                                 *[g.data_ptr() if g is not None else None for g in G],
+                                                 ws.data_ptr(), ws.numel() * 8, stream), "nlml_pose_grams")
+    return tuple(G)
+
+
+def project_identity(A: torch.Tensor, U: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
+    """K7c: A f32[I,K], U f64[I,R] (R <= 16) -> f32[R,K] = U^T A, f64 sums, one rounding; out_dtype=torch.float64: the sums
+    themselves."""
+    out_f64 = _out_f64(out_dtype)
+    _need_cuda(A, "A", torch.float32)
+    _need_cuda(U, "U", torch.float64)
+    if A.dim() != 2 or U.dim() != 2 or U.shape[0] != A.shape[0] or min(A.shape) < 1:
+        raise ValueError(f"A [I,K] and U [I,R] disagree: {tuple(A.shape)}, {tuple(U.shape)}")
+    if not _lib.TUCKER_RANK_MIN <= U.shape[1] <= _lib.TUCKER_RANK_MAX:
+        raise ValueError(f"U: R = {U.shape[1]} outside [{_lib.TUCKER_RANK_MIN}, {_lib.TUCKER_RANK_MAX}]")
+    A, U = A.contiguous(), U.contiguous()
+    out = torch.empty((U.shape[1], A.shape[1]), dtype=out_dtype, device=A.device)
+    with _on_device_of(("A", A), ("U", U)) as stream:
+        _lib.check(_lib.lib().nlml_project_identity_ex(A.data_ptr(), A.shape[0], A.shape[1], U.data_ptr(), U.shape[1], out.data_ptr(),
+                                                       out_f64, stream), "nlml_project_identity")
+    return out
+
+
+def project_pose(X: torch.Tensor, U_yaw=None, U_pitch=None, U_roll=None, out_dtype=torch.float32) -> torch.Tensor:
+    """K7d: X f32[I,ny,np,nr,M] (or f64) x_2 U_yaw^T x_3 U_pitch^T x_4 U_roll^T -> f32[I,ny',np',nr',M] (or f64, unrounded); each factor
+    f64[n,r] (r <= 3) or None, which leaves that mode as it is.  With all three None the result is a copy of X."""
+    X = _tensor5(X)
+    out_f64 = _out_f64(out_dtype)
+    shape = list(X.shape)
+    Us = []
+    for k, (U, name) in enumerate(((U_yaw, "U_yaw"), (U_pitch, "U_pitch"), (U_roll, "U_roll"))):
+        if U is not None:
+            _need_cuda(U, name, torch.float64)
+            if U.dim() != 2 or U.shape[0] != X.shape[1 + k] or not 1 <= U.shape[1] <= _lib.POSE_RANK_MAX:
+                raise ValueError(f"{name}: expected [{X.shape[1 + k]}, r] with 1 <= r <= {_lib.POSE_RANK_MAX}, got {tuple(U.shape)}")
+            U = U.contiguous()
+            shape[1 + k] = U.shape[1]
+        Us.append(U)
+    out = torch.empty(shape, dtype=out_dtype, device=X.device)
+    args = [a for U in Us for a in ((U.data_ptr(), U.shape[1]) if U is not None else (None, 0))]
+    with _on_device_of(("X", X), ("U_yaw", Us[0]), ("U_pitch", Us[1]), ("U_roll", Us[2])) as stream:
+        _lib.check(_lib.lib().nlml_project_pose_ex(X.data_ptr(), int(X.dtype == torch.float64), *X.shape, *args, out.data_ptr(), out_f64,
+                                                   stream), "nlml_project_pose")
+    return out
+
+
 # ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------
 _eval_ws: dict = {}
 
@@ -550,7 +651,8 @@ def _load_torch_ops():
     # the registered ops; *_small take an explicit workspace, landmarks_to_pose_valid is the video tick's forward (pose + face mask)
     for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
-                 "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks"):
+                 "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks", "mode_gram", "pose_grams", "project_identity",
+                 "project_pose"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
 

@@ -1,0 +1,238 @@
+"""Tucker decomposition of the rotation training tensor (TD_main.py:181), on the device.
+
+The reference's line is ``core, factors = tucker(tensor, rank=[5, 3, 3, 3, 1404])`` (tensorly): HOSVD initialisation followed by
+HOOI sweeps (De Lathauwer, De Moor, Vandewalle 2000).  This module restates that published algorithm over four device primitives
+(csrc/tucker_decompose.hip, K7a..K7d: ops.mode_gram, ops.pose_grams, ops.project_identity, ops.project_pose); nothing of tensorly is
+used.  Every unfolding's leading left singular vectors are taken as the leading eigenvectors of its f64 Gram matrix.
+
+Why the feature mode never appears: every shipped configuration has R_features = I_features = 1404, so the feature factor is square
+and orthogonal, and
+
+    W = core x_5 U_feat = X x_1 U_id^T x_2 U_yaw^T x_3 U_pitch^T x_4 U_roll^T
+
+needs no 1404 x 1404 eigenproblem.  ``tucker`` therefore returns W itself -- the tensor K3, K3g and the Powell kernel consume --
+and refuses any rank[4] other than the feature extent.  ``thin_core`` splits W into a (core, U_feat) pair for
+artefacts.core_to_W / nlml_mode5_product where one is wanted.
+
+Sign convention: each factor column is flipped so that its entry of largest magnitude (the lowest index on a tie) is positive, the
+convention all 14 columns of the shipped Factor_Matrices.npz follow.
+
+``decompose_to_npz`` writes Factor_Matrices.npz only.  Trained_data.npz also needs TD_Trainer's cosine fit of the pose factors,
+which is not part of this module yet (the next step of the TD_main port), so that file is NOT written here.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+IDENTITY_RANK_MAX = 16     # NLML_TUCKER_RANK_MAX: the TD kernels' (and K7c's) limit
+POSE_RANK_MAX = 3          # NLML_POSE_RANK_MAX: W is [R,3,3,3,M] for every consumer
+
+
+def fix_signs(U):
+    """Flip each column so that its entry of largest magnitude (lowest index on a tie) is positive.  U: numpy [n,R]."""
+    U = np.array(U, dtype=np.float64, copy=True)
+    for r in range(U.shape[1]):
+        if U[np.argmax(np.abs(U[:, r])), r] < 0:
+            U[:, r] = -U[:, r]
+    return U
+
+
+def _leading_numpy(G, R):
+    w, V = np.linalg.eigh(np.asarray(G, dtype=np.float64))
+    return fix_signs(V[:, ::-1][:, :R])
+
+
+class _NumpyBackend:
+    """The four primitives in numpy f64 on the host: the CPU tests' path and the timing baseline."""
+
+    def __init__(self, tensor):
+        if hasattr(tensor, "detach"):
+            tensor = tensor.detach().cpu().numpy()
+        self.X = np.ascontiguousarray(tensor, dtype=np.float64)
+
+    def mode_gram(self, T):
+        A = T.reshape(T.shape[0], -1)
+        return A @ A.T
+
+    def pose_gram(self, T, mode):
+        A = np.moveaxis(T, mode, 0).reshape(T.shape[mode], -1)
+        return A @ A.T
+
+    def pose_grams(self, T):
+        return [self.pose_gram(T, mode) for mode in (1, 2, 3)]
+
+    def project_identity(self, T, U):
+        return np.tensordot(U.T, T, axes=(1, 0))
+
+    def project_pose(self, T, Uy, Up, Ur):
+        for mode, U in ((1, Uy), (2, Up), (3, Ur)):
+            if U is not None:
+                T = np.moveaxis(np.tensordot(U.T, T, axes=(1, mode)), 0, mode)
+        return T
+
+    def leading(self, G, R):
+        return _leading_numpy(G, R)
+
+    def trace(self, G):
+        return float(np.trace(G))
+
+    def sumsq(self, T):
+        return float(np.sum(np.square(T, dtype=np.float64)))
+
+    def out_tensor(self, T):
+        return np.ascontiguousarray(T, dtype=np.float32)
+
+    def out_factor(self, U):
+        return U
+
+
+class _DeviceBackend:
+    """The four primitives as HIP kernels; factors stay on the device as f64, and so does every projected tensor between two steps
+    (a factor computed from an f32-rounded projection would sit 2^-24 from the exact one, far outside the f64 Grams' own error);
+    only W is rounded to f32, once.  The eigen-solve of a small f64 Gram is plumbing: torch.linalg.eigh on the device, numpy on
+    the host where that solver is unavailable."""
+
+    def __init__(self, tensor):
+        import torch
+
+        from . import ops
+        self.torch, self.ops = torch, ops
+        if not torch.is_tensor(tensor):
+            tensor = torch.as_tensor(np.ascontiguousarray(tensor, dtype=np.float32))
+        if not tensor.is_cuda:
+            tensor = tensor.to("cuda")
+        if tensor.dtype != torch.float32:
+            raise TypeError(f"tensor: expected float32, got {tensor.dtype}")
+        self.X = tensor.contiguous()
+
+    def mode_gram(self, T):
+        return self.ops.mode_gram(T.reshape(T.shape[0], -1))
+
+    def pose_gram(self, T, mode):
+        return self.ops.pose_grams(T, which=[m == mode for m in (1, 2, 3)])[mode - 1]
+
+    def pose_grams(self, T):
+        return self.ops.pose_grams(T)             # one pass over the tensor for all three
+
+    def project_identity(self, T, U):
+        return self.ops.project_identity(T.reshape(T.shape[0], -1), U, out_dtype=self.torch.float64).reshape(
+            (U.shape[1],) + tuple(T.shape[1:]))
+
+    def project_pose(self, T, Uy, Up, Ur):
+        return self.ops.project_pose(T, Uy, Up, Ur, out_dtype=self.torch.float64)
+
+    def leading(self, G, R):
+        torch = self.torch
+        try:
+            w, V = torch.linalg.eigh(G)
+            V = V.flip(1)[:, :R]
+            rows = V.abs().argmax(dim=0)           # the first index of the maximum, as numpy's argmax
+            sign = torch.where(V[rows, torch.arange(R, device=V.device)] < 0, -1.0, 1.0).to(V.dtype)
+            return (V * sign).contiguous()
+        except RuntimeError:
+            return torch.from_numpy(_leading_numpy(G.cpu().numpy(), R)).to(G.device)
+
+    def trace(self, G):
+        return float(self.torch.trace(G))
+
+    def sumsq(self, T):
+        return float(T.double().square().sum())
+
+    def out_tensor(self, T):
+        return T.to(self.torch.float32)
+
+    def out_factor(self, U):
+        return U
+
+
+def _check_rank(shape, rank):
+    if len(shape) != 5:
+        raise ValueError(f"tensor: expected [I, ny, np, nr, M], got {tuple(shape)}")
+    rank = [int(r) for r in rank]
+    if len(rank) != 5:
+        raise ValueError(f"rank: expected [R_identity, R_yaw, R_pitch, R_roll, R_features], got {rank}")
+    if rank[4] != shape[4]:
+        raise ValueError(
+            f"rank[4] = {rank[4]} but the tensor has {shape[4]} features: only R_features = I_features is supported.  With a square "
+            "(orthogonal) feature factor W = core x_5 U_feat equals the tensor projected on the four other factors, so no feature "
+            "eigenproblem is solved; a smaller R_features would need that 1404 x 1404 problem and is out of scope")
+    if not 1 <= rank[0] <= min(IDENTITY_RANK_MAX, shape[0]):
+        raise ValueError(f"rank[0] = {rank[0]}: the identity rank must be in 1..{min(IDENTITY_RANK_MAX, shape[0])} "
+                         f"({IDENTITY_RANK_MAX} is the limit of the TD kernels, {shape[0]} the number of identities)")
+    for k, name in ((1, "yaw"), (2, "pitch"), (3, "roll")):
+        if not 1 <= rank[k] <= min(POSE_RANK_MAX, shape[k]):
+            raise ValueError(f"rank[{k}] = {rank[k]}: the {name} rank must be in 1..{min(POSE_RANK_MAX, shape[k])}")
+    return rank
+
+
+def tucker(tensor, rank, n_iter_max=100, tol=1e-4, backend="device", return_errors=False):
+    """HOSVD + HOOI of tensor f32[I,ny,np,nr,M] -> (W f32[R_id,r_yaw,r_pitch,r_roll,M], [U_id, U_yaw, U_pitch, U_roll]).
+
+    rank          [R_identity, R_yaw, R_pitch, R_roll, R_features]; R_features must equal M (see the module docstring),
+                  R_identity <= 16, the pose ranks <= 3
+    n_iter_max    HOOI sweeps at most (0: the HOSVD factors and their projection)
+    tol           stop when the relative reconstruction error sqrt(|X|^2 - |W|^2) / |X| changes by less than tol between two sweeps
+    backend       "device": HIP kernels, a GPU tensor in, GPU tensors out (factors f64);  "numpy": the same driver over numpy f64
+                  versions of the four primitives (host arrays in and out)
+    return_errors also return the list of the sweeps' relative reconstruction errors
+    """
+    if backend not in ("device", "numpy"):
+        raise ValueError(f"backend: expected 'device' or 'numpy', got {backend!r}")
+    rank = _check_rank(tuple(tensor.shape), rank)
+    be = _DeviceBackend(tensor) if backend == "device" else _NumpyBackend(tensor)
+    X = be.X
+
+    # HOSVD: the leading eigenvectors of each mode's Gram of the full tensor
+    G_id = be.mode_gram(X)
+    norm2 = be.trace(G_id)
+    U = [be.leading(G_id, rank[0])] + [be.leading(G, rank[mode]) for mode, G in zip((1, 2, 3), be.pose_grams(X))]
+
+    def project(U):
+        Z = be.project_identity(X, U[0])
+        return Z, be.project_pose(Z, U[1], U[2], U[3])
+
+    errors = []
+    W = None
+    for _ in range(int(n_iter_max)):
+        # mode 1: the pose modes contracted first (27 M columns), then its Gram
+        U[0] = be.leading(be.mode_gram(be.project_pose(X, U[1], U[2], U[3])), rank[0])
+        Z = be.project_identity(X, U[0])
+        for mode in (1, 2, 3):
+            others = [None if m == mode else U[m] for m in (1, 2, 3)]
+            U[mode] = be.leading(be.pose_gram(be.project_pose(Z, *others), mode), rank[mode])
+        W = be.project_pose(Z, U[1], U[2], U[3])
+        errors.append(float(np.sqrt(max(norm2 - be.sumsq(W), 0.0) / norm2)) if norm2 > 0 else 0.0)
+        if len(errors) >= 2 and abs(errors[-2] - errors[-1]) < tol:
+            break
+    if W is None:
+        W = project(U)[1]
+    out = (be.out_tensor(W), [be.out_factor(u) for u in U])
+    return out + (errors,) if return_errors else out
+
+
+def thin_core(W):
+    """W f32[R,a,b,c,M] -> (core f32[R,a,b,c,Q], U_feat f32[M,Q]), Q = min(R a b c, M): the thin SVD of W's mode-5 unfolding in torch
+    f64, so that W = core x_5 U_feat (artefacts.core_to_W, nlml_mode5_product) with an orthonormal U_feat.  For the shipped ranks
+    Q = 135."""
+    import torch
+
+    Wt = W if torch.is_tensor(W) else torch.as_tensor(np.asarray(W))
+    lead, M = tuple(Wt.shape[:-1]), Wt.shape[-1]
+    A, S, Bh = torch.linalg.svd(Wt.reshape(-1, M).double(), full_matrices=False)   # Wm = A diag(S) Bh
+    core = (A * S).to(torch.float32).reshape(lead + (S.shape[0],))
+    return core.contiguous(), Bh.T.to(torch.float32).contiguous()
+
+
+def decompose_to_npz(tensor, config, out_dir, backend="device", **kwargs):
+    """Decompose with the ranks of config["tensor_decom_ranks"] (configs/config_TD_main.yaml) and write <out_dir>/Factor_Matrices.npz
+    with the reference's keys and dtypes (TD_main.py:261): f32 U_yaw, U_pitch, U_roll, U_id.  Returns (W, factors) as ``tucker``.
+    Trained_data.npz is not written: it also holds TD_Trainer's cosine fit, which this package does not compute yet."""
+    r = config["tensor_decom_ranks"]
+    rank = [r["R_identity"], r["R_yaw"], r["R_pitch"], r["R_roll"], r["R_features"]]
+    W, factors = tucker(tensor, rank, backend=backend, **kwargs)
+    host = [np.asarray(u.detach().cpu().numpy() if hasattr(u, "detach") else u, dtype=np.float32) for u in factors]
+    os.makedirs(out_dir, exist_ok=True)
+    np.savez(os.path.join(out_dir, "Factor_Matrices.npz"), U_yaw=host[1], U_pitch=host[2], U_roll=host[3], U_id=host[0])
+    return W, factors
