@@ -322,6 +322,25 @@ int nlml_landmarks_to_pose_ws(const float* raw, int64_t B, int normalize,
                               const void* blob, size_t blob_bytes, float* out, float* latent, uint8_t* valid,
                               void* workspace, size_t ws_bytes, void* stream);
 
+/* K2 ARGUMENT CHECKS.  Every K2 forward entry point (the ten above and nlml_encoder_heads_fwd_debug) checks its arguments in this order
+ * and returns at the first that fails, before any launch; a host may rely on which of two errors it gets:
+ *   1. nlml_landmarks_to_pose_ws only: B > 0 and raw NULL -> NLML_E_BADARG (every other form reports a missing input at 4)
+ *   2. the blob: B < 0 or F <= 0 -> NLML_E_BADARG;  B > 0 and blob or out NULL -> NLML_E_BADARG;  blob not 16-byte aligned ->
+ *      NLML_E_BADARG;  blob_bytes not the size of a blob of width F in any mode -> NLML_E_BADBLOB  (the last two at B == 0 as well)
+ *   3. the form's mode: _small takes NLML_MODE_F16X2 and NLML_MODE_F16X2S blobs, _streamed and _quad NLML_MODE_F16X2S, _debug
+ *      NLML_MODE_F32; another -> NLML_E_BADARG (at B == 0 as well)
+ *   4. B > 0 and the input missing (raw NULL; x NULL or ldx < F) -> NLML_E_BADARG
+ *   5. B == 0 -> 0: no launch, and neither the input nor the workspace is looked at (a NULL workspace is fine)
+ *   6. the workspace of the path that runs -- the form's own; for _ws the one its rule above picks, which is the four-tile path only
+ *      where the workspace holds the quad part, unless NLML_K2_QUAD_MIN is set: NULL or fewer bytes than that path needs ->
+ *      NLML_E_BADARG; then not 16-byte aligned -> NLML_E_BADARG.  The fused kernels need none.
+ *   7. the streamed and the four-tile path: rows that cannot be read 16 bytes at a time (x or raw 16-byte aligned, F % 4 == 0,
+ *      ldx % 4 == 0) -> NLML_E_BADARG; _ws never picks these paths for such rows.  _debug with pre_tanh or stamps given: the same
+ *      condition -> NLML_E_BADARG.  The other paths read rows of any 4-byte alignment.
+ * nlml_last_error() names the path ("small-batch path", "streamed-tail path", "quad path", "debug build") or the function family and
+ * the condition.  (tests/test_k2_abi_contract_host.py)
+ */
+
 /* ------------------------------------------------------------------------------------------
  * K3  Tucker objective, batched over face-evaluations.
  * Replaces objective() (TD_Tester.py:31-58): f = a*cos(b*w+c)+d (:25-28) in f64 rounded to

@@ -1,8 +1,11 @@
-// abi.cpp -- the extern "C" surface declared in include/nlml_hpe.h: argument checks, then the
-// launchers in the .hip files.  No allocation, no synchronisation, no global mutable state beyond values read once and kept (the
-// NLML_K2_* environment variables, a device's compute-unit count).
+// abi.cpp -- the extern "C" surface declared in include/nlml_hpe.h: ALL the argument checks, in the order that header states, then the
+// launchers in the .hip files, which refuse nothing.  A refusal is fail(code, text) or, where the text names its caller, refuse(code,
+// who, what); every alignment test is aligned().  K2: k2_forward checks a call once, hands it on as one K2Call (abi_internal.h) and
+// chains the strict-fast mode's re-evaluation launch behind whichever form ran.  No allocation, no synchronisation, no global mutable
+// state beyond values read once and kept (the NLML_K2_* environment variables, a device's compute-unit count).
 #include <hip/hip_runtime_api.h>
 
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +37,19 @@ int64_t k2_quad_faces(int64_t B, int cus) {
 
 using namespace nlml;
 
+// The one place a refusal's text is put together: "<who>: <what>", `what` a printf format for the values behind it (a literal '%' is "%%")
+__attribute__((format(printf, 3, 4))) static int refuse(int code, const char* who, const char* what, ...) {
+  char msg[sizeof g_err];
+  const int n = std::snprintf(msg, sizeof msg, "%s: ", who);
+  va_list ap;
+  va_start(ap, what);
+  if (n >= 0 && (size_t)n < sizeof msg) std::vsnprintf(msg + n, sizeof msg - n, what, ap);
+  va_end(ap);
+  return fail(code, msg);
+}
+// p may be read or written `bytes` (a power of two) at a time; NULL is aligned
+static bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 static bool known_mode(int mode) { return mode == NLML_MODE_F32 || mode == NLML_MODE_BF16 || mode == NLML_MODE_F16X2 || mode == NLML_MODE_F16X2S; }
 static bool split_f16(int mode) { return mode == NLML_MODE_F16X2 || mode == NLML_MODE_F16X2S; }
 
@@ -44,16 +60,14 @@ const char* nlml_last_error(void) { return g_err; }
 
 int nlml_normalize_ipd(const float* raw, int64_t B, int normalize, float* out, uint8_t* valid, void* stream) {
   if (B < 0 || (B > 0 && (!raw || !out))) return fail(NLML_E_BADARG, "normalize_ipd: null buffer or negative B");
-  if ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(out)) & 15)
-    return fail(NLML_E_BADARG, "normalize_ipd: raw/out must be 16-byte aligned");
+  if (!aligned(raw, 16) || !aligned(out, 16)) return fail(NLML_E_BADARG, "normalize_ipd: raw/out must be 16-byte aligned");
   return launch_normalize_ipd(raw, B, normalize, out, valid, stream);
 }
 
 int nlml_normalize_centroid(const float* raw, int64_t B, float* out, uint8_t* valid, double* stats, void* stream) {
   if (B < 0 || (B > 0 && (!raw || !out))) return fail(NLML_E_BADARG, "normalize_centroid: null buffer or negative B");
-  if ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(out)) & 15)
-    return fail(NLML_E_BADARG, "normalize_centroid: raw/out must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(stats) & 7) return fail(NLML_E_BADARG, "normalize_centroid: stats must be 8-byte aligned");
+  if (!aligned(raw, 16) || !aligned(out, 16)) return fail(NLML_E_BADARG, "normalize_centroid: raw/out must be 16-byte aligned");
+  if (!aligned(stats, 8)) return fail(NLML_E_BADARG, "normalize_centroid: stats must be 8-byte aligned");
   return launch_normalize_centroid(raw, B, out, valid, stats, stream);
 }
 
@@ -71,22 +85,17 @@ int nlml_normalize_centroid_host(const float* h_raw, int64_t B, float* h_out, ui
 // of rows to write (0: nothing to do), or the error.
 static int check_rotation_grid(const char* who, bool have_buffers, int64_t I, int ny, int np, int nr, int order, int zy, int zp, int zr,
                                int64_t* rows) {
-  char msg[128];
   const bool empty = I == 0 || ny == 0 || np == 0 || nr == 0;
-  auto refuse = [&](const char* what) {
-    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return fail(NLML_E_BADARG, msg);
-  };
-  if (!empty && !have_buffers) return refuse("null buffer");
-  if (I < 0 || ny < 0 || np < 0 || nr < 0) return refuse("negative extent");
-  if (order != NLML_ROT_INTRINSIC && order != NLML_ROT_EXTRINSIC) return refuse("unknown order");
-  if (zy < -1 || zy >= ny || zp < -1 || zp >= np || zr < -1 || zr >= nr) return refuse("zero index outside -1..n-1");
+  if (!empty && !have_buffers) return refuse(NLML_E_BADARG, who, "null buffer");
+  if (I < 0 || ny < 0 || np < 0 || nr < 0) return refuse(NLML_E_BADARG, who, "negative extent");
+  if (order != NLML_ROT_INTRINSIC && order != NLML_ROT_EXTRINSIC) return refuse(NLML_E_BADARG, who, "unknown order");
+  if (zy < -1 || zy >= ny || zp < -1 || zp >= np || zr < -1 || zr >= nr) return refuse(NLML_E_BADARG, who, "zero index outside -1..n-1");
   *rows = 0;
   if (empty) return 0;
   int64_t n = 0;
   if (__builtin_mul_overflow(I, (int64_t)ny, &n) || __builtin_mul_overflow(n, (int64_t)np, &n) || __builtin_mul_overflow(n, (int64_t)nr, &n) ||
       n > INT64_MAX / (NLML_F_REFERENCE * 8))
-    return refuse("tensor too large for 64-bit byte offsets");
+    return refuse(NLML_E_BADARG, who, "tensor too large for 64-bit byte offsets");
   *rows = n;
   return 0;
 }
@@ -99,10 +108,8 @@ int nlml_compose_rotation_tensor(const float* base, int64_t I, const double* rot
                                          zero_yaw, zero_pitch, zero_roll, &rows))
     return rc;
   if (rows == 0) return 0;
-  if ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(out)) & 15)
-    return fail(NLML_E_BADARG, "compose_rotation_tensor: base/out must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(rot_yaw) | reinterpret_cast<uintptr_t>(rot_pitch) | reinterpret_cast<uintptr_t>(rot_roll) |
-       reinterpret_cast<uintptr_t>(out64)) & 7)
+  if (!aligned(base, 16) || !aligned(out, 16)) return fail(NLML_E_BADARG, "compose_rotation_tensor: base/out must be 16-byte aligned");
+  if (!aligned(rot_yaw, 8) || !aligned(rot_pitch, 8) || !aligned(rot_roll, 8) || !aligned(out64, 8))
     return fail(NLML_E_BADARG, "compose_rotation_tensor: the matrices and out64 must be 8-byte aligned");
   return launch_compose_rotation_tensor(base, rows, rot_yaw, ny, rot_pitch, np, rot_roll, nr, order, zero_yaw, zero_pitch, zero_roll, out,
                                         out64, stream);
@@ -124,10 +131,8 @@ int nlml_rotate_landmarks(const float* lm, const double* rot, float* out, double
   if (B < 0) return fail(NLML_E_BADARG, "rotate_landmarks: negative extent");
   if (B == 0) return 0;
   if (B > INT64_MAX / (NLML_F_REFERENCE * 8)) return fail(NLML_E_BADARG, "rotate_landmarks: too many faces for 64-bit byte offsets");
-  if ((reinterpret_cast<uintptr_t>(lm) | reinterpret_cast<uintptr_t>(out)) & 15)
-    return fail(NLML_E_BADARG, "rotate_landmarks: lm/out must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(rot) | reinterpret_cast<uintptr_t>(out64)) & 7)
-    return fail(NLML_E_BADARG, "rotate_landmarks: rot/out64 must be 8-byte aligned");
+  if (!aligned(lm, 16) || !aligned(out, 16)) return fail(NLML_E_BADARG, "rotate_landmarks: lm/out must be 16-byte aligned");
+  if (!aligned(rot, 8) || !aligned(out64, 8)) return fail(NLML_E_BADARG, "rotate_landmarks: rot/out64 must be 8-byte aligned");
   return launch_rotate_landmarks(lm, rot, out, out64, B, stream);
 }
 
@@ -158,7 +163,7 @@ int nlml_encoder_heads_pack(int F, int mode, const float* const h_enc_w[6], cons
 static int check_blob_args(int64_t B, int F, const void* blob, size_t blob_bytes, const float* out, int* mode) {
   if (B < 0 || F <= 0) return fail(NLML_E_BADARG, "encoder_heads: negative B or bad F");
   if (B > 0 && (!blob || !out)) return fail(NLML_E_BADARG, "encoder_heads: null buffer");
-  if (reinterpret_cast<uintptr_t>(blob) & 15) return fail(NLML_E_BADARG, "encoder_heads: blob must be 16-byte aligned");
+  if (!aligned(blob, 16)) return fail(NLML_E_BADARG, "encoder_heads: blob must be 16-byte aligned");
   if (blob_bytes == blob_bytes_for(F, NLML_MODE_F32)) *mode = NLML_MODE_F32;
   else if (blob_bytes == blob_bytes_for(F, NLML_MODE_BF16)) *mode = NLML_MODE_BF16;
   else if (blob_bytes == blob_bytes_for(F, NLML_MODE_F16X2)) *mode = NLML_MODE_F16X2;
@@ -229,8 +234,25 @@ static int64_t auto_quad_part(bool strict_fast, const K2Input& in, int64_t B) { 
 // kernel over the whole batch; AUTO = the fastest of them for the batch size and the blob's mode, through a caller-provided workspace.
 enum K2Form { K2_FUSED, K2_SMALL, K2_STREAMED, K2_QUAD, K2_AUTO };
 
+// What a path other than the fused kernels needs of a call (B > 0), the last of the "K2 argument checks" (include/nlml_hpe.h): the
+// workspace's presence and size, its alignment, and for the streamed and the quad path rows readable 16 bytes at a time.
+static int check_k2_path(K2Form form, const K2Call& c, int64_t quad_faces) {
+  if (form == K2_FUSED) return 0;
+  const char* who = form == K2_SMALL ? "small-batch path" : form == K2_STREAMED ? "streamed-tail path" : "quad path";
+  // (k2_forward's own arithmetic, k2_quad_faces or the whole batch: held to the launcher's contract here, where every refusal is)
+  if (form == K2_QUAD && (quad_faces < 0 || quad_faces > c.B || (quad_faces < c.B && quad_faces % (4 * TILE_FACES))))
+    return refuse(NLML_E_BADARG, who, "the quad part is whole workgroups of 256 faces, or the whole batch");
+  if (form == K2_QUAD && quad_faces == 0) return 0;   // (no quad part: all of it through the fused kernel, which needs no workspace)
+  const size_t need = form == K2_SMALL ? small_workspace_bytes(c.B, c.F) : form == K2_STREAMED ? tailws_workspace_bytes(c.B, c.F)
+                                                                                               : quad_workspace_bytes(quad_faces);
+  if (!c.ws || c.ws_bytes < need) return refuse(NLML_E_BADARG, who, "workspace too small");
+  if (!aligned(c.ws, 16)) return refuse(NLML_E_BADARG, who, "workspace must be 16-byte aligned");
+  if (form != K2_SMALL && !c.in.vec4) return refuse(NLML_E_BADARG, who, "x must be 16-byte aligned with F and ldx multiples of 4");
+  return 0;
+}
+
 // landmarks: the input is raw [B,468,3] (x, ldx unused), else the feature rows x / ldx (raw null).  workspace / ws_bytes are read by the
-// forms that need one.
+// forms that need one.  The checks and their order: include/nlml_hpe.h, "K2 argument checks".
 static int k2_forward(K2Form form, bool landmarks, const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
                       const void* blob, size_t blob_bytes, float* out, float* latent, uint8_t* valid, void* workspace, size_t ws_bytes,
                       void* stream) {
@@ -245,27 +267,30 @@ static int k2_forward(K2Form form, bool landmarks, const float* x, int64_t ldx, 
   if (form == K2_STREAMED && mode != NLML_MODE_F16X2S) return fail(NLML_E_BADARG, "streamed-tail path: NLML_MODE_F16X2S blob only");
   if (form == K2_QUAD && mode != NLML_MODE_F16X2S) return fail(NLML_E_BADARG, "quad path: NLML_MODE_F16X2S blob only");
   if (no_input) return fail(NLML_E_BADARG, no_input);
+  if (B == 0) return 0;
+  const K2Call c{k2_input(x, ldx, raw, normalize, F), B, F, blob, out, latent, valid, workspace, ws_bytes};
   const int split = mode == NLML_MODE_F16X2S;
   int64_t quad_faces = B;   // K2_QUAD: the whole batch
   if (form == K2_AUTO) {
-    const K2Input in = k2_input(x, ldx, raw, normalize, F);
-    quad_faces = auto_quad_part(split, in, B);
+    quad_faces = auto_quad_part(split, c.in, B);
     // whole rounds only if the workspace takes them -- never a failure the fused kernel would not have; asked for by the environment, always
-    const bool fits = workspace && ws_bytes >= quad_workspace_bytes(quad_faces) && !(reinterpret_cast<uintptr_t>(workspace) & 15);
+    const bool fits = workspace && ws_bytes >= quad_workspace_bytes(quad_faces) && aligned(workspace, 16);
     if (quad_faces > 0 && (fits || quad_min() != kQuadMinUnset)) form = K2_QUAD;
     else if (split_f16(mode) && B <= kSmallMax) form = K2_SMALL;
-    else if (k2_wide(split, in) && streamed_min() >= 0 && B >= streamed_min()) form = K2_STREAMED;
+    else if (k2_wide(split, c.in) && streamed_min() >= 0 && B >= streamed_min()) form = K2_STREAMED;
     else form = K2_FUSED;
   }
-  if (form == K2_SMALL)
-    return launch_encoder_heads_f16x2_small(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, split, stream);
-  if (form == K2_STREAMED)
-    return launch_encoder_heads_f16x2_tailws(x, ldx, raw, normalize, B, F, blob, out, latent, valid, workspace, ws_bytes, stream);
-  if (form == K2_QUAD)
-    return launch_encoder_heads_f16x2_w8_mixed(x, ldx, raw, normalize, B, F, blob, out, latent, valid, quad_faces, workspace, ws_bytes, stream);
-  if (mode == NLML_MODE_BF16) return launch_encoder_heads_bf16(x, ldx, raw, normalize, B, F, blob, out, latent, valid, stream);
-  if (split_f16(mode)) return launch_encoder_heads_f16x2(x, ldx, raw, normalize, B, F, blob, out, latent, valid, split, stream);
-  return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, blob, out, latent, valid, nullptr, nullptr, stream);
+  if (int rc = check_k2_path(form, c, quad_faces)) return rc;
+  int rc;
+  if (form == K2_SMALL) rc = launch_encoder_heads_f16x2_small(c, split, stream);
+  else if (form == K2_STREAMED) rc = launch_encoder_heads_f16x2_tailws(c, stream);
+  else if (form == K2_QUAD) rc = launch_encoder_heads_f16x2_w8_mixed(c, quad_faces, stream);
+  else if (mode == NLML_MODE_BF16) rc = launch_encoder_heads_bf16(c, stream);
+  else if (mode == NLML_MODE_F16X2) rc = launch_encoder_heads_f16x2(c, stream);
+  else if (split) rc = launch_encoder_heads_f16x2_w8(c, stream);
+  else rc = launch_encoder_heads_f32(c, nullptr, nullptr, stream);
+  // a strict-fast forward is its split-f16 launch(es) followed by the f32 re-evaluation launch over all B, whichever form ran
+  return rc || !split ? rc : launch_strict_reeval(c, stream);
 }
 
 int nlml_encoder_heads_fwd(const float* x, int64_t ldx, int64_t B, int F, const void* blob, size_t blob_bytes,
@@ -279,7 +304,10 @@ int nlml_encoder_heads_fwd_debug(const float* x, int64_t ldx, int64_t B, int F, 
   if (int rc = check_blob_args(B, F, blob, blob_bytes, out, &mode)) return rc;
   if (mode != NLML_MODE_F32) return fail(NLML_E_BADARG, "debug build: f32 blob only");
   if (B > 0 && (!x || ldx < F)) return fail(NLML_E_BADARG, "encoder_heads: null x or ldx < F");
-  return launch_encoder_heads_f32(x, ldx, nullptr, 0, B, F, blob, out, latent, nullptr, pre_tanh, stamps, stream);
+  if (B == 0) return 0;
+  const K2Call c{k2_input(x, ldx, nullptr, 0, F), B, F, blob, out, latent, nullptr, nullptr, 0};
+  if ((pre_tanh || stamps) && !c.in.vec4) return fail(NLML_E_BADARG, "debug build: features input, F % 4 == 0 only");
+  return launch_encoder_heads_f32(c, pre_tanh, stamps, stream);
 }
 
 int nlml_landmarks_to_pose(const float* raw, int64_t B, int normalize, const void* blob, size_t blob_bytes,
@@ -332,11 +360,7 @@ static int k2_quad_part(const char* who, const float* rows, int64_t ld, int64_t 
                         size_t* ws_bytes) {
   if (quad_faces) *quad_faces = 0;
   if (ws_bytes) *ws_bytes = 0;
-  if (B < 0 || F <= 0 || !quad_faces) {
-    char msg[96];
-    std::snprintf(msg, sizeof msg, "%s: negative B, F <= 0 or null quad_faces", who);
-    return fail(NLML_E_BADARG, msg);
-  }
+  if (B < 0 || F <= 0 || !quad_faces) return refuse(NLML_E_BADARG, who, "negative B, F <= 0 or null quad_faces");
   *quad_faces = auto_quad_part(blob_bytes == blob_bytes_for(F, NLML_MODE_F16X2S), k2_input(rows, ld, nullptr, 0, F), B);
   if (ws_bytes) *ws_bytes = quad_workspace_bytes(*quad_faces);
   return 0;
@@ -399,12 +423,6 @@ int nlml_mode5_product(const float* core, const float* U_feat, int Q, int R5, in
 }
 
 // ---- K7: the Tucker decomposition's primitives (tucker_decompose.hip) ----------------------------------
-static int k7_refuse(const char* who, const char* what) {
-  char msg[160];
-  std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return fail(NLML_E_BADARG, msg);
-}
-static bool k7_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 // I x K within 64-bit byte offsets of f64 partials (I <= 4096 keeps every product below 2^63)
 static bool k7_matrix_ok(int64_t I, int64_t K) { return I >= 1 && I <= NLML_GRAM_I_MAX && K >= 1 && K <= INT64_MAX / (8 * NLML_GRAM_I_MAX); }
 static bool k7_bins_ok(int ny, int np, int nr) {
@@ -424,12 +442,12 @@ int nlml_mode_gram(const float* A, int64_t I, int64_t K, double* G, void* worksp
 
 int nlml_mode_gram_ex(const void* A, int a_f64, int64_t I, int64_t K, double* G, void* workspace, size_t workspace_bytes, void* stream) {
   const char* who = "mode_gram";
-  if (!A || !G || !workspace) return k7_refuse(who, "null buffer (A, G, workspace)");
-  if (I < 1 || I > NLML_GRAM_I_MAX) return k7_refuse(who, "I outside 1..NLML_GRAM_I_MAX (4096)");
-  if (!k7_matrix_ok(I, K)) return k7_refuse(who, "K < 1 or too large for 64-bit byte offsets");
-  if (!k7_aligned(A, a_f64 ? 8 : 4) || !k7_aligned(G, 8) || !k7_aligned(workspace, 8))
-    return k7_refuse(who, "A must be aligned to its element (4 bytes f32, 8 bytes f64), G and the workspace 8-byte aligned");
-  if (workspace_bytes < mode_gram_workspace_bytes(I, K)) return k7_refuse(who, "workspace too small (nlml_mode_gram_workspace_bytes)");
+  if (!A || !G || !workspace) return refuse(NLML_E_BADARG, who, "null buffer (A, G, workspace)");
+  if (I < 1 || I > NLML_GRAM_I_MAX) return refuse(NLML_E_BADARG, who, "I outside 1..NLML_GRAM_I_MAX (4096)");
+  if (!k7_matrix_ok(I, K)) return refuse(NLML_E_BADARG, who, "K < 1 or too large for 64-bit byte offsets");
+  if (!aligned(A, a_f64 ? 8 : 4) || !aligned(G, 8) || !aligned(workspace, 8))
+    return refuse(NLML_E_BADARG, who, "A must be aligned to its element (4 bytes f32, 8 bytes f64), G and the workspace 8-byte aligned");
+  if (workspace_bytes < mode_gram_workspace_bytes(I, K)) return refuse(NLML_E_BADARG, who, "workspace too small (nlml_mode_gram_workspace_bytes)");
   return launch_mode_gram(A, a_f64 != 0, I, K, G, workspace, stream);
 }
 
@@ -448,14 +466,14 @@ int nlml_pose_grams(const float* X, int64_t I, int ny, int np, int nr, int64_t M
 int nlml_pose_grams_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, double* Gy, double* Gp, double* Gr,
                        void* workspace, size_t workspace_bytes, void* stream) {
   const char* who = "pose_grams";
-  if (!X || !workspace || (!Gy && !Gp && !Gr)) return k7_refuse(who, "null buffer (X, workspace, and at least one of Gy, Gp, Gr)");
-  if (I < 1 || M < 1) return k7_refuse(who, "I < 1 or M < 1");
-  if (!k7_bins_ok(ny, np, nr)) return k7_refuse(who, "ny, np, nr outside 1..NLML_POSE_BINS_MAX (32)");
-  if (ny * np * nr > NLML_POSE_GRAMS_MAX_CELLS) return k7_refuse(who, "ny np nr beyond NLML_POSE_GRAMS_MAX_CELLS (768): the slab does not fit in LDS");
-  if (!k7_tensor_ok(I, ny, np, nr, M)) return k7_refuse(who, "tensor too large for 64-bit byte offsets");
-  if (!k7_aligned(X, x_f64 ? 8 : 4) || !k7_aligned(Gy, 8) || !k7_aligned(Gp, 8) || !k7_aligned(Gr, 8) || !k7_aligned(workspace, 8))
-    return k7_refuse(who, "X must be aligned to its element (4 bytes f32, 8 bytes f64), the Grams and the workspace 8-byte aligned");
-  if (workspace_bytes < pose_grams_workspace_bytes(I, ny, np, nr, M)) return k7_refuse(who, "workspace too small (nlml_pose_grams_workspace_bytes)");
+  if (!X || !workspace || (!Gy && !Gp && !Gr)) return refuse(NLML_E_BADARG, who, "null buffer (X, workspace, and at least one of Gy, Gp, Gr)");
+  if (I < 1 || M < 1) return refuse(NLML_E_BADARG, who, "I < 1 or M < 1");
+  if (!k7_bins_ok(ny, np, nr)) return refuse(NLML_E_BADARG, who, "ny, np, nr outside 1..NLML_POSE_BINS_MAX (32)");
+  if (ny * np * nr > NLML_POSE_GRAMS_MAX_CELLS) return refuse(NLML_E_BADARG, who, "ny np nr beyond NLML_POSE_GRAMS_MAX_CELLS (768): the slab does not fit in LDS");
+  if (!k7_tensor_ok(I, ny, np, nr, M)) return refuse(NLML_E_BADARG, who, "tensor too large for 64-bit byte offsets");
+  if (!aligned(X, x_f64 ? 8 : 4) || !aligned(Gy, 8) || !aligned(Gp, 8) || !aligned(Gr, 8) || !aligned(workspace, 8))
+    return refuse(NLML_E_BADARG, who, "X must be aligned to its element (4 bytes f32, 8 bytes f64), the Grams and the workspace 8-byte aligned");
+  if (workspace_bytes < pose_grams_workspace_bytes(I, ny, np, nr, M)) return refuse(NLML_E_BADARG, who, "workspace too small (nlml_pose_grams_workspace_bytes)");
   return launch_pose_grams(X, x_f64 != 0, I, ny, np, nr, M, Gy, Gp, Gr, workspace, stream);
 }
 
@@ -465,13 +483,13 @@ int nlml_project_identity(const float* A, int64_t I, int64_t K, const double* U,
 
 int nlml_project_identity_ex(const float* A, int64_t I, int64_t K, const double* U, int R, void* out, int out_f64, void* stream) {
   const char* who = "project_identity";
-  if (!A || !U || !out) return k7_refuse(who, "null buffer (A, U, out)");
-  if (I < 1 || K < 1) return k7_refuse(who, "I < 1 or K < 1");
-  if (R < NLML_TUCKER_RANK_MIN || R > NLML_TUCKER_RANK_MAX) return k7_refuse(who, "R outside 1..NLML_TUCKER_RANK_MAX (16)");
+  if (!A || !U || !out) return refuse(NLML_E_BADARG, who, "null buffer (A, U, out)");
+  if (I < 1 || K < 1) return refuse(NLML_E_BADARG, who, "I < 1 or K < 1");
+  if (R < NLML_TUCKER_RANK_MIN || R > NLML_TUCKER_RANK_MAX) return refuse(NLML_E_BADARG, who, "R outside 1..NLML_TUCKER_RANK_MAX (16)");
   int64_t n = 0;
-  if (__builtin_mul_overflow(I, K, &n) || n > INT64_MAX / 8) return k7_refuse(who, "A too large for 64-bit byte offsets");
-  if (!k7_aligned(A, 4) || !k7_aligned(out, out_f64 ? 8 : 4) || !k7_aligned(U, 8))
-    return k7_refuse(who, "A and out must be aligned to their element (4 bytes f32, 8 bytes f64), U 8-byte aligned");
+  if (__builtin_mul_overflow(I, K, &n) || n > INT64_MAX / 8) return refuse(NLML_E_BADARG, who, "A too large for 64-bit byte offsets");
+  if (!aligned(A, 4) || !aligned(out, out_f64 ? 8 : 4) || !aligned(U, 8))
+    return refuse(NLML_E_BADARG, who, "A and out must be aligned to their element (4 bytes f32, 8 bytes f64), U 8-byte aligned");
   return launch_project_identity(A, I, K, U, R, out, out_f64 != 0, stream);
 }
 
@@ -483,14 +501,14 @@ int nlml_project_pose(const float* X, int64_t I, int ny, int np, int nr, int64_t
 int nlml_project_pose_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
                          int rp, const double* Ur, int rr, void* out, int out_f64, void* stream) {
   const char* who = "project_pose";
-  if (!X || !out) return k7_refuse(who, "null buffer (X, out)");
-  if (I < 1 || M < 1) return k7_refuse(who, "I < 1 or M < 1");
-  if (!k7_bins_ok(ny, np, nr)) return k7_refuse(who, "ny, np, nr outside 1..NLML_POSE_BINS_MAX (32)");
+  if (!X || !out) return refuse(NLML_E_BADARG, who, "null buffer (X, out)");
+  if (I < 1 || M < 1) return refuse(NLML_E_BADARG, who, "I < 1 or M < 1");
+  if (!k7_bins_ok(ny, np, nr)) return refuse(NLML_E_BADARG, who, "ny, np, nr outside 1..NLML_POSE_BINS_MAX (32)");
   if ((Uy && (ry < 1 || ry > NLML_POSE_RANK_MAX)) || (Up && (rp < 1 || rp > NLML_POSE_RANK_MAX)) || (Ur && (rr < 1 || rr > NLML_POSE_RANK_MAX)))
-    return k7_refuse(who, "rank of a given factor outside 1..NLML_POSE_RANK_MAX (3)");
-  if (!k7_tensor_ok(I, ny, np, nr, M)) return k7_refuse(who, "tensor too large for 64-bit byte offsets");
-  if (!k7_aligned(X, x_f64 ? 8 : 4) || !k7_aligned(out, out_f64 ? 8 : 4) || !k7_aligned(Uy, 8) || !k7_aligned(Up, 8) || !k7_aligned(Ur, 8))
-    return k7_refuse(who, "X and out must be aligned to their element (4 bytes f32, 8 bytes f64), the factors 8-byte aligned");
+    return refuse(NLML_E_BADARG, who, "rank of a given factor outside 1..NLML_POSE_RANK_MAX (3)");
+  if (!k7_tensor_ok(I, ny, np, nr, M)) return refuse(NLML_E_BADARG, who, "tensor too large for 64-bit byte offsets");
+  if (!aligned(X, x_f64 ? 8 : 4) || !aligned(out, out_f64 ? 8 : 4) || !aligned(Uy, 8) || !aligned(Up, 8) || !aligned(Ur, 8))
+    return refuse(NLML_E_BADARG, who, "X and out must be aligned to their element (4 bytes f32, 8 bytes f64), the factors 8-byte aligned");
   return launch_project_pose(X, x_f64 != 0, I, ny, np, nr, M, Uy, ry, Up, rp, Ur, rr, out, out_f64 != 0, stream);
 }
 
@@ -504,8 +522,6 @@ size_t nlml_pose_eval_workspace_bytes(int64_t B, int n_intervals) {
   if (B < 0 || !eval_k_ok(n_intervals)) return 0;
   return (size_t)eval_records(B) * nlml_pose_eval_record_len(n_intervals) * sizeof(double);
 }
-
-static bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
 
 int nlml_pose_eval(const float* pose_rad, const double* pred_deg, const uint8_t* valid, const double* gt_deg, int64_t B,
                    const double* h_lo, const double* h_hi, int decimals, const double* h_intervals, const int32_t* h_axes,
@@ -522,8 +538,8 @@ int nlml_pose_eval(const float* pose_rad, const double* pred_deg, const uint8_t*
   if (decimals > 15) return fail(NLML_E_BADARG, "pose_eval: decimals > 15");
   const size_t need = nlml_pose_eval_workspace_bytes(B, n_intervals);
   if (workspace_bytes < need || (need > 0 && !workspace)) return fail(NLML_E_BADARG, "pose_eval: workspace too small");
-  if (misaligned8(pred_deg) || misaligned8(gt_deg) || misaligned8(workspace) || misaligned8(record_out) || misaligned8(result_out) ||
-      misaligned8(pred_out) || (reinterpret_cast<uintptr_t>(pose_rad) & 3))
+  if (!aligned(pred_deg, 8) || !aligned(gt_deg, 8) || !aligned(workspace, 8) || !aligned(record_out, 8) || !aligned(result_out, 8) ||
+      !aligned(pred_out, 8) || !aligned(pose_rad, 4))
     return fail(NLML_E_BADARG, "pose_eval: f64 buffers must be 8-byte aligned, pose_rad 4-byte aligned");
   PoseEvalArgs a{};
   for (int i = 0; i < 3; ++i) { a.lo[i] = h_lo[i]; a.hi[i] = h_hi[i]; }
@@ -545,7 +561,7 @@ int nlml_pose_eval_merge(const double* records, int64_t n, int n_intervals, doub
   if (n < 0) return fail(NLML_E_BADARG, "pose_eval_merge: negative record count");
   if (!eval_k_ok(n_intervals)) return fail(NLML_E_BADARG, "pose_eval_merge: number of intervals outside [0, NLML_POSE_EVAL_MAX_INTERVALS]");
   if ((n > 0 && !records) || !result_out) return fail(NLML_E_BADARG, "pose_eval_merge: null records / result_out");
-  if (misaligned8(records) || misaligned8(record_out) || misaligned8(result_out))
+  if (!aligned(records, 8) || !aligned(record_out, 8) || !aligned(result_out, 8))
     return fail(NLML_E_BADARG, "pose_eval_merge: buffers must be 8-byte aligned");
   return launch_pose_eval_merge(records, n, n_intervals, record_out, result_out, stream);
 }
@@ -554,9 +570,7 @@ int nlml_pose_eval_merge(const double* records, int64_t n, int n_intervals, doub
 static_assert(PW_NMAX == 3 + NLML_TUCKER_RANK_MAX && PW_N == 3 + 5, "powell.h's state sizes follow the ranks");
 static bool rank_ok(int r_id) { return r_id >= NLML_TUCKER_RANK_MIN && r_id <= NLML_TUCKER_RANK_MAX; }
 static int bad_rank(const char* who, int r_id) {
-  char msg[160];
-  snprintf(msg, sizeof msg, "%s: identity rank %d outside [%d, %d]", who, r_id, NLML_TUCKER_RANK_MIN, NLML_TUCKER_RANK_MAX);
-  return fail(NLML_E_SHAPE, msg);
+  return refuse(NLML_E_SHAPE, who, "identity rank %d outside [%d, %d]", r_id, NLML_TUCKER_RANK_MIN, NLML_TUCKER_RANK_MAX);
 }
 
 // The checks of every TD entry point, in the order include/nlml_hpe.h promises ("TD argument checks": hosts may match on which of two
@@ -565,19 +579,15 @@ static int bad_rank(const char* who, int r_id) {
 // rank and order in range needs nothing else: the launchers return at once.
 static int check_td_args(const char* who, int r_id, int order, int64_t N, int64_t ldx, bool null_buffer, const float* Wm, const float* x) {
   if (!rank_ok(r_id)) return bad_rank(who, r_id);
-  const char* what = nullptr;
-  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) what = "unknown order";
-  else if (N < 0) what = "negative N";
-  else if (N == 0) return 0;
-  else if (null_buffer) what = "null buffer";
-  else if (ldx < NLML_F_REFERENCE) what = "ldx < 1404";
+  if (order != NLML_TD_ORDER_FAST && order != NLML_TD_ORDER_REFERENCE) return refuse(NLML_E_BADARG, who, "unknown order");
+  if (N < 0) return refuse(NLML_E_BADARG, who, "negative N");
+  if (N == 0) return 0;
+  if (null_buffer) return refuse(NLML_E_BADARG, who, "null buffer");
+  if (ldx < NLML_F_REFERENCE) return refuse(NLML_E_BADARG, who, "ldx < 1404");
   // the matrix-core order reads Wm and the x rows with 16-byte vector loads (tucker_common.h load11 / tucker_few)
-  else if (order == NLML_TD_ORDER_FAST && (((reinterpret_cast<uintptr_t>(Wm) | reinterpret_cast<uintptr_t>(x)) & 15) || (ldx & 3)))
-    what = "NLML_TD_ORDER_FAST needs Wm and x 16-byte aligned and ldx % 4 == 0";
-  if (!what) return 0;
-  char msg[160];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return fail(NLML_E_BADARG, msg);
+  if (order == NLML_TD_ORDER_FAST && (!aligned(Wm, 16) || !aligned(x, 16) || ldx % 4 != 0))
+    return refuse(NLML_E_BADARG, who, "NLML_TD_ORDER_FAST needs Wm and x 16-byte aligned and ldx %% 4 == 0");
+  return 0;
 }
 
 static int td_objective(const char* who, const float* Wm, const float* x, int64_t ldx, const int32_t* x_index, const double* params,
@@ -633,7 +643,7 @@ int nlml_tucker_gradient_r(const float* Wm, const float* x, int64_t ldx, const i
     return rc;
   const size_t need = tucker_gradient_workspace_bytes(N);
   if (workspace_bytes < need || (need > 0 && !workspace)) return fail(NLML_E_BADARG, "tucker_gradient_r: workspace too small");
-  if (misaligned8(workspace) || misaligned8(err) || misaligned8(grad) || misaligned8(params))
+  if (!aligned(workspace, 8) || !aligned(err, 8) || !aligned(grad, 8) || !aligned(params, 8))
     return fail(NLML_E_BADARG, "tucker_gradient_r: f64 buffers and the workspace must be 8-byte aligned");
   return launch_tucker_gradient(Wm, x, ldx, x_index, params, cos_params, N, err, grad, r_id, workspace, stream);
 }
@@ -654,16 +664,11 @@ int nlml_tucker_gradient_host(const float* h_Wm, const float* h_x, int64_t ldx, 
 // S = PowellState (the shipped artefacts' 8 parameters, a constant of the type: nlml_powell_*) or PowellStateN (n = 3 + r_id
 // parameters, remembered in the state the rank-aware device kernel runs: nlml_powell_*_n)
 static bool dim_ok(int n) { return n >= 3 + NLML_TUCKER_RANK_MIN && n <= 3 + NLML_TUCKER_RANK_MAX; }
-static int null_pointer(const char* who) {
-  char msg[64];
-  snprintf(msg, sizeof msg, "%s: null pointer", who);
-  return fail(NLML_E_BADARG, msg);
-}
 
 extern "C++" {   // templates have no C linkage
 template <class S> static int powell_host_init(const char* who, void* h_state, int n, const double* h_x0, double xtol, double ftol) {
   if (!dim_ok(n)) return bad_rank(who, n - 3);
-  if (!h_state || !h_x0) return null_pointer(who);
+  if (!h_state || !h_x0) return refuse(NLML_E_BADARG, who, "null pointer");
   S& s = *static_cast<S*>(h_state);
   if (S::kDyn) std::memset(h_state, 0, sizeof(S));
   s.set_dim(n);
@@ -672,7 +677,7 @@ template <class S> static int powell_host_init(const char* who, void* h_state, i
 }
 
 template <class S> static int powell_host_step(const char* who, void* h_state, double fin, double* h_xeval) {
-  if (!h_state || !h_xeval) return null_pointer(who);
+  if (!h_state || !h_xeval) return refuse(NLML_E_BADARG, who, "null pointer");
   S& s = *static_cast<S*>(h_state);
   if (!dim_ok(s.dim())) return bad_rank(who, s.dim() - 3);
   const bool need = powell_step(s, fin);
@@ -682,7 +687,7 @@ template <class S> static int powell_host_step(const char* who, void* h_state, d
 
 template <class S>
 static int powell_host_result(const char* who, const void* h_state, double* h_x, double* h_fval, int* h_nfev, int* h_nit, int* h_status) {
-  if (!h_state || !h_x) return null_pointer(who);
+  if (!h_state || !h_x) return refuse(NLML_E_BADARG, who, "null pointer");
   const S& s = *static_cast<const S*>(h_state);
   if (!dim_ok(s.dim())) return bad_rank(who, s.dim() - 3);
   std::memcpy(h_x, s.x, sizeof(double) * s.dim());

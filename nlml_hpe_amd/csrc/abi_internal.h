@@ -28,13 +28,26 @@ inline K2Input k2_input(const float* x, int64_t ldx, const float* raw, int norma
   a.vec4 = (F % 4 == 0) && (a.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.src) & 15) == 0);
   return a;
 }
-// The arguments every K2 kernel takes (Args: hx::Args, bf::w8::Args or the f32 kernel's EncArgs), from a launcher's own arguments and
-// its input; whatever else an Args holds keeps its default or is the launcher's to fill.
-template <class Args>
-Args k2_args(const K2Input& in, int64_t B, int F, const void* blob, float* out, float* latent, uint8_t* valid) {
+// One K2 forward as every launcher gets it: the input, the batch, the blob, the outputs and the caller's workspace, already checked
+// (abi.cpp, "K2 argument checks": B > 0, and whatever the form needs of ws / ws_bytes and of in.vec4 holds).  Host side only: the
+// kernels take their own argument structs (k2_args).
+struct K2Call {
+  K2Input in;
+  int64_t B;
+  int F;
+  const void* blob;
+  float* out;
+  float* latent;
+  uint8_t* valid;
+  void* ws;
+  size_t ws_bytes;
+};
+// The arguments every K2 kernel takes (Args: hx::Args, bf::w8::Args or the f32 kernel's EncArgs) from a call; whatever else an Args
+// holds keeps its default or is the launcher's to fill.
+template <class Args> Args k2_args(const K2Call& c) {
   Args a{};
-  a.B = B; a.F = F; a.blob = blob; a.out = out; a.latent = latent; a.valid = valid;
-  a.x = in.src; a.ldx = in.ld; a.norm = in.norm;
+  a.B = c.B; a.F = c.F; a.blob = c.blob; a.out = c.out; a.latent = c.latent; a.valid = c.valid;
+  a.x = c.in.src; a.ldx = c.in.ld; a.norm = c.in.norm;
   return a;
 }
 // The <VEC4, NORM> kernel instance of an input: calls fn(std::bool_constant<VEC4>{}, std::bool_constant<NORM>{}).
@@ -52,56 +65,43 @@ int pack_blob(int F, int mode, const float* const enc_w[6], const float* const e
               const float* const head_w[3][5], const float* const head_b[3][5],
               void* blob, size_t blob_bytes);
 
-// encoder_heads.hip
-int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int normalize,
-                             int64_t B, int F, const void* blob, float* out, float* latent,
-                             uint8_t* valid, float* pre_tanh, unsigned long long* stamps, void* stream,
-                             int reeval_over = -1);   // >= 0: re-evaluation launch behind a split-f16 one (encoder_heads.hip)
+// The K2 launchers: a checked call, the launcher's own extras, the stream.  None of them refuses anything.
+// encoder_heads.hip; reeval_over >= 0: the re-evaluation launch behind a split-f16 one
+int launch_encoder_heads_f32(const K2Call& c, float* pre_tanh, unsigned long long* stamps, void* stream, int reeval_over = -1);
 // the f32 image inside an NLML_MODE_F16X2S blob (layout.h, layout_strict_f32_image16): byte offset from the blob's start
 size_t strict_f32_image_offset(int F);
-// the strict-fast mode's re-evaluation launch behind its split-f16 kernels (fused, streamed, layer-per-launch): the f32 kernel on that image
-int launch_strict_reeval(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F, const void* blob,
-                         float* out, float* latent, void* stream);
+// the strict-fast mode's re-evaluation launch behind its split-f16 kernels (fused, streamed, quad, layer-per-launch): the f32 kernel on
+// that image, no mask.  Every strict-fast forward ends with it; abi.cpp's k2_forward is the one caller.
+int launch_strict_reeval(const K2Call& c, void* stream);
 // faces of a tile the strict-fast kernels re-evaluate themselves on the vector ALUs (as NLML_MODE_F16X2 does); a tile with more goes
 // to the f32 re-evaluation launch.  0: every face beyond f16's range is re-evaluated on the f32 matrix cores -- one rule, one
 // accuracy class (the strict parity kernel's bits), and no slow-path code inside the strict kernels.
 constexpr int STRICT_INKERNEL_RESCUE_MAX = 0;
 // encoder_heads_bf16_w8.hip (throughput mode, eight waves per workgroup)
-int launch_encoder_heads_bf16(const float* x, int64_t ldx, const float* raw, int normalize,
-                              int64_t B, int F, const void* blob, float* out, float* latent,
-                              uint8_t* valid, void* stream);
-// encoder_heads_f16x2.hip (split-f16 parity mode)
-int launch_encoder_heads_f16x2(const float* x, int64_t ldx, const float* raw, int normalize,
-                               int64_t B, int F, const void* blob, float* out, float* latent,
-                               uint8_t* valid, int split, void* stream);   // split: NLML_MODE_F16X2S
+int launch_encoder_heads_bf16(const K2Call& c, void* stream);
+// encoder_heads_f16x2.hip (NLML_MODE_F16X2, the split-f16 parity mode's fused kernel)
+int launch_encoder_heads_f16x2(const K2Call& c, void* stream);
 // encoder_heads_f16x2_w8.hip (NLML_MODE_F16X2S, eight waves per workgroup: the strict-fast mode's fused kernel)
-int launch_encoder_heads_f16x2_w8(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                  const void* blob, float* out, float* latent, uint8_t* valid, void* stream);
-// the same forward as TWO launches (+ the re-evaluation launch): the trunk (layers 0-2, the eight-wave kernel ending with layer 2's output
-// in `workspace`) and the streamed tail (encoder_heads_f16x2_tailws.hip: layers E3.. and the heads with the weights through LDS once per
-// 256 faces); bit-identical to the fused kernel
+int launch_encoder_heads_f16x2_w8(const K2Call& c, void* stream);
+// the same forward as TWO launches: the trunk (layers 0-2, the eight-wave kernel ending with layer 2's output in c.ws) and the streamed
+// tail (encoder_heads_f16x2_tailws.hip: layers E3.. and the heads with the weights through LDS once per 256 faces); bit-identical to the
+// fused kernel
 size_t tailws_workspace_bytes(int64_t B, int F);
-int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                      const void* blob, float* out, float* latent, uint8_t* valid, void* workspace,
-                                      size_t ws_bytes, void* stream);
+int launch_encoder_heads_f16x2_tailws(const K2Call& c, void* stream);
 // the same forward with FOUR tiles per workgroup and the streamed tail inside the launch (encoder_heads_f16x2_w8.hip,
-// encoder_heads_f16x2_w8q_kernel; + the re-evaluation launch): bit-identical to the fused kernel.  The first quad_faces faces (a multiple
-// of 256, or all B) go that way and the others through the fused kernel, one re-evaluation launch over all B.
-// The workspace holds the quad part's hand-over, quad_workspace_bytes(quad_faces) (1 KiB per face of whole 64-face tiles).
+// encoder_heads_f16x2_w8q_kernel): bit-identical to the fused kernel.  The first quad_faces faces (a multiple of 256, or all B) go that
+// way and the others through the fused kernel.
+// c.ws holds the quad part's hand-over, quad_workspace_bytes(quad_faces) (1 KiB per face of whole 64-face tiles).
 size_t quad_workspace_bytes(int64_t quad_faces);
-int launch_encoder_heads_f16x2_w8_mixed(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                        const void* blob, float* out, float* latent, uint8_t* valid, int64_t quad_faces,
-                                        void* workspace, size_t ws_bytes, void* stream);
+int launch_encoder_heads_f16x2_w8_mixed(const K2Call& c, int64_t quad_faces, void* stream);
 // The dispatcher's split (abi.cpp; exported as nlml_k2_quad_split): how many of B faces go through the four-tile kernel on a device of
 // `cus` compute units -- whole rounds of one workgroup per unit, ((B / 64) / (4 cus)) * cus workgroups of 256 faces; 0 for cus <= 0
 int64_t k2_quad_faces(int64_t B, int cus);
 // encoder_heads_f16x2_tailws.hip: h3 = layer 2's output as operand fragments, nfb 32-face blocks of it -> poses (and the latent)
 int launch_tail_ws(const void* blob, const void* h3, int64_t nfb, int64_t B, float* out, float* latent, void* stream);
-// encoder_heads_f16x2_small.hip (split-f16 mode, big layers as separate launches + one tail launch, for small batches)
+// encoder_heads_f16x2_small.hip (split-f16 modes, big layers as separate launches + the tail's, for small batches; split: NLML_MODE_F16X2S)
 size_t small_workspace_bytes(int64_t B, int F);
-int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                     const void* blob, float* out, float* latent, uint8_t* valid, void* workspace,
-                                     size_t ws_bytes, int split, void* stream);
+int launch_encoder_heads_f16x2_small(const K2Call& c, int split, void* stream);
 // artefacts.hip
 int launch_cosine_table(const float* angles, int64_t n, const double* cos_params, int R, double* out, void* stream);
 int launch_mode5_product(const float* core, const float* U, int Q, int R5, int M, float* W, void* stream);

@@ -813,12 +813,10 @@ __global__ __launch_bounds__(256, 1) void encoder_heads_f32_kernel(EncArgs a) {
   NLML_STAMP(13);
 }
 
-int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int normalize,
-                             int64_t B, int F, const void* blob, float* out, float* latent,
-                             uint8_t* valid, float* pre_tanh, unsigned long long* stamps, void* stream, int reeval_over) {
-  if (B == 0) return 0;
-  const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  EncArgs a = k2_args<EncArgs>(in, B, F, blob, out, latent, valid);
+int launch_encoder_heads_f32(const K2Call& c, float* pre_tanh, unsigned long long* stamps, void* stream, int reeval_over) {
+  const K2Input& in = c.in;
+  const int64_t B = c.B;
+  EncArgs a = k2_args<EncArgs>(c);
   a.pre_tanh = pre_tanh;
   a.stamps = stamps;
   a.reeval_over = reeval_over;
@@ -831,8 +829,7 @@ int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int 
   const int tile = wide ? 64 : 32;
   const dim3 grid((unsigned)((B + tile - 1) / tile)), block(256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dbg) {
-    if (in.norm || !in.vec4) return fail(NLML_E_BADARG, "debug build: features input, F % 4 == 0 only");
+  if (dbg) {   // (feature rows readable 16 bytes at a time: nlml_encoder_heads_fwd_debug has checked)
     hipLaunchKernelGGL((encoder_heads_f32_kernel<true, false, true, 2>), dim3((unsigned)((B + 63) / 64)), block, 0, st, a);
   } else {
     k2_with_variant(in, [&](auto V, auto N) {
@@ -845,10 +842,11 @@ int launch_encoder_heads_f32(const float* x, int64_t ldx, const float* raw, int 
 
 // tiles with faces beyond f16's range (more than STRICT_INKERNEL_RESCUE_MAX = 0 of them): the whole tile again on the f32 matrix cores, from the
 // f32 image behind the split-f16 one; every other tile of that launch ends after one 768-byte read
-int launch_strict_reeval(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F, const void* blob,
-                         float* out, float* latent, void* stream) {
-  return launch_encoder_heads_f32(x, ldx, raw, normalize, B, F, static_cast<const char*>(blob) + strict_f32_image_offset(F), out, latent,
-                                  nullptr, nullptr, nullptr, stream, STRICT_INKERNEL_RESCUE_MAX);
+int launch_strict_reeval(const K2Call& c, void* stream) {
+  K2Call r = c;
+  r.blob = static_cast<const char*>(c.blob) + strict_f32_image_offset(c.F);
+  r.valid = nullptr;
+  return launch_encoder_heads_f32(r, nullptr, nullptr, stream, STRICT_INKERNEL_RESCUE_MAX);
 }
 
 }  // namespace nlml

@@ -222,14 +222,11 @@ __global__ __launch_bounds__(512) void encoder_heads_bf16_w8_kernel(Args a) {
 }  // namespace w8
 }  // namespace bf
 
-int launch_encoder_heads_bf16(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                              const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
-  if (B == 0) return 0;
-  const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  const bf::w8::Args a = k2_args<bf::w8::Args>(in, B, F, blob, out, latent, valid);
-  const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(512);
+int launch_encoder_heads_bf16(const K2Call& c, void* stream) {
+  const bf::w8::Args a = k2_args<bf::w8::Args>(c);
+  const dim3 grid((unsigned)((c.B + TILE_FACES - 1) / TILE_FACES)), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  k2_with_variant(in, [&](auto V, auto N) {
+  k2_with_variant(c.in, [&](auto V, auto N) {
     hipLaunchKernelGGL((bf::w8::encoder_heads_bf16_w8_kernel<decltype(V)::value, decltype(N)::value>), grid, block, 0, st, a);
   });
   return hip_launch_status();

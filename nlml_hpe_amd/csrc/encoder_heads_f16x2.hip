@@ -315,16 +315,12 @@ __global__ __launch_bounds__(256, 1) void encoder_heads_f16x2_kernel(Args a) {
 
 }  // namespace hx
 
-int launch_encoder_heads_f16x2(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                               const void* blob, float* out, float* latent, uint8_t* valid, int split, void* stream) {
-  if (B == 0) return 0;
-  // the strict-fast mode runs on the eight-wave kernel (encoder_heads_f16x2_w8.hip)
-  if (split) return launch_encoder_heads_f16x2_w8(x, ldx, raw, normalize, B, F, blob, out, latent, valid, stream);
-  const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  const hx::Args a = k2_args<hx::Args>(in, B, F, blob, out, latent, valid);
-  const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(256);
+// (the strict-fast mode runs on the eight-wave kernel: encoder_heads_f16x2_w8.hip)
+int launch_encoder_heads_f16x2(const K2Call& c, void* stream) {
+  const hx::Args a = k2_args<hx::Args>(c);
+  const dim3 grid((unsigned)((c.B + TILE_FACES - 1) / TILE_FACES)), block(256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  k2_with_variant(in, [&](auto V, auto N) {
+  k2_with_variant(c.in, [&](auto V, auto N) {
     hipLaunchKernelGGL((hx::encoder_heads_f16x2_kernel<decltype(V)::value, decltype(N)::value>), grid, block, 0, st, a);
   });
   return hip_launch_status();

@@ -417,27 +417,25 @@ size_t small_workspace_bytes(int64_t B, int F) {
   return hx::LayerFrags::bytes(B, F);
 }
 
-int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                     const void* blob, float* out, float* latent, uint8_t* valid, void* workspace,
-                                     size_t ws_bytes, int split, void* stream) {
+int launch_encoder_heads_f16x2_small(const K2Call& c, int split, void* stream) {
   using namespace hxs;
-  if (B == 0) return 0;
-  if (ws_bytes < small_workspace_bytes(B, F) || !workspace) return fail(NLML_E_BADARG, "small-batch path: workspace too small");
-  if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(NLML_E_BADARG, "small-batch path: workspace must be 16-byte aligned");
+  const int64_t B = c.B;
+  const int F = c.F;
+  const void* blob = c.blob;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int ntiles = (int)((B + 63) / 64);
   const int k16 = layout_e0_steps(kLayoutHX, F);
   const int buf_steps = LayerFrags::steps(k16);
-  h8* bufA = reinterpret_cast<h8*>(workspace);
+  h8* bufA = reinterpret_cast<h8*>(c.ws);
   h8* bufB = bufA + ntiles * LayerFrags::tile_units(buf_steps);
 
-  const K2Input rows = k2_input(x, ldx, raw, normalize, F);
+  const K2Input& rows = c.in;
   if (rows.vec4)
     hipLaunchKernelGGL(prepass_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, rows.src, rows.ld, B, F,
-                       rows.norm, k16, buf_steps, bufA, valid);
+                       rows.norm, k16, buf_steps, bufA, c.valid);
   else
     hipLaunchKernelGGL(prepass_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, rows.src, rows.ld, B, F,
-                       rows.norm, k16, buf_steps, bufA, valid);
+                       rows.norm, k16, buf_steps, bufA, c.valid);
 
   // the three big layers: {stage, K16, blocks per job, jobs}; ReLU; job j covers output columns 32 * blocks * j ..
   struct S { int stage, K16, nb, jobs; };
@@ -479,7 +477,8 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
   }
   {
     // (no mask: the pre-pass wrote it; x: the tail's slow path re-reads the face's input)
-    const hx::Args ta = k2_args<hx::Args>(rows, B, F, blob, out, latent, nullptr);
+    hx::Args ta = k2_args<hx::Args>(c);
+    ta.valid = nullptr;
     if (split) {   // E3..E5, then the three heads as workgroups of their own; the latent image passes through the free buffer
       hipLaunchKernelGGL(hx::tail_encoder_kernel, dim3((unsigned)(2 * ntiles)), dim3(256), 0, st, ta, (const h8*)in, buf_steps, reinterpret_cast<char*>(outb));
       hipLaunchKernelGGL(hx::head_kernel, dim3((unsigned)(6 * ntiles)), dim3(256), 0, st, ta, reinterpret_cast<const char*>(outb));
@@ -487,9 +486,7 @@ int launch_encoder_heads_f16x2_small(const float* x, int64_t ldx, const float* r
       hipLaunchKernelGGL(tail_kernel<64>, dim3((unsigned)(2 * ntiles)), dim3(256), 0, st, ta, (const h8*)in, buf_steps);
     }
   }
-  if (int rc = hip_launch_status()) return rc;
-  // the strict-fast mode's f32 re-evaluation launch, as behind its fused kernel (encoder_heads_f16x2_w8.hip)
-  return split ? launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream) : 0;
+  return hip_launch_status();
 }
 
 }  // namespace nlml

@@ -18,7 +18,6 @@ __global__ __launch_bounds__(512) void tail_ws_kernel(TwArgs a) {
 }  // namespace hx
 
 int launch_tail_ws(const void* blob, const void* h3, int64_t nfb, int64_t B, float* out, float* latent, void* stream) {
-  if (B == 0) return 0;
   hx::TwArgs a;
   a.blob = blob; a.h3 = reinterpret_cast<const hx::u4*>(h3); a.out = out; a.latent = latent; a.B = B; a.nfb = nfb;
   hipLaunchKernelGGL(hx::tail_ws_kernel, dim3((unsigned)((nfb + 7) / 8)), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), a);

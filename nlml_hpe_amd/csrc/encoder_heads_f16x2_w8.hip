@@ -438,87 +438,65 @@ __global__ __launch_bounds__(512) void encoder_heads_f16x2_w8q_kernel(Args a, Tw
 
 }  // namespace hx
 
-// ---- the strict-fast forward as trunk launch + streamed tail launch (+ the f32 re-evaluation launch) -------------------------------
+// ---- the strict-fast forward as trunk launch + streamed tail launch ----------------------------------------------------------------
+// (every strict-fast form: + the f32 re-evaluation launch, which the caller enqueues behind the launches here)
 size_t tailws_workspace_bytes(int64_t B, int F) {
   if (B <= 0 || F <= 0) return 0;
   return hx::TrunkFrags::bytes(B);
 }
 
-int launch_encoder_heads_f16x2_tailws(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                      const void* blob, float* out, float* latent, uint8_t* valid, void* workspace,
-                                      size_t ws_bytes, void* stream) {
-  if (B == 0) return 0;
-  if (!workspace || ws_bytes < tailws_workspace_bytes(B, F)) return fail(NLML_E_BADARG, "streamed-tail path: workspace too small");
-  if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(NLML_E_BADARG, "streamed-tail path: workspace must be 16-byte aligned");
-  const K2Input in = k2_input(x, ldx, raw, normalize, F);
-  hx::Args a = k2_args<hx::Args>(in, B, F, blob, out, latent, valid);
-  a.h3ws = workspace;
-  if (!in.vec4) return fail(NLML_E_BADARG, "streamed-tail path: x must be 16-byte aligned with F and ldx multiples of 4");
-  const int64_t ntiles = (B + TILE_FACES - 1) / TILE_FACES;
+int launch_encoder_heads_f16x2_tailws(const K2Call& c, void* stream) {
+  hx::Args a = k2_args<hx::Args>(c);
+  a.h3ws = c.ws;
+  const int64_t ntiles = (c.B + TILE_FACES - 1) / TILE_FACES;
   const dim3 grid((unsigned)ntiles), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (a.norm) hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<true, true, true>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<true, false, true>), grid, block, 0, st, a);
   if (int rc = hip_launch_status()) return rc;
-  if (int rc = launch_tail_ws(blob, workspace, 2 * ntiles, B, out, latent, stream)) return rc;
-  return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
+  return launch_tail_ws(c.blob, c.ws, 2 * ntiles, c.B, c.out, c.latent, stream);
 }
 
-
-// the fused kernel alone over B faces of `in`'s rows (no re-evaluation launch behind it)
-static int launch_w8_fused_kernel(const K2Input& in, int64_t B, int F, const void* blob, float* out, float* latent, uint8_t* valid,
-                                  void* stream) {
-  const hx::Args a = k2_args<hx::Args>(in, B, F, blob, out, latent, valid);
-  const dim3 grid((unsigned)((B + TILE_FACES - 1) / TILE_FACES)), block(512);
+// ---- the fused kernel --------------------------------------------------------------------------------------------------------------
+int launch_encoder_heads_f16x2_w8(const K2Call& c, void* stream) {
+  const hx::Args a = k2_args<hx::Args>(c);
+  const dim3 grid((unsigned)((c.B + TILE_FACES - 1) / TILE_FACES)), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  k2_with_variant(in, [&](auto V, auto N) {
+  k2_with_variant(c.in, [&](auto V, auto N) {
     hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8_kernel<decltype(V)::value, decltype(N)::value>), grid, block, 0, st, a);
   });
   return hip_launch_status();
 }
 
-int launch_encoder_heads_f16x2_w8(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                  const void* blob, float* out, float* latent, uint8_t* valid, void* stream) {
-  if (B == 0) return 0;
-  if (int rc = launch_w8_fused_kernel(k2_input(x, ldx, raw, normalize, F), B, F, blob, out, latent, valid, stream)) return rc;
-  return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
-}
-
-// ---- the strict-fast forward with four tiles per workgroup and the streamed tail inside the launch (+ the f32 re-evaluation launch) ----
+// ---- the strict-fast forward with four tiles per workgroup and the streamed tail inside the launch ---------------------------------
 // The first quad_faces faces (a multiple of 256, or all B of them) go through encoder_heads_f16x2_w8q_kernel, the others through the
-// fused kernel on offset pointers in the same stream; one re-evaluation launch over all B follows.
+// fused kernel on offset pointers in the same stream.
 size_t quad_workspace_bytes(int64_t quad_faces) { return quad_faces <= 0 ? 0 : hx::TrunkFrags::bytes(quad_faces); }
 
-int launch_encoder_heads_f16x2_w8_mixed(const float* x, int64_t ldx, const float* raw, int normalize, int64_t B, int F,
-                                        const void* blob, float* out, float* latent, uint8_t* valid, int64_t quad_faces,
-                                        void* workspace, size_t ws_bytes, void* stream) {
-  if (B == 0) return 0;
-  if (quad_faces < 0 || quad_faces > B || (quad_faces < B && quad_faces % (4 * TILE_FACES)))
-    return fail(NLML_E_BADARG, "quad path: the quad part is whole workgroups of 256 faces, or the whole batch");
-  K2Input in = k2_input(x, ldx, raw, normalize, F);
+int launch_encoder_heads_f16x2_w8_mixed(const K2Call& c, int64_t quad_faces, void* stream) {
   if (quad_faces > 0) {
-    if (!workspace || ws_bytes < quad_workspace_bytes(quad_faces)) return fail(NLML_E_BADARG, "quad path: workspace too small");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(NLML_E_BADARG, "quad path: workspace must be 16-byte aligned");
-    if (!in.vec4) return fail(NLML_E_BADARG, "quad path: x must be 16-byte aligned with F and ldx multiples of 4");
-    hx::Args a = k2_args<hx::Args>(in, quad_faces, F, blob, out, latent, valid);
-    a.h3ws = workspace;
+    hx::Args a = k2_args<hx::Args>(c);
+    a.B = quad_faces;
+    a.h3ws = c.ws;
     const int64_t ntiles = (quad_faces + TILE_FACES - 1) / TILE_FACES;
     hx::TwArgs t;
-    t.blob = blob; t.h3 = reinterpret_cast<const hx::u4*>(workspace); t.out = out; t.latent = latent; t.B = quad_faces; t.nfb = 2 * ntiles;
+    t.blob = c.blob; t.h3 = reinterpret_cast<const hx::u4*>(c.ws); t.out = c.out; t.latent = c.latent; t.B = quad_faces; t.nfb = 2 * ntiles;
     const dim3 grid((unsigned)((ntiles + 3) / 4)), block(512);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (a.norm) hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8q_kernel<true, true>), grid, block, 0, st, a, t);
     else hipLaunchKernelGGL((hx::encoder_heads_f16x2_w8q_kernel<true, false>), grid, block, 0, st, a, t);
     if (int rc = hip_launch_status()) return rc;
   }
-  if (quad_faces < B) {   // (ld % 4 == 0 wherever there is a quad part: the remainder's rows are as aligned as the batch's)
-    K2Input rest = in;
-    rest.src = in.src + quad_faces * in.ld;
-    if (int rc = launch_w8_fused_kernel(rest, B - quad_faces, F, blob, out + quad_faces * 3,
-                                        latent ? latent + quad_faces * NLML_LATENT : nullptr, valid ? valid + quad_faces : nullptr, stream))
-      return rc;
+  if (quad_faces < c.B) {   // (ld % 4 == 0 wherever there is a quad part: the remainder's rows are as aligned as the batch's)
+    K2Call rest = c;
+    rest.in.src += quad_faces * c.in.ld;
+    rest.B -= quad_faces;
+    rest.out += quad_faces * 3;
+    if (rest.latent) rest.latent += quad_faces * NLML_LATENT;
+    if (rest.valid) rest.valid += quad_faces;
+    return launch_encoder_heads_f16x2_w8(rest, stream);
   }
-  return launch_strict_reeval(x, ldx, raw, normalize, B, F, blob, out, latent, stream);
+  return 0;
 }
 
 }  // namespace nlml
