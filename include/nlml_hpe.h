@@ -600,6 +600,42 @@ int nlml_project_identity_ex(const float* A, int64_t I, int64_t K, const double*
 int nlml_project_pose_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
                          int rp, const double* Ur, int rr, void* out, int out_f64, void* stream);
 
+/* K8: the cosine fit of the pose factors -- a batch of independent fits of  a cos(b radians(w) + c) + d  to a column, each a whole
+ * Powell minimisation, in one launch.  Replaces TD_Trainer.Train's scipy.optimize.minimize(objective, guess, method='Powell') per
+ * column of U_yaw, U_pitch and U_roll (TD_Trainer.py:37-42,70-93,320-322); its results are the optimized_* rows of Trained_data.npz.
+ *   y       f64[C,ld]   fit f's samples y[f][0..n[f]) (a factor column, upcast: exact)
+ *   w_deg   f64[C,ld]   fit f's angles in DEGREES (the bins)
+ *   ld      row stride of y and w_deg in elements, >= every n[f]; offsets are 64-bit
+ *   n       i32[C]      DEVICE: rows of each fit, 1..NLML_COSINE_FIT_ROWS_MAX; fits of different n may share a launch
+ *   h_n     i32[C]      HOST: the same values.  The library never reads device memory on the host, so the checks below read this
+ *                       copy; the kernel reads n, and clamps it to min(64, ld) so that no row is read beyond its stride.
+ *   x0      f64[C,4]    the starts (a, b, c, d)
+ *   xtol, ftol          scipy's xtol / ftol (its defaults: 1e-4 both)
+ *   x       f64[C,4]    res.x;   fun f64[C] res.fun;   nfev, nit i32[C] res.nfev, res.nit;   status i32[C] as nlml_tucker_powell's
+ *                       (1 converged, 2 maxfev = 4000 reached, 3 maxiter, 4 NaN); fun, nfev, nit, status may be NULL
+ * The objective is 1/2 sum_i (y_i - (a cos(b w_i pi/180 + c) + d))^2 in the reference's f64 operation order with its two library calls
+ * (np.cos and the scalar ** 2, neither correctly rounded in glibc) replaced by their correctly rounded values; csrc/cosine_fit_ref.h
+ * states the order.  The minimiser is the Powell machine of nlml_tucker_powell with four parameters: given the same objective values it
+ * visits scipy's trial points bit for bit.  One wave per fit, the whole minimisation inside the launch, no atomics: a fit's result does
+ * not depend on its position in the batch or on C.
+ * nlml_cosine_fit_objective evaluates that objective on the device at N parameter points params f64[N,4] against ONE fit's rows
+ * (y, w_deg f64[n]: pass the fit's row pointers) -> out f64[N]: the evaluation the fit kernel runs, read out.
+ * The *_host forms run the same header on HOST buffers in plain C++ (no GPU involved; no device copy of n) and return the same bits.
+ * Checks, in this order, each NLML_E_BADARG with a message and before any GPU call.  Fits: a NULL required buffer (unless C == 0);
+ * C < 0; C == 0 returns 0 and launches nothing; an n outside 1..64; ld < an n; C above 2^31 - 1 or C ld beyond 64-bit byte offsets;
+ * a misaligned pointer (8 bytes f64, 4 bytes i32).  Objective: a NULL buffer (unless N == 0); N < 0; n outside 1..64; N above
+ * 2^31 - 1; N == 0 returns 0; a misaligned pointer. */
+#define NLML_COSINE_FIT_ROWS_MAX 64
+int nlml_cosine_fit(const double* y, const double* w_deg, int64_t ld, const int32_t* n, const int32_t* h_n, int64_t C,
+                    const double* x0, double xtol, double ftol, double* x, double* fun, int32_t* nfev, int32_t* nit,
+                    int32_t* status, void* stream);
+int nlml_cosine_fit_host(const double* h_y, const double* h_w_deg, int64_t ld, const int32_t* h_n, int64_t C, const double* h_x0,
+                         double xtol, double ftol, double* h_x, double* h_fun, int32_t* h_nfev, int32_t* h_nit, int32_t* h_status);
+int nlml_cosine_fit_objective(const double* y, const double* w_deg, int n, const double* params, int64_t N, double* out,
+                              void* stream);
+int nlml_cosine_fit_objective_host(const double* h_y, const double* h_w_deg, int n, const double* h_params, int64_t N,
+                                   double* h_out);
+
 /* Host-side stepping of the same Powell state machine (no GPU involved): the caller evaluates
  * the objective.  Used to check the restated control flow against scipy on the CPU.
  *   h_state: caller-allocated buffer of nlml_powell_state_bytes() bytes.

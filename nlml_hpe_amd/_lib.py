@@ -104,6 +104,13 @@ SYMBOLS = {
     "nlml_project_identity_ex": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "nlml_project_pose_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_void_p, C.c_int] * 3
                              + [C.c_void_p, C.c_int, C.c_void_p]),
+    # K8 (cosine fit): y, w_deg, ld, [n,] h_n, C, x0, xtol, ftol, x, fun, nfev, nit, status[, stream] | y, w_deg, n, params, N, out[, stream]
+    "nlml_cosine_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double]
+                        + [C.c_void_p] * 6),
+    "nlml_cosine_fit_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double]
+                             + [C.c_void_p] * 5),
+    "nlml_cosine_fit_objective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nlml_cosine_fit_objective_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "nlml_powell_state_bytes": (C.c_size_t, []),
     "nlml_powell_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "nlml_powell_step": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
@@ -136,6 +143,7 @@ MODE_GRAM_KCHUNK = 4096            # NLML_GRAM_KCHUNK: the least columns of a K 
 POSE_BINS_MAX = 32                 # NLML_POSE_BINS_MAX
 POSE_GRAMS_MAX_CELLS = 768         # NLML_POSE_GRAMS_MAX_CELLS
 POSE_RANK_MAX = 3                  # NLML_POSE_RANK_MAX
+COSINE_FIT_ROWS_MAX = 64          # NLML_COSINE_FIT_ROWS_MAX
 POSE_EVAL_MAX_INTERVALS = 64       # NLML_POSE_EVAL_MAX_INTERVALS
 POSE_EVAL_FACES_PER_RECORD = 2048  # NLML_POSE_EVAL_FACES_PER_RECORD
 

@@ -13,6 +13,7 @@
 #include "../../include/nlml_hpe.h"
 #include "abi_internal.h"
 #include "centroid_ref.h"
+#include "cosine_fit_ref.h"
 #include "layout.h"
 #include "powell.h"
 #include "rotate_ref.h"
@@ -657,6 +658,73 @@ int nlml_tucker_gradient_host(const float* h_Wm, const float* h_x, int64_t ldx, 
   for (int64_t n = 0; n < N; ++n)
     tg_gradient_host(h_Wm, h_x + (h_x_index ? (int64_t)h_x_index[n] : n) * ldx, h_params + n * (3 + r_id), h_cos_params, r_id,
                      h_err ? h_err + n : nullptr, h_grad + n * (3 + r_id), h_v ? h_v + n * NLML_F_REFERENCE : nullptr);
+  return 0;
+}
+
+// ---- K8: the cosine fit of the pose factors (cosine_fit_ref.h, cosine_fit.hip) -----------------------------------------------
+static_assert(CF_ROWS_MAX == NLML_COSINE_FIT_ROWS_MAX, "one row per lane");
+// The checks of include/nlml_hpe.h ("K8") in their stated order; -> 0 with *run = whether there is anything to do.
+static int check_cosine_fit(const char* who, bool null_buffer, int64_t C, int64_t ld, const int32_t* h_n, bool* run) {
+  *run = false;
+  if (C != 0 && null_buffer) return refuse(NLML_E_BADARG, who, "null buffer");
+  if (C < 0) return refuse(NLML_E_BADARG, who, "negative C");
+  if (C == 0) return 0;
+  for (int64_t f = 0; f < C; ++f)
+    if (h_n[f] < 1 || h_n[f] > NLML_COSINE_FIT_ROWS_MAX)
+      return refuse(NLML_E_BADARG, who, "n[%lld] = %d outside [1, %d]", (long long)f, (int)h_n[f], NLML_COSINE_FIT_ROWS_MAX);
+  for (int64_t f = 0; f < C; ++f)
+    if (ld < h_n[f]) return refuse(NLML_E_BADARG, who, "ld = %lld < n[%lld] = %d", (long long)ld, (long long)f, (int)h_n[f]);
+  if (C > (int64_t)INT32_MAX || ld > INT64_MAX / 8 / C) return refuse(NLML_E_BADARG, who, "batch too large for 64-bit byte offsets");
+  *run = true;
+  return 0;
+}
+static int check_cosine_objective(const char* who, bool null_buffer, int n, int64_t N, bool* run) {
+  *run = false;
+  if (N != 0 && null_buffer) return refuse(NLML_E_BADARG, who, "null buffer");
+  if (N < 0) return refuse(NLML_E_BADARG, who, "negative N");
+  if (n < 1 || n > NLML_COSINE_FIT_ROWS_MAX) return refuse(NLML_E_BADARG, who, "n = %d outside [1, %d]", n, NLML_COSINE_FIT_ROWS_MAX);
+  if (N > (int64_t)INT32_MAX) return refuse(NLML_E_BADARG, who, "too many points for one launch");
+  *run = N != 0;
+  return 0;
+}
+
+int nlml_cosine_fit(const double* y, const double* w_deg, int64_t ld, const int32_t* n, const int32_t* h_n, int64_t C, const double* x0,
+                    double xtol, double ftol, double* x, double* fun, int32_t* nfev, int32_t* nit, int32_t* status, void* stream) {
+  bool run;
+  if (int rc = check_cosine_fit("cosine_fit", !y || !w_deg || !n || !h_n || !x0 || !x, C, ld, h_n, &run)) return rc;
+  if (!run) return 0;
+  if (!aligned(y, 8) || !aligned(w_deg, 8) || !aligned(x0, 8) || !aligned(x, 8) || !aligned(fun, 8))
+    return fail(NLML_E_BADARG, "cosine_fit: f64 buffers must be 8-byte aligned");
+  if (!aligned(n, 4) || !aligned(nfev, 4) || !aligned(nit, 4) || !aligned(status, 4))
+    return fail(NLML_E_BADARG, "cosine_fit: i32 buffers must be 4-byte aligned");
+  return launch_cosine_fit(y, w_deg, ld, n, C, x0, xtol, ftol, x, fun, nfev, nit, status, stream);
+}
+
+// the same fits (cosine_fit_ref.h) on host buffers: plain C++, no HIP call
+int nlml_cosine_fit_host(const double* h_y, const double* h_w_deg, int64_t ld, const int32_t* h_n, int64_t C, const double* h_x0,
+                         double xtol, double ftol, double* h_x, double* h_fun, int32_t* h_nfev, int32_t* h_nit, int32_t* h_status) {
+  bool run;
+  if (int rc = check_cosine_fit("cosine_fit_host", !h_y || !h_w_deg || !h_n || !h_x0 || !h_x, C, ld, h_n, &run)) return rc;
+  if (!run) return 0;
+  for (int64_t f = 0; f < C; ++f)
+    cf_fit_host(h_y + f * ld, h_w_deg + f * ld, h_n[f], h_x0 + f * CF_NPAR, xtol, ftol, h_x + f * CF_NPAR, h_fun ? h_fun + f : nullptr,
+                h_nfev ? h_nfev + f : nullptr, h_nit ? h_nit + f : nullptr, h_status ? h_status + f : nullptr);
+  return 0;
+}
+
+int nlml_cosine_fit_objective(const double* y, const double* w_deg, int n, const double* params, int64_t N, double* out, void* stream) {
+  bool run;
+  if (int rc = check_cosine_objective("cosine_fit_objective", !y || !w_deg || !params || !out, n, N, &run)) return rc;
+  if (!run) return 0;
+  if (!aligned(y, 8) || !aligned(w_deg, 8) || !aligned(params, 8) || !aligned(out, 8))
+    return fail(NLML_E_BADARG, "cosine_fit_objective: f64 buffers must be 8-byte aligned");
+  return launch_cosine_fit_objective(y, w_deg, n, params, N, out, stream);
+}
+
+int nlml_cosine_fit_objective_host(const double* h_y, const double* h_w_deg, int n, const double* h_params, int64_t N, double* h_out) {
+  bool run;
+  if (int rc = check_cosine_objective("cosine_fit_objective_host", !h_y || !h_w_deg || !h_params || !h_out, n, N, &run)) return rc;
+  for (int64_t e = 0; run && e < N; ++e) h_out[e] = cf_objective(h_y, h_w_deg, n, h_params + e * CF_NPAR);
   return 0;
 }
 

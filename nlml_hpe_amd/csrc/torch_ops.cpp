@@ -326,6 +326,38 @@ at::Tensor cosine_table(const at::Tensor& angles_, const at::Tensor& cosp_) {
   return out;
 }
 
+// K8: C cosine fits in one launch.  y, w_deg f64[C,ld], n the row counts (host integers: the entry point checks them; their device copy
+// is made here), x0 f64[C,4] -> (x f64[C,4], fun f64[C], nfev, nit, status i32[C])
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> cosine_fit(const at::Tensor& y_, const at::Tensor& w_, at::IntArrayRef n,
+                                                                                   const at::Tensor& x0_, double xtol, double ftol) {
+  need(y_, "y", at::kDouble);
+  need(w_, "w_deg", at::kDouble);
+  need(x0_, "x0", at::kDouble);
+  same_device(y_, w_, "w_deg");
+  same_device(y_, x0_, "x0");
+  TORCH_CHECK(y_.dim() == 2 && w_.sizes() == y_.sizes(), "y and w_deg: expected two [C,ld] tensors of one shape, got ", y_.sizes(), ", ", w_.sizes());
+  const int64_t C = y_.size(0), ld = y_.size(1);
+  TORCH_CHECK(x0_.dim() == 2 && x0_.size(0) == C && x0_.size(1) == 4, "x0: expected [", C, ",4], got ", x0_.sizes());
+  TORCH_CHECK((int64_t)n.size() == C, "n: expected ", C, " row counts, got ", n.size());
+  std::vector<int32_t> h_n(n.size());
+  for (size_t f = 0; f < n.size(); ++f) {
+    TORCH_CHECK(n[f] >= 1 && n[f] <= NLML_COSINE_FIT_ROWS_MAX && n[f] <= ld, "n[", f, "] = ", n[f], " outside [1, min(", NLML_COSINE_FIT_ROWS_MAX,
+                ", ld = ", ld, ")]");
+    h_n[f] = (int32_t)n[f];
+  }
+  const at::Tensor y = y_.contiguous(), w = w_.contiguous(), x0 = x0_.contiguous();
+  const auto f64 = y.options(), i32 = y.options().dtype(at::kInt);
+  at::Tensor d_n = at::empty({C}, i32);
+  if (C) d_n.copy_(at::from_blob(h_n.data(), {C}, at::TensorOptions().dtype(at::kInt)));   // pageable source: the copy is complete on return
+  at::Tensor res = at::empty({C, 4}, f64), fun = at::empty({C}, f64), nfev = at::empty({C}, i32), nit = at::empty({C}, i32),
+             status = at::empty({C}, i32);
+  OnDevice dev(y);
+  check(nlml_cosine_fit(y.data_ptr<double>(), w.data_ptr<double>(), ld, d_n.data_ptr<int32_t>(), h_n.data(), C, x0.data_ptr<double>(), xtol,
+                        ftol, res.data_ptr<double>(), fun.data_ptr<double>(), nfev.data_ptr<int32_t>(), nit.data_ptr<int32_t>(),
+                        status.data_ptr<int32_t>(), dev.stream), "nlml_cosine_fit");
+  return {res, fun, nfev, nit, status};
+}
+
 // K5: the evaluation block in one native pass.  pose f32[B,3] radians or f64[B,3] degrees (by dtype), valid bool/u8[B] or None,
 // gt f64[B,3]; lo / hi the inclusive GT range, intervals [K*2] (low, high) with their axes [K]; the records' workspace comes from
 // torch's allocator -> (record f64[12+2K], result f64[14+2K])
@@ -496,6 +528,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> tucker_po
 }
 void video_post_meta(const at::Tensor&, const at::Tensor&, const std::optional<at::Tensor>&, double, double, double, double, double, at::Tensor,
                      at::Tensor, at::Tensor, at::Tensor, at::Tensor) {}   // everything in place: nothing to shape
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> cosine_fit_meta(const at::Tensor& y, const at::Tensor&, at::IntArrayRef,
+                                                                                        const at::Tensor&, double, double) {
+  const int64_t C = y.size(0);
+  const auto i32 = y.options().dtype(at::kInt);
+  return {at::empty({C, 4}, y.options()), at::empty({C}, y.options()), at::empty({C}, i32), at::empty({C}, i32), at::empty({C}, i32)};
+}
 at::Tensor cosine_table_meta(const at::Tensor& angles, const at::Tensor& cosp) { return at::empty({angles.size(0), cosp.size(0)}, cosp.options()); }
 
 std::tuple<at::Tensor, at::Tensor> pose_eval_meta(const at::Tensor& pose, const std::optional<at::Tensor>&, const at::Tensor& gt,
@@ -527,6 +565,7 @@ TORCH_LIBRARY(nlml_hpe, m) {
   m.def("video_post(Tensor pose_rad, Tensor raw, Tensor? valid, float frame_w, float frame_h, float alpha, float max_jump, float size, "
         "Tensor(a!) state, Tensor(b!) smoothed, Tensor(c!) centre, Tensor(d!) endpoints, Tensor(e!) updated) -> ()");
   m.def("cosine_table(Tensor angles_rad, Tensor cos_params) -> Tensor");
+  m.def("cosine_fit(Tensor y, Tensor w_deg, int[] n, Tensor x0, float xtol=1e-4, float ftol=1e-4) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("pose_eval(Tensor pose, Tensor? valid, Tensor gt, float[] lo, float[] hi, int decimals, float[] intervals, int[] axes) "
         "-> (Tensor, Tensor)");
   m.def("pose_eval_merge(Tensor records, int K) -> (Tensor, Tensor)");
@@ -551,6 +590,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
   m.impl("tucker_powell", &tucker_powell);
   m.impl("video_post", &video_post);
   m.impl("cosine_table", &cosine_table);
+  m.impl("cosine_fit", &cosine_fit);
   m.impl("pose_eval", &pose_eval);
   m.impl("pose_eval_merge", &pose_eval_merge);
   m.impl("mode_gram", &mode_gram);
@@ -574,6 +614,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("tucker_powell", &tucker_powell_meta);
   m.impl("video_post", &video_post_meta);
   m.impl("cosine_table", &cosine_table_meta);
+  m.impl("cosine_fit", &cosine_fit_meta);
   m.impl("pose_eval", &pose_eval_meta);
   m.impl("pose_eval_merge", &pose_eval_merge_meta);
   m.impl("mode_gram", &mode_gram_meta);

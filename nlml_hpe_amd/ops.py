@@ -545,6 +545,75 @@ def project_pose(X: torch.Tensor, U_yaw=None, U_pitch=None, U_roll=None, out_dty
     return out
 
 
+# ---- K8: the cosine fit of the pose factors (csrc/cosine_fit.hip; the driver is nlml_hpe_amd/TD_Trainer.py) -------------------
+def _fit_rows(y: torch.Tensor, w_deg: torch.Tensor):
+    _need_cuda(y, "y", torch.float64)
+    _need_cuda(w_deg, "w_deg", torch.float64)
+    if y.dim() != 2 or w_deg.shape != y.shape:
+        raise ValueError(f"y and w_deg: expected two [C,ld] tensors of one shape, got {tuple(y.shape)}, {tuple(w_deg.shape)}")
+    return y.contiguous(), w_deg.contiguous()
+
+
+def cosine_fit(y: torch.Tensor, w_deg: torch.Tensor, n, x0: torch.Tensor, xtol: float = 1e-4, ftol: float = 1e-4):
+    """K8: C independent fits of a cos(b radians(w) + c) + d, each scipy's minimize(objective, x0, method='Powell') of
+    TD_Trainer.objective (TD_Trainer.py:37-42,81-88), in one launch.
+
+    y f64[C,ld] the samples and w_deg f64[C,ld] their angles in degrees, row f holding fit f's n[f] values first; n the row counts
+    (a sequence or an integer tensor [C], 1 <= n[f] <= min(64, ld); an int: the same for every fit); x0 f64[C,4] the starts.
+
+    Returns dict(x=f64[C,4] (a, b, c, d), fun=f64[C], nfev=i32[C], nit=i32[C], status=i32[C]); status as tucker_powell's.  A fit's
+    result does not depend on its place in the batch.
+    """
+    y, w_deg = _fit_rows(y, w_deg)
+    _need_cuda(x0, "x0", torch.float64)
+    Cn, ld = y.shape
+    if tuple(x0.shape) != (Cn, 4):
+        raise ValueError(f"x0: expected [{Cn},4], got {tuple(x0.shape)}")
+    if isinstance(n, int):
+        n = [n] * Cn
+    h_n = torch.as_tensor(n.detach().cpu() if torch.is_tensor(n) else list(n)).to(torch.int32).contiguous()
+    if tuple(h_n.shape) != (Cn,):
+        raise ValueError(f"n: expected {Cn} row counts, got shape {tuple(h_n.shape)}")
+    if Cn and (int(h_n.min()) < 1 or int(h_n.max()) > min(_lib.COSINE_FIT_ROWS_MAX, ld)):
+        raise ValueError(f"n: every row count must be in [1, min({_lib.COSINE_FIT_ROWS_MAX}, ld = {ld})], got {int(h_n.min())}..{int(h_n.max())}")
+    dev = y.device
+    x0 = x0.contiguous()
+    d_n = h_n.to(dev)
+    res = torch.empty((Cn, 4), dtype=torch.float64, device=dev)
+    fun = torch.empty((Cn,), dtype=torch.float64, device=dev)
+    nfev = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    nit = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    status = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    with _on_device_of(("y", y), ("w_deg", w_deg), ("x0", x0)) as stream:
+        _lib.check(_lib.lib().nlml_cosine_fit(y.data_ptr(), w_deg.data_ptr(), ld, d_n.data_ptr(), h_n.data_ptr(), Cn, x0.data_ptr(),
+                                              float(xtol), float(ftol), res.data_ptr(), fun.data_ptr(), nfev.data_ptr(), nit.data_ptr(),
+                                              status.data_ptr(), stream), "nlml_cosine_fit")
+    return {"x": res, "fun": fun, "nfev": nfev, "nit": nit, "status": status}
+
+
+def cosine_fit_objective(y: torch.Tensor, w_deg: torch.Tensor, n, params: torch.Tensor, fit: int = 0) -> torch.Tensor:
+    """The objective K8 minimises, evaluated on the device at params f64[N,4] against the rows of fit `fit` of y / w_deg f64[C,ld]
+    (n as in cosine_fit) -> f64[N]: 1/2 sum_i (y_i - (a cos(b radians(w_i) + c) + d))^2 in the reference's operation order."""
+    y, w_deg = _fit_rows(y, w_deg)
+    _need_cuda(params, "params", torch.float64)
+    if params.dim() != 2 or params.shape[1] != 4:
+        raise ValueError(f"params: expected [N,4], got {tuple(params.shape)}")
+    Cn, ld = y.shape
+    fit = int(fit)
+    if not 0 <= fit < Cn:
+        raise ValueError(f"fit: {fit} outside [0, {Cn})")
+    rows = int(n) if isinstance(n, int) else int(n[fit])
+    if not 1 <= rows <= min(_lib.COSINE_FIT_ROWS_MAX, ld):
+        raise ValueError(f"n: {rows} outside [1, min({_lib.COSINE_FIT_ROWS_MAX}, ld = {ld})]")
+    params = params.contiguous()
+    N = params.shape[0]
+    out = torch.empty((N,), dtype=torch.float64, device=y.device)
+    with _on_device_of(("y", y), ("w_deg", w_deg), ("params", params)) as stream:
+        _lib.check(_lib.lib().nlml_cosine_fit_objective(y[fit].data_ptr(), w_deg[fit].data_ptr(), rows, params.data_ptr(), N,
+                                                        out.data_ptr(), stream), "nlml_cosine_fit_objective")
+    return out
+
+
 # ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------
 _eval_ws: dict = {}
 
@@ -652,7 +721,7 @@ def _load_torch_ops():
     for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
                  "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks", "mode_gram", "pose_grams", "project_identity",
-                 "project_pose"):
+                 "project_pose", "cosine_fit"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
 

@@ -17,8 +17,8 @@ artefacts.core_to_W / nlml_mode5_product where one is wanted.
 Sign convention: each factor column is flipped so that its entry of largest magnitude (the lowest index on a tie) is positive, the
 convention all 14 columns of the shipped Factor_Matrices.npz follow.
 
-``decompose_to_npz`` writes Factor_Matrices.npz only.  Trained_data.npz also needs TD_Trainer's cosine fit of the pose factors,
-which is not part of this module yet (the next step of the TD_main port), so that file is NOT written here.
+``decompose_to_npz`` writes Factor_Matrices.npz only.  ``train_to_npz`` goes on to TD_Trainer's cosine fit of the pose factors (K8)
+and writes Trained_data.npz as well: the two files the TD path loads.
 """
 from __future__ import annotations
 
@@ -228,7 +228,7 @@ def thin_core(W):
 def decompose_to_npz(tensor, config, out_dir, backend="device", **kwargs):
     """Decompose with the ranks of config["tensor_decom_ranks"] (configs/config_TD_main.yaml) and write <out_dir>/Factor_Matrices.npz
     with the reference's keys and dtypes (TD_main.py:261): f32 U_yaw, U_pitch, U_roll, U_id.  Returns (W, factors) as ``tucker``.
-    Trained_data.npz is not written: it also holds TD_Trainer's cosine fit, which this package does not compute yet."""
+    Trained_data.npz is not written: it also holds TD_Trainer's cosine fit; train_to_npz runs that and writes both files."""
     r = config["tensor_decom_ranks"]
     rank = [r["R_identity"], r["R_yaw"], r["R_pitch"], r["R_roll"], r["R_features"]]
     W, factors = tucker(tensor, rank, backend=backend, **kwargs)
@@ -236,3 +236,39 @@ def decompose_to_npz(tensor, config, out_dir, backend="device", **kwargs):
     os.makedirs(out_dir, exist_ok=True)
     np.savez(os.path.join(out_dir, "Factor_Matrices.npz"), U_yaw=host[1], U_pitch=host[2], U_roll=host[3], U_id=host[0])
     return W, factors
+
+
+def _bins(spec):
+    """The angle bins of a configuration entry {min_bin, max_bin, interval} as TD_main.py builds them: np.arange(min, max, interval)."""
+    return np.arange(spec["min_bin"], spec["max_bin"], spec["interval"])
+
+
+def train_to_npz(tensor, config, out_dir, backend="device", **kwargs):
+    """The training chain behind the tensor (TD_main.py:181-262): decompose with the ranks of config["tensor_decom_ranks"], fit the
+    three pose factors' cosines over the bins of config["yaw_bins"], ["pitch_bins"], ["roll_bins"] (TD_Trainer.Train, K8) and write
+    BOTH artefacts to out_dir with the reference's keys and dtypes:
+
+      Factor_Matrices.npz   f32 U_yaw, U_pitch, U_roll, U_id                      (as decompose_to_npz)
+      Trained_data.npz      f64 optimized_yaw, optimized_pitch, optimized_roll [R_pose,4]; f32 W [R,ry,rp,rr,M]; f32 CoreTensor
+
+    The fit runs on the f32 factors that are written -- the columns every consumer of the files sees.  CoreTensor is W itself:
+    with rank[4] equal to the feature extent the feature factor is square and orthogonal, any orthogonal U_feat (and the matching
+    core) reproduces the same W, and U_feat = I is the choice that needs no 1404 x 1404 eigenproblem (``thin_core`` gives a thin
+    pair where one is wanted).  No consumer of this package reads CoreTensor for anything but its presence.
+
+    backend "device": K7 and K8 on the GPU;  "numpy": the numpy decomposition and the host form of the fit (no GPU involved).
+    Returns (W, factors, (optimized_yaw, optimized_pitch, optimized_roll))."""
+    from . import TD_Trainer
+
+    bins = [_bins(config[k]) for k in ("yaw_bins", "pitch_bins", "roll_bins")]
+    W, factors = decompose_to_npz(tensor, config, out_dir, backend=backend, **kwargs)
+    fm = np.load(os.path.join(out_dir, "Factor_Matrices.npz"))
+    pairs = [(fm[k], b) for k, b in zip(("U_yaw", "U_pitch", "U_roll"), bins)]
+    for (U, b), name in zip(pairs, ("yaw", "pitch", "roll")):
+        if U.shape[0] != len(b):
+            raise ValueError(f"{name}: the tensor has {U.shape[0]} bins but config[{name}_bins] gives {len(b)}")
+    optimized = TD_Trainer.Train(*pairs, backend="device" if backend == "device" else "host")
+    Wh = np.ascontiguousarray(W.detach().cpu().numpy() if hasattr(W, "detach") else W, dtype=np.float32)
+    np.savez(os.path.join(out_dir, "Trained_data.npz"), optimized_yaw=optimized[0], optimized_pitch=optimized[1],
+             optimized_roll=optimized[2], CoreTensor=Wh, W=Wh)
+    return W, factors, optimized
