@@ -565,21 +565,34 @@ int nlml_mode5_product(const float* core, const float* U_feat, int Q, int R5, in
  * entry point refuses).
  *
  * nlml_mode_gram (K7a)  G f64[I,I] = A A^T on the f64 matrix cores, upper-triangle tiles then mirrored: G is symmetric bit for bit.
- *   1 <= I <= NLML_GRAM_I_MAX, K >= 1.  K is cut into slices of at least NLML_GRAM_KCHUNK columns (more when the tiles
- *   alone fill the device), added in ascending order.
+ *   1 <= I <= NLML_GRAM_I_MAX, K >= 1.  K is cut into slices: with ceil(I / 128) tile rows and as many pairs as their upper
+ *   triangle holds, tiles (tiles + 1) / 2, a slice is ceil(K / max(1, 1024 / pairs)) columns (the inner division rounds down),
+ *   rounded up to a multiple of 32 and at least NLML_GRAM_KCHUNK; there are ceil(K / slice) of them and the workspace holds
+ *   slices x pairs tiles of 128 x 128 f64.  Within a slice an entry is ONE chain fma(A[i][k], A[j][k], acc), k ascending from +0.0;
+ *   the slices are added s = 0.0, s += slice, in ascending order.
  * nlml_pose_grams (K7b)  Gy f64[ny,ny], Gp f64[np,np], Gr f64[nr,nr]: the Grams of the mode-2, -3 and -4 unfoldings in one pass
- *   over X; a NULL output is skipped (at least one must be given).  ny, np, nr in 1..NLML_POSE_BINS_MAX and
- *   ny np nr <= NLML_POSE_GRAMS_MAX_CELLS (all cells by 32 columns stay in LDS).
- * nlml_project_identity (K7c)  out f32[R,K] = U^T A, U f64[I,R], 1 <= R <= NLML_TUCKER_RANK_MAX; i-ascending f64 fma chain, one
- *   rounding to f32.
+ *   over X; a NULL output is skipped (at least one must be given) and changes nothing in the others.  ny, np, nr in
+ *   1..NLML_POSE_BINS_MAX and ny np nr <= NLML_POSE_GRAMS_MAX_CELLS (all cells by 32 columns stay in LDS).  The order: a slab is one
+ *   identity by 32 columns (the last of a row may be short), slab number i ceil(M / 32) + column block; partial b of
+ *   min(slabs, 1024) takes the slabs b, b + partials, ...  For a mode of extent n with O cells outside it and J inside
+ *   (cell = (o n + a) J + j), wave w of 4 takes the pairs (o, j) numbered o J + j = w, w + 4, ... and for each runs the slab's
+ *   columns ascending; an entry of the wave is one fma chain from +0.0 over all of that, slab after slab.  The waves are added
+ *   0.0 + w0 + w1 + w2 + w3, then the partials ascending from 0.0; the upper triangle is computed and mirrored.
+ * nlml_project_identity (K7c)  out f32[R,K] = U^T A, U f64[I,R], 1 <= R <= NLML_TUCKER_RANK_MAX; one chain
+ *   fma(U[i][r], (double)A[i][k], acc) per output, i ascending from +0.0, one rounding to f32.
  * nlml_project_pose (K7d)  out f32[I,ny',np',nr',M] = X x_2 Uy^T x_3 Up^T x_4 Ur^T, Uy f64[ny,ry] etc.; a NULL factor leaves its
  *   mode as it is (n' = n, its rank argument is ignored), else n' = its rank in 1..NLML_POSE_RANK_MAX.  f64 fma chains nested
- *   roll inside pitch inside yaw, each ascending; one rounding to f32.  With all three NULL, out is X copied bit for bit.
+ *   roll inside pitch inside yaw, each ascending from +0.0: tr[c] = fma(Ur[r][c], x, tr[c]) over r, tp[b][c] = fma(Up[p][b], tr[c],
+ *   tp[b][c]) over p, acc[a][b][c] = fma(Uy[y][a], tp[b][c], acc[a][b][c]) over y; a NULL factor's chain has the one step of the
+ *   output's own index with coefficient 1.0; one rounding to f32.  With all three NULL, out is X copied bit for bit.
  *
- * The *_ex forms take or give a tensor in f64 where the flag (a_f64, x_f64, out_f64) is nonzero -- same shapes, same sums, 8-byte
- * alignment, and no rounding of an f64 output.  The decomposition keeps its projected tensors that way between two steps: a factor
- * computed from an f32-rounded projection sits 2^-24 from the exact one, far outside the f64 Grams' own error.  The plain forms are
- * the *_ex forms with every flag 0.  nlml_pose_grams_workspace_bytes serves both element types. */
+ * The *_ex forms take or give a tensor in f64 where the flag (a_f64, x_f64, out_f64) is nonzero -- same shapes, 8-byte alignment,
+ * no rounding of an f64 output, and the sums and orders stated above (on f64 values that f32 holds, the f32 form's bits) -- with one
+ * exception: nlml_pose_grams_ex with x_f64 cuts a row into slabs of 16 columns, not 32, so it has min(I ceil(M / 16), 1024) partials
+ * and groups the columns differently; on inputs that are not exactly summable its bits may differ from the f32 form's.  The
+ * decomposition keeps its projected tensors in f64 between two steps: a factor computed from an f32-rounded projection sits 2^-24
+ * from the exact one, far outside the f64 Grams' own error.  The plain forms are the *_ex forms with every flag 0.
+ * nlml_pose_grams_workspace_bytes serves both element types (it is the f64 form's partial count, never the smaller). */
 #define NLML_GRAM_I_MAX      4096
 #define NLML_GRAM_KCHUNK     4096
 #define NLML_POSE_BINS_MAX        32

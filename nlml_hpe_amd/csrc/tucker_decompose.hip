@@ -22,7 +22,19 @@
 //        contraction nested roll-inside-pitch-inside-yaw so that an element costs rr + rp rr / nr + ry rp rr / (np nr) fma instead of
 //        the ry rp rr of the Kronecker form; ranks are template parameters (<= 3 each), the accumulators registers.
 // The kernels are templates on the tensors' element types: the *_ex entry points take or give f64 where the driver keeps a projected
-// tensor unrounded between two steps (K7a, K7b, K7d in; K7c, K7d out); the sums and their order are the f32 forms'.
+// tensor unrounded between two steps (K7a, K7b, K7d in; K7c, K7d out); the sums and their order are the f32 forms' -- except K7b's,
+// whose f64 slab is 16 columns wide (the same 128 bytes of a row), so that it has other slabs, other partials and, on inputs that
+// are not exactly summable, other bits.
+//
+// The orders, as include/nlml_hpe.h states them and oracle/csrc/oracle.c ("K7") restates them on the host; tests/test_tucker_order_gpu.py
+// holds the kernels to those models bit for bit:
+//   K7a  slice = max(NLML_GRAM_KCHUNK, ceil(K / max(1, 1024 / pairs)) rounded up to 32 columns), pairs = the upper triangle of
+//        ceil(I / 128) tile rows; per slice ONE fma chain per entry, k ascending (the matrix instruction adds its four k in ascending
+//        order to its accumulator, and zero columns past the slice change nothing); slices added ascending from 0.0.
+//   K7b  partial b of min(slabs, 1024) takes slabs b, b + partials, ...; wave w the pairs (o, j) = w, w + 4, ... of each mode's outer
+//        and inner cells, columns ascending inside a pair, one chain per entry over all slabs of the workgroup; then
+//        0.0 + w0 + w1 + w2 + w3 and the partials ascending from 0.0.
+//   K7c  i ascending.     K7d  roll inside pitch inside yaw, each ascending; a kept mode is one step with coefficient 1.0.
 #include <hip/hip_runtime.h>
 
 #include "../../include/nlml_hpe.h"

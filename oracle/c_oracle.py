@@ -128,3 +128,71 @@ def tucker_objective(Wm, x, params, cosp, want_xhat=False, device_order=False, r
     lib().oracle_tucker_objective(_p(Wm), _p(x), _p(params), _p(cosp), C.c_int64(N), _p(err), _p(xh) if want_xhat else None,
                                   C.c_int(int(device_order)))
     return (err, xh) if want_xhat else err
+
+
+# ---- K7: the summation orders of the Tucker decomposition's four primitives (oracle.c, "K7") ----------------------------------------
+def _tensor_in(a):
+    """-> (contiguous array, f64 flag): f64 stays f64 (a projection kept unrounded), anything else is taken as f32."""
+    a = np.asarray(a)
+    a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    return a, int(a.dtype == np.float64)
+
+
+def mode_gram_plan(I: int, K: int):
+    """K7a's slice rule -> (tile pairs, columns per slice, slices)."""
+    v = [C.c_int64() for _ in range(3)]
+    lib().oracle_mode_gram_plan(C.c_int64(I), C.c_int64(K), *[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
+def mode_gram(A, variant=0):
+    """K7a's order: A f32 or f64 [I,K] -> G f64[I,I].  variant != 0: the wrong orders listed at oracle_mode_gram."""
+    A, f64 = _tensor_in(A)
+    I, K = A.shape
+    G = np.empty((I, I))
+    lib().oracle_mode_gram(_p(A), C.c_int(f64), C.c_int64(I), C.c_int64(K), _p(G), C.c_int(int(variant)))
+    return G
+
+
+def pose_grams(X, which=(True, True, True), variant=0):
+    """K7b's order: X f32 or f64 [I,ny,np,nr,M] -> (Gy, Gp, Gr), None where `which` is false; 32-column slabs for f32 input, 16 for
+    f64.  variant != 0: the wrong orders listed at oracle_pose_grams."""
+    X, f64 = _tensor_in(X)
+    I, ny, np_, nr, M = X.shape
+    G = [np.empty((n, n)) if w else None for n, w in zip((ny, np_, nr), which)]
+    lib().oracle_pose_grams(_p(X), C.c_int(f64), C.c_int64(I), C.c_int(ny), C.c_int(np_), C.c_int(nr), C.c_int64(M),
+                            *[_p(g) if g is not None else None for g in G], C.c_int(int(variant)))
+    return tuple(G)
+
+
+def project_identity(A, U, out_dtype=np.float32, variant=0):
+    """K7c's order: A f32[I,K], U f64[I,R] -> U^T A as f32 (one cast) or f64 [R,K].  variant != 0: see oracle_project_identity."""
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    U = np.ascontiguousarray(U, dtype=np.float64)
+    I, K = A.shape
+    if U.ndim != 2 or U.shape[0] != I or not 1 <= U.shape[1] <= 16:
+        raise ValueError(f"U {U.shape}: expected [{I},R] with R in 1..16")
+    out = np.empty((U.shape[1], K), out_dtype)
+    lib().oracle_project_identity(_p(A), C.c_int64(I), C.c_int64(K), _p(U), C.c_int(U.shape[1]), _p(out),
+                                  C.c_int(int(out.dtype == np.float64)), C.c_int(int(variant)))
+    return out
+
+
+def project_pose(X, Uy=None, Up=None, Ur=None, out_dtype=np.float32, variant=0):
+    """K7d's order: X f32 or f64 [I,ny,np,nr,M] contracted with every factor given (f64[n,r], r <= 3; None keeps the mode) -> f32 (one
+    cast) or f64.  variant != 0: see oracle_project_pose."""
+    X, f64 = _tensor_in(X)
+    shape = list(X.shape)
+    Us, args = [], []
+    for k, U in enumerate((Uy, Up, Ur)):
+        if U is not None:
+            U = np.ascontiguousarray(U, dtype=np.float64)
+            if U.ndim != 2 or U.shape[0] != X.shape[1 + k] or not 1 <= U.shape[1] <= 3:
+                raise ValueError(f"factor {k} {U.shape}: expected [{X.shape[1 + k]},r] with r in 1..3")
+            shape[1 + k] = U.shape[1]
+        Us.append(U)
+        args += [_p(U) if U is not None else None, C.c_int(U.shape[1] if U is not None else 0)]
+    out = np.empty(shape, out_dtype)
+    lib().oracle_project_pose(_p(X), C.c_int(f64), C.c_int64(X.shape[0]), C.c_int(X.shape[1]), C.c_int(X.shape[2]), C.c_int(X.shape[3]),
+                              C.c_int64(X.shape[4]), *args, _p(out), C.c_int(int(out.dtype == np.float64)), C.c_int(int(variant)))
+    return out

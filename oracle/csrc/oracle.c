@@ -317,3 +317,234 @@ void oracle_tucker_objective(const float* Wm, const float* x, const double* para
     err[n] = device_order ? residual_device_order(x + n * 1404, accv) : 0.5 * s;   /* :49 */
   }
 }
+
+/* ---- K7: the four primitives of the Tucker decomposition (TD_main.py:181) ------------------
+ * The SUMMATION ORDERS of nlml_mode_gram, nlml_pose_grams, nlml_project_identity and nlml_project_pose, written from the prose of
+ * include/nlml_hpe.h (its K7 paragraph) and of the header comment of nlml_hpe_amd/csrc/tucker_decompose.hip; no kernel header is
+ * included and libm enters through fma alone.  A tensor argument is f32, or f64 where its flag is nonzero.  variant 0 is the order;
+ * the others are deliberately WRONG orders with which tests/test_tucker_order_host.py shows that the inputs of
+ * tests/test_tucker_order_gpu.py tell them apart. */
+static inline double k7_load(const void* p, int f64, int64_t idx) {
+  return f64 ? ((const double*)p)[idx] : (double)((const float*)p)[idx];
+}
+/* one step of a chain: fused, or (the wrong order "multiply and add rounded separately"; -ffp-contract=off) in two roundings */
+static inline double k7_step(double u, double x, double acc, int split) {
+  if (split) { const double t = u * x; return t + acc; }
+  return fma(u, x, acc);
+}
+
+/* K7a's slice rule: ceil(I / 128) tile rows, the pairs of the upper triangle, K cut into max(1, 1024 / pairs) slices at most, a
+ * slice rounded up to 32 columns and never below 4,096. */
+void oracle_mode_gram_plan(int64_t I, int64_t K, int64_t* pairs, int64_t* slice, int64_t* splits) {
+  const int64_t tiles = (I + 127) / 128;
+  *pairs = tiles * (tiles + 1) / 2;
+  const int64_t smax = 1024 / *pairs > 1 ? 1024 / *pairs : 1;
+  int64_t s = (K + smax - 1) / smax;
+  s = (s + 31) / 32 * 32;
+  *slice = s < 4096 ? 4096 : s;
+  *splits = (K + *slice - 1) / *slice;
+}
+
+/* G f64[I,I] = A A^T.  Per slice every entry is one chain fma(A[i][k], A[j][k], acc), k ascending from +0.0 (what the f64 matrix
+ * instruction accumulates over its steps of four k); the slices are added s = 0.0; s += part, ascending; i <= j is computed once and
+ * mirrored.  Wrong orders: 1 k descending inside a slice; 2 multiply and add rounded separately; 3 one chain over the whole K, no
+ * slices; 4 the slices added descending. */
+void oracle_mode_gram(const void* A, int a_f64, int64_t I, int64_t K, double* G, int variant) {
+  int64_t pairs, slice, splits;
+  oracle_mode_gram_plan(I, K, &pairs, &slice, &splits);
+  if (variant == 3) { slice = K; splits = 1; }
+  double* D = (double*)malloc((size_t)I * (size_t)K * sizeof(double));   /* the one conversion per element */
+  for (int64_t e = 0; e < I * K; ++e) D[e] = k7_load(A, a_f64, e);
+#pragma omp parallel for schedule(dynamic)
+  for (int64_t i = 0; i < I; ++i)
+    for (int64_t j = i; j < I; ++j) {
+      const double *a = D + i * K, *b = D + j * K;
+      double s = 0.0;
+      for (int64_t t = 0; t < splits; ++t) {
+        const int64_t sp = variant == 4 ? splits - 1 - t : t;
+        const int64_t kbeg = sp * slice, kend = kbeg + slice < K ? kbeg + slice : K;
+        double acc = 0.0;
+        if (variant == 1)
+          for (int64_t k = kend - 1; k >= kbeg; --k) acc = fma(a[k], b[k], acc);
+        else if (variant == 2)
+          for (int64_t k = kbeg; k < kend; ++k) acc = k7_step(a[k], b[k], acc, 1);
+        else
+          for (int64_t k = kbeg; k < kend; ++k) acc = fma(a[k], b[k], acc);
+        s += acc;
+      }
+      G[i * I + j] = s;
+      G[j * I + i] = s;
+    }
+  free(D);
+}
+
+/* One pose mode's Gram: the mode has extent n, O cells outside it and J inside (cell = (o n + a) J + j).  A slab is one identity by
+ * tc columns; partial b of parts = min(slabs, 1024) takes the slabs b, b + parts, ...; within a slab wave w of 4 takes the (o, j)
+ * pairs w, w + 4, ... (o j = o J + j) and for each runs the slab's columns ascending, one fma chain per entry that goes on over
+ * the wave's pairs and the partial's slabs (the columns beyond M are zero and change nothing).  The four waves are added
+ * 0.0 + w0 + w1 + w2 + w3, then the partials ascending from 0.0; the upper triangle is computed and mirrored. */
+static void k7_pose_gram(const void* X, int x_f64, int64_t I, int cells, int64_t M, int O, int n, int J, int tc, int variant, double* G) {
+  const int64_t mtiles = (M + tc - 1) / tc, slabs = I * mtiles;
+  const int parts = (int)(slabs < 1024 ? slabs : 1024);
+  const int OJ = O * J, quarter = (OJ + 3) / 4;
+  double* part = (double*)malloc((size_t)parts * n * n * sizeof(double));
+#pragma omp parallel for schedule(dynamic)
+  for (int b = 0; b < parts; ++b) {
+    double acc[4][32][32];
+    memset(acc, 0, sizeof acc);
+    for (int w = 0; w < 4; ++w)
+      for (int64_t sl = b; sl < slabs; sl += parts) {
+        const int64_t i = sl / mtiles, m0 = (sl - i * mtiles) * tc;
+        const int first = variant == 1 ? w * quarter : w, step = variant == 1 ? 1 : 4;
+        const int last = variant == 1 ? ((w + 1) * quarter < OJ ? (w + 1) * quarter : OJ) : OJ;
+        for (int oj = first; oj < last; oj += step) {
+          const int o = oj / J, j = oj - o * J;
+          for (int c = 0; c < tc && m0 + c < M; ++c) {
+            double x[32];
+            for (int a = 0; a < n; ++a) x[a] = k7_load(X, x_f64, (i * cells + (int64_t)((o * n + a) * J + j)) * M + m0 + c);
+            for (int a = 0; a < n; ++a)
+              for (int a2 = a; a2 < n; ++a2) acc[w][a][a2] = fma(x[a], x[a2], acc[w][a][a2]);
+          }
+        }
+      }
+    for (int a = 0; a < n; ++a)
+      for (int a2 = a; a2 < n; ++a2) {
+        double s = 0.0;
+        for (int w = 0; w < 4; ++w) s += acc[w][a][a2];
+        part[((size_t)b * n + a) * n + a2] = s;
+      }
+  }
+  for (int a = 0; a < n; ++a)
+    for (int a2 = a; a2 < n; ++a2) {
+      double s = 0.0;
+      for (int t = 0; t < parts; ++t) s += part[((size_t)(variant == 3 ? parts - 1 - t : t) * n + a) * n + a2];
+      G[a * n + a2] = s;
+      G[a2 * n + a] = s;
+    }
+  free(part);
+}
+
+/* Gy f64[ny,ny], Gp f64[np,np], Gr f64[nr,nr] of X [I,ny,np,nr,M]; a NULL output is skipped.  A slab is 32 columns wide for f32
+ * input and 16 for f64 input.  Wrong orders: 1 each wave takes a contiguous quarter of the (o, j) pairs; 2 32-column slabs for
+ * f64 input too; 3 the partials added descending. */
+void oracle_pose_grams(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, double* Gy, double* Gp, double* Gr,
+                       int variant) {
+  const int tc = x_f64 && variant != 2 ? 16 : 32, cells = ny * np * nr;
+  if (Gy) k7_pose_gram(X, x_f64, I, cells, M, 1, ny, np * nr, tc, variant, Gy);
+  if (Gp) k7_pose_gram(X, x_f64, I, cells, M, ny, np, nr, tc, variant, Gp);
+  if (Gr) k7_pose_gram(X, x_f64, I, cells, M, ny * np, nr, 1, tc, variant, Gr);
+}
+
+/* out[r][k] = sum_i U[i][r] A[i][k], A f32[I,K], U f64[I,R], R <= 16: one chain fma(U[i][r], (double)A[i][k], acc), i ascending
+ * from +0.0; an f32 output is that sum cast once.  Wrong orders: 1 i descending; 2 multiply and add rounded separately; 3 U
+ * rounded to f32. */
+void oracle_project_identity(const float* A, int64_t I, int64_t K, const double* U, int R, void* out, int out_f64, int variant) {
+#pragma omp parallel for schedule(static)
+  for (int64_t k = 0; k < K; ++k) {
+    double acc[16];
+    for (int r = 0; r < R; ++r) acc[r] = 0.0;
+    for (int64_t t = 0; t < I; ++t) {
+      const int64_t i = variant == 1 ? I - 1 - t : t;
+      const double x = (double)A[i * K + k];
+      for (int r = 0; r < R; ++r) {
+        const double u = variant == 3 ? (double)(float)U[i * R + r] : U[i * R + r];
+        acc[r] = k7_step(u, x, acc[r], variant == 2);
+      }
+    }
+    for (int r = 0; r < R; ++r) {
+      if (out_f64) ((double*)out)[(int64_t)r * K + k] = acc[r];
+      else ((float*)out)[(int64_t)r * K + k] = (float)acc[r];
+    }
+  }
+}
+
+/* out [I,ny',np',nr',M] = X x_2 Uy^T x_3 Up^T x_4 Ur^T, Uy f64[ny,ry] etc. (ranks <= 3).  Three nested fma chains, each ascending
+ * from +0.0: over roll tr[c] = fma(Ur[r][c], x, tr[c]); over pitch tp[b][c] = fma(Up[p][b], tr[c], tp[b][c]); over yaw
+ * acc[a][b][c] = fma(Uy[y][a], tp[b][c], acc[a][b][c]).  A NULL factor keeps its mode (n' = n): its chain has the one step of the
+ * output's own index, with coefficient 1.0.  An f32 output is the sum cast once.  Wrong orders: 1 every chain descending;
+ * 2 multiply and add rounded separately; 3 the Kronecker form, coefficient (Uy Up) Ur and one chain over (y, p, r); 4 yaw innermost
+ * (yaw inside pitch inside roll). */
+void oracle_project_pose(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
+                         int rp, const double* Ur, int rr, void* out, int out_f64, int variant) {
+  const int RY = Uy ? ry : 1, RP = Up ? rp : 1, RR = Ur ? rr : 1;
+  const int by = Uy ? 1 : ny, bp = Up ? 1 : np, br = Ur ? 1 : nr;
+  const int oy = Uy ? ry : ny, op = Up ? rp : np, orr = Ur ? rr : nr;
+  const int64_t total = I * by * bp * br * M;
+  const int split = variant == 2, desc = variant == 1;
+#pragma omp parallel for schedule(static)
+  for (int64_t idx = 0; idx < total; ++idx) {
+    int64_t q = idx / M;
+    const int64_t m = idx - q * M;
+    const int rb = (int)(q % br); q /= br;
+    const int pb = (int)(q % bp); q /= bp;
+    const int yb = (int)(q % by);
+    const int64_t i = q / by;
+    const int y0 = Uy ? 0 : yb, y1 = Uy ? ny : yb + 1, p0 = Up ? 0 : pb, p1 = Up ? np : pb + 1, r0 = Ur ? 0 : rb, r1 = Ur ? nr : rb + 1;
+    const int64_t xi = i * ny * np * nr * M + m;
+#define K7_X(y, p, r) k7_load(X, x_f64, xi + (int64_t)(((y) * np + (p)) * nr + (r)) * M)
+#define K7_UY(y, a) (Uy ? Uy[(y) * RY + (a)] : 1.0)
+#define K7_UP(p, b) (Up ? Up[(p) * RP + (b)] : 1.0)
+#define K7_UR(r, c) (Ur ? Ur[(r) * RR + (c)] : 1.0)
+    double acc[3][3][3];
+    memset(acc, 0, sizeof acc);
+    if (variant == 3) {
+      for (int y = y0; y < y1; ++y)
+        for (int p = p0; p < p1; ++p)
+          for (int r = r0; r < r1; ++r) {
+            const double x = K7_X(y, p, r);
+            for (int a = 0; a < RY; ++a)
+              for (int b = 0; b < RP; ++b)
+                for (int c = 0; c < RR; ++c) acc[a][b][c] = fma((K7_UY(y, a) * K7_UP(p, b)) * K7_UR(r, c), x, acc[a][b][c]);
+          }
+    } else if (variant == 4) {
+      for (int r = r0; r < r1; ++r) {
+        double tp[3][3];
+        memset(tp, 0, sizeof tp);
+        for (int p = p0; p < p1; ++p) {
+          double ty[3] = {0.0, 0.0, 0.0};
+          for (int y = y0; y < y1; ++y) {
+            const double x = K7_X(y, p, r);
+            for (int a = 0; a < RY; ++a) ty[a] = fma(K7_UY(y, a), x, ty[a]);
+          }
+          for (int a = 0; a < RY; ++a)
+            for (int b = 0; b < RP; ++b) tp[a][b] = fma(K7_UP(p, b), ty[a], tp[a][b]);
+        }
+        for (int a = 0; a < RY; ++a)
+          for (int b = 0; b < RP; ++b)
+            for (int c = 0; c < RR; ++c) acc[a][b][c] = fma(K7_UR(r, c), tp[a][b], acc[a][b][c]);
+      }
+    } else {
+      for (int ty_ = 0; ty_ < y1 - y0; ++ty_) {
+        const int y = desc ? y1 - 1 - ty_ : y0 + ty_;
+        double tp[3][3];
+        memset(tp, 0, sizeof tp);
+        for (int tp_ = 0; tp_ < p1 - p0; ++tp_) {
+          const int p = desc ? p1 - 1 - tp_ : p0 + tp_;
+          double tr[3] = {0.0, 0.0, 0.0};
+          for (int tr_ = 0; tr_ < r1 - r0; ++tr_) {
+            const int r = desc ? r1 - 1 - tr_ : r0 + tr_;
+            const double x = K7_X(y, p, r);
+            for (int c = 0; c < RR; ++c) tr[c] = k7_step(K7_UR(r, c), x, tr[c], split);
+          }
+          for (int b = 0; b < RP; ++b)
+            for (int c = 0; c < RR; ++c) tp[b][c] = k7_step(K7_UP(p, b), tr[c], tp[b][c], split);
+        }
+        for (int a = 0; a < RY; ++a)
+          for (int b = 0; b < RP; ++b)
+            for (int c = 0; c < RR; ++c) acc[a][b][c] = k7_step(K7_UY(y, a), tp[b][c], acc[a][b][c], split);
+      }
+    }
+#undef K7_X
+#undef K7_UY
+#undef K7_UP
+#undef K7_UR
+    const int64_t oi = i * oy * op * orr * M + m;
+    for (int a = 0; a < RY; ++a)
+      for (int b = 0; b < RP; ++b)
+        for (int c = 0; c < RR; ++c) {
+          const int64_t at = oi + (int64_t)(((Uy ? a : yb) * op + (Up ? b : pb)) * orr + (Ur ? c : rb)) * M;
+          if (out_f64) ((double*)out)[at] = acc[a][b][c];
+          else ((float*)out)[at] = (float)acc[a][b][c];
+        }
+  }
+}

@@ -3,7 +3,13 @@
 Exactly summable inputs (integer-valued f32, |a| <= 1024) make every f64 sum exact whatever its order, so the Grams must equal the
 integer Gram bit for bit; random inputs are held to the f64 accumulation bound.  Shapes sit below, at and above every size at which
 the kernels change path: one matrix-core tile (16), one workgroup tile (128), one LDS stage (32 columns), K not a multiple of 4
-(scalar loads), more than one K slice, a partial last slice."""
+(scalar loads), more than one K slice, a partial last slice.
+
+What this file does not reach is in tests/test_tucker_order_gpu.py (inputs in tests/tucker_order_cases.py, their host side in
+tests/test_tucker_order_host.py): exact answers for K7a with three and more tile rows, at NLML_GRAM_I_MAX and with slices longer than
+NLML_GRAM_KCHUNK; for K7b where a workgroup takes several slabs and on its n > 16 branch for every mode; every rank instance of K7c;
+every rank triple, NULL pattern and dtype form of K7d; the scalar-load forms through an unaligned base pointer; and, on random
+inputs, each kernel's summation order bit for bit against the host models of oracle/csrc/oracle.c."""
 import functools
 
 import numpy as np
