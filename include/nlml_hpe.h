@@ -649,6 +649,66 @@ int nlml_cosine_fit_objective(const double* y, const double* w_deg, int n, const
 int nlml_cosine_fit_objective_host(const double* h_y, const double* h_w_deg, int n, const double* h_params, int64_t N,
                                    double* h_out);
 
+/* K9: training steps of the landmark encoder -- the inner loop of the reference's NLML_HPE_EncoderTrainer.train_encoder
+ * (:393-456, the training loop; :463-517, the validation loop) for the encoder K2 runs:
+ *   Linear(F,1024) ReLU Linear(1024,512) ReLU Linear(512,256) ReLU Linear(256,128) ReLU Linear(128,64) Tanh Linear(64,9)
+ * nlml_encoder_train_steps runs ceil(n / batch) consecutive steps; step s takes the batch slots [s batch, min(n, (s + 1) batch)) (the
+ * last batch may be partial) and does, all in f32 on v_mfma_f32_32x32x2_f32 (csrc/encoder_train_ref.h states every operation order):
+ *   forward on the rows x[order[slot]];  t = (t_yaw[labels[row][0]], t_pitch[labels[row][1]], t_roll[labels[row][2]]);
+ *   loss = sum (pred - t)^2 / (3 B) (the reference's three MSELoss means, B the batch's real row count);
+ *   G <- G + grad (zero_grad != 0: G <- grad; the reference never calls zero_grad, so 0 is its behaviour);
+ *   n = ||G||_2 over all twelve tensors (summed in f64), c = min(1, max_norm / (n + 1e-6)), G <- c G IN PLACE (clip_grad_norm_);
+ *   p <- p - lr (G + weight_decay p)  (SGD without momentum; the decay term does not enter G).
+ *   x        f32[N,ldx]   the dataset, row stride ldx >= F elements; offsets are 64-bit
+ *   labels   i32[N,ld_lab]  the rows' (yaw, pitch, roll) bins in the first three columns, ld_lab >= 3
+ *   t_yaw    f32[n_yaw,3], t_pitch f32[n_pitch,3], t_roll f32[n_roll,3]  the target tables (float32(U_yaw) ...)
+ *   params   f32[P]       W0,b0,W1,b1,...,W5,b5 contiguous, W [out,in] row-major: the state dict's tensors are views of it.
+ *                         P = 1024 F + 1024 + 512*1024 + 512 + 256*512 + 256 + 128*256 + 128 + 64*128 + 64 + 9*64 + 9.  Updated in place.
+ *   grads    f32[P]       the gradient accumulator G in the same layout, read and written (zero_grad: only written)
+ *   F        136 or 1404;   batch 1..NLML_ENCODER_TRAIN_BATCH_MAX
+ *   order    i32[n] or NULL (= 0, 1, .., n - 1): the dataset rows in the order they are visited
+ *   lr, weight_decay, max_norm  of this call (one epoch: StepLR changes lr between calls); rounded to f32 as torch rounds them
+ *   loss_out f32[steps], norm_out f32[steps] (n before clipping), either may be NULL;   steps = ceil(n / batch)
+ *   status   i32[1] or NULL: OR of NLML_ENCODER_TRAIN_CLAMPED_ORDER (an order entry outside [0, N)) and
+ *            NLML_ENCODER_TRAIN_CLAMPED_LABEL (a label outside its table), overwritten by the call.  The library never reads device
+ *            memory on the host, so order and labels cannot be checked there: the kernels clamp both into range, read nothing out of
+ *            bounds, and report it here.
+ *   workspace  nlml_encoder_train_workspace_bytes(F, batch) bytes (0 for an F or batch outside the above); contents irrelevant
+ * Every step is fourteen launches ordered by the stream: no atomics, no grid-wide barrier, no host synchronisation, nothing copied to
+ * the host; the same call on the same inputs gives the same bits, and a result does not depend on ldx or on where the rows lie.
+ * nlml_encoder_eval_losses: forward and loss only, batch after batch, the batches' losses to loss_out f32[steps] -- the validation
+ * pass; the forward is the training step's, bit for bit.
+ * The *_host forms run encoder_train_ref.h on HOST buffers in plain C++ (no GPU involved, no workspace).  They are NOT claimed to
+ * return the device's bits: tanhf is ocml's on the device and glibc's on the host.  Every sum that is a chain on the device is an
+ * fmaf chain in the same order on the host.
+ * K9 argument checks, in this order, each NLML_E_BADARG with a message and before any GPU call: F not 136 or 1404; batch outside
+ * 1..256; n < 0; n == 0 returns 0 at once (nothing else is looked at); a NULL required buffer (x, labels, the tables, params, grads
+ * when training, workspace on the device); N outside 1..2^31-1; ld_lab < 3; a table without rows; ldx < F; N ldx or N ld_lab
+ * beyond 64-bit byte offsets; training: lr, weight_decay or max_norm not finite, or max_norm < 0; device: workspace_bytes too
+ * small; params, grads or workspace not 16-byte aligned; any other buffer not 4-byte aligned. */
+#define NLML_ENCODER_TRAIN_BATCH_MAX     256
+#define NLML_ENCODER_TRAIN_CLAMPED_ORDER 1
+#define NLML_ENCODER_TRAIN_CLAMPED_LABEL 2
+size_t nlml_encoder_train_workspace_bytes(int F, int batch);
+int nlml_encoder_train_steps(const float* x, int64_t ldx, int64_t N, const int32_t* labels, int64_t ld_lab, const float* t_yaw,
+                             int n_yaw, const float* t_pitch, int n_pitch, const float* t_roll, int n_roll, float* params,
+                             float* grads, int F, int batch, const int32_t* order, int64_t n, double lr, double weight_decay,
+                             double max_norm, int zero_grad, float* loss_out, float* norm_out, int32_t* status, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int nlml_encoder_eval_losses(const float* x, int64_t ldx, int64_t N, const int32_t* labels, int64_t ld_lab, const float* t_yaw,
+                             int n_yaw, const float* t_pitch, int n_pitch, const float* t_roll, int n_roll, const float* params,
+                             int F, int batch, const int32_t* order, int64_t n, float* loss_out, int32_t* status, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int nlml_encoder_train_steps_host(const float* h_x, int64_t ldx, int64_t N, const int32_t* h_labels, int64_t ld_lab,
+                                  const float* h_t_yaw, int n_yaw, const float* h_t_pitch, int n_pitch, const float* h_t_roll,
+                                  int n_roll, float* h_params, float* h_grads, int F, int batch, const int32_t* h_order, int64_t n,
+                                  double lr, double weight_decay, double max_norm, int zero_grad, float* h_loss_out,
+                                  float* h_norm_out, int32_t* h_status);
+int nlml_encoder_eval_losses_host(const float* h_x, int64_t ldx, int64_t N, const int32_t* h_labels, int64_t ld_lab,
+                                  const float* h_t_yaw, int n_yaw, const float* h_t_pitch, int n_pitch, const float* h_t_roll,
+                                  int n_roll, const float* h_params, int F, int batch, const int32_t* h_order, int64_t n,
+                                  float* h_loss_out, int32_t* h_status);
+
 /* Host-side stepping of the same Powell state machine (no GPU involved): the caller evaluates
  * the objective.  Used to check the restated control flow against scipy on the CPU.
  *   h_state: caller-allocated buffer of nlml_powell_state_bytes() bytes.

@@ -46,6 +46,11 @@ def _td_entries():
 
 _ROT_GRID = ([C.c_void_p, C.c_int64] + [C.c_void_p, C.c_int] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p])
 
+# K9: x, ldx, N, labels, ld_lab, (table, rows) x 3 | F, batch, order, n | lr, weight_decay, max_norm, zero_grad
+_ET_DATA = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p, C.c_int] * 3
+_ET_RUN = [C.c_int, C.c_int, C.c_void_p, C.c_int64]
+_ET_HYPER = [C.c_double, C.c_double, C.c_double, C.c_int]
+
 SYMBOLS = {
     **dict(_k2_forwards()),
     **dict(_td_entries()),
@@ -111,6 +116,14 @@ SYMBOLS = {
                              + [C.c_void_p] * 5),
     "nlml_cosine_fit_objective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "nlml_cosine_fit_objective_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    # K9 (encoder training): the dataset and tables, then params[, grads], F, batch, order, n[, lr, weight_decay, max_norm, zero_grad],
+    # loss_out[, norm_out], status[, workspace, workspace_bytes, stream]
+    "nlml_encoder_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "nlml_encoder_train_steps": (C.c_int, _ET_DATA + [C.c_void_p, C.c_void_p] + _ET_RUN + _ET_HYPER + [C.c_void_p] * 3
+                                 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_encoder_eval_losses": (C.c_int, _ET_DATA + [C.c_void_p] + _ET_RUN + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_encoder_train_steps_host": (C.c_int, _ET_DATA + [C.c_void_p, C.c_void_p] + _ET_RUN + _ET_HYPER + [C.c_void_p] * 3),
+    "nlml_encoder_eval_losses_host": (C.c_int, _ET_DATA + [C.c_void_p] + _ET_RUN + [C.c_void_p] * 2),
     "nlml_powell_state_bytes": (C.c_size_t, []),
     "nlml_powell_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "nlml_powell_step": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
@@ -144,6 +157,9 @@ POSE_BINS_MAX = 32                 # NLML_POSE_BINS_MAX
 POSE_GRAMS_MAX_CELLS = 768         # NLML_POSE_GRAMS_MAX_CELLS
 POSE_RANK_MAX = 3                  # NLML_POSE_RANK_MAX
 COSINE_FIT_ROWS_MAX = 64          # NLML_COSINE_FIT_ROWS_MAX
+ENCODER_TRAIN_BATCH_MAX = 256      # NLML_ENCODER_TRAIN_BATCH_MAX
+ENCODER_TRAIN_CLAMPED_ORDER = 1    # NLML_ENCODER_TRAIN_CLAMPED_ORDER
+ENCODER_TRAIN_CLAMPED_LABEL = 2    # NLML_ENCODER_TRAIN_CLAMPED_LABEL
 POSE_EVAL_MAX_INTERVALS = 64       # NLML_POSE_EVAL_MAX_INTERVALS
 POSE_EVAL_FACES_PER_RECORD = 2048  # NLML_POSE_EVAL_FACES_PER_RECORD
 

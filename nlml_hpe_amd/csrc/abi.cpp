@@ -5,6 +5,7 @@
 // state beyond values read once and kept (the NLML_K2_* environment variables, a device's compute-unit count).
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +15,7 @@
 #include "abi_internal.h"
 #include "centroid_ref.h"
 #include "cosine_fit_ref.h"
+#include "encoder_train_ref.h"
 #include "layout.h"
 #include "powell.h"
 #include "rotate_ref.h"
@@ -725,6 +727,107 @@ int nlml_cosine_fit_objective_host(const double* h_y, const double* h_w_deg, int
   bool run;
   if (int rc = check_cosine_objective("cosine_fit_objective_host", !h_y || !h_w_deg || !h_params || !h_out, n, N, &run)) return rc;
   for (int64_t e = 0; run && e < N; ++e) h_out[e] = cf_objective(h_y, h_w_deg, n, h_params + e * CF_NPAR);
+  return 0;
+}
+
+// ---- K9: training steps of the landmark encoder (encoder_train_ref.h, encoder_train.hip) --------------------------------------
+static_assert(ET_BATCH_MAX == NLML_ENCODER_TRAIN_BATCH_MAX && ET_STATUS_ORDER == NLML_ENCODER_TRAIN_CLAMPED_ORDER &&
+              ET_STATUS_LABEL == NLML_ENCODER_TRAIN_CLAMPED_LABEL, "the header's constants are the kernels'");
+// The checks of include/nlml_hpe.h ("K9 argument checks") in their stated order, shared by the four forms: train (grads wanted) or
+// validation, device (workspace, alignment) or host.  -> 0 with *run = whether there is anything to do.
+static int check_encoder_train(const char* who, bool train, bool device, const EtCall& c, const void* workspace, size_t workspace_bytes,
+                               double lr, double weight_decay, bool* run) {
+  *run = false;
+  if (c.F != 136 && c.F != NLML_F_REFERENCE) return refuse(NLML_E_BADARG, who, "F = %d: expected 136 or %d", c.F, NLML_F_REFERENCE);
+  if (c.batch < 1 || c.batch > NLML_ENCODER_TRAIN_BATCH_MAX)
+    return refuse(NLML_E_BADARG, who, "batch = %d outside [1, %d]", c.batch, NLML_ENCODER_TRAIN_BATCH_MAX);
+  if (c.n < 0) return refuse(NLML_E_BADARG, who, "negative n");
+  if (c.n == 0) return 0;
+  if (!c.x || !c.labels || !c.table[0] || !c.table[1] || !c.table[2] || !c.params || (train && !c.grads) || (device && !workspace))
+    return refuse(NLML_E_BADARG, who, "null buffer");
+  if (c.N < 1 || c.N > (int64_t)INT32_MAX) return refuse(NLML_E_BADARG, who, "N = %lld outside [1, 2^31 - 1]", (long long)c.N);
+  if (c.ld_lab < 3) return refuse(NLML_E_BADARG, who, "ld_lab = %lld < 3", (long long)c.ld_lab);
+  for (int t = 0; t < 3; ++t)
+    if (c.rows[t] < 1) return refuse(NLML_E_BADARG, who, "target table %d has %d rows", t, c.rows[t]);
+  if (c.ldx < c.F) return refuse(NLML_E_BADARG, who, "ldx = %lld < F = %d", (long long)c.ldx, c.F);
+  if (c.ldx > INT64_MAX / 4 / c.N || c.ld_lab > INT64_MAX / 4 / c.N)
+    return refuse(NLML_E_BADARG, who, "dataset too large for 64-bit byte offsets");
+  if (train && !(std::isfinite(lr) && std::isfinite(weight_decay) && std::isfinite(c.max_norm) && c.max_norm >= 0.0))
+    return refuse(NLML_E_BADARG, who, "lr, weight_decay and max_norm must be finite, max_norm not negative");
+  if (device) {
+    const size_t need = et_workspace(c.F, c.batch).bytes;
+    if (workspace_bytes < need) return refuse(NLML_E_BADARG, who, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (!aligned(c.params, 16) || !aligned(c.grads, 16) || !aligned(workspace, 16))
+      return refuse(NLML_E_BADARG, who, "params, grads and workspace must be 16-byte aligned");
+    if (!aligned(c.x, 4) || !aligned(c.labels, 4) || !aligned(c.table[0], 4) || !aligned(c.table[1], 4) || !aligned(c.table[2], 4) ||
+        !aligned(c.order, 4) || !aligned(c.loss_out, 4) || !aligned(c.norm_out, 4) || !aligned(c.status, 4))
+      return refuse(NLML_E_BADARG, who, "f32 and i32 buffers must be 4-byte aligned");
+  }
+  *run = true;
+  return 0;
+}
+static EtCall encoder_call(const float* x, int64_t ldx, int64_t N, const int32_t* labels, int64_t ld_lab, const float* t_yaw, int n_yaw,
+                           const float* t_pitch, int n_pitch, const float* t_roll, int n_roll, float* params, float* grads, int F, int batch,
+                           const int32_t* order, int64_t n, double lr, double weight_decay, double max_norm, int zero_grad, float* loss_out,
+                           float* norm_out, int32_t* status) {
+  EtCall c;
+  c.x = x; c.ldx = ldx; c.N = N; c.labels = labels; c.ld_lab = ld_lab;
+  c.table[0] = t_yaw; c.table[1] = t_pitch; c.table[2] = t_roll;
+  c.rows[0] = n_yaw; c.rows[1] = n_pitch; c.rows[2] = n_roll;
+  c.params = params; c.grads = grads; c.F = F; c.batch = batch; c.order = order; c.n = n;
+  c.lr = (float)lr; c.wd = (float)weight_decay; c.max_norm = max_norm; c.zero_grad = zero_grad ? 1 : 0;
+  c.loss_out = loss_out; c.norm_out = norm_out; c.status = status;
+  return c;
+}
+
+size_t nlml_encoder_train_workspace_bytes(int F, int batch) {
+  if ((F != 136 && F != NLML_F_REFERENCE) || batch < 1 || batch > NLML_ENCODER_TRAIN_BATCH_MAX) return 0;
+  return et_workspace(F, batch).bytes;
+}
+
+int nlml_encoder_train_steps(const float* x, int64_t ldx, int64_t N, const int32_t* labels, int64_t ld_lab, const float* t_yaw, int n_yaw,
+                             const float* t_pitch, int n_pitch, const float* t_roll, int n_roll, float* params, float* grads, int F,
+                             int batch, const int32_t* order, int64_t n, double lr, double weight_decay, double max_norm, int zero_grad,
+                             float* loss_out, float* norm_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  const EtCall c = encoder_call(x, ldx, N, labels, ld_lab, t_yaw, n_yaw, t_pitch, n_pitch, t_roll, n_roll, params, grads, F, batch, order, n,
+                                lr, weight_decay, max_norm, zero_grad, loss_out, norm_out, status);
+  bool run;
+  if (int rc = check_encoder_train("encoder_train_steps", true, true, c, workspace, workspace_bytes, lr, weight_decay, &run)) return rc;
+  return run ? launch_encoder_train(c, workspace, stream) : 0;
+}
+
+int nlml_encoder_eval_losses(const float* x, int64_t ldx, int64_t N, const int32_t* labels, int64_t ld_lab, const float* t_yaw, int n_yaw,
+                             const float* t_pitch, int n_pitch, const float* t_roll, int n_roll, const float* params, int F, int batch,
+                             const int32_t* order, int64_t n, float* loss_out, int32_t* status, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  const EtCall c = encoder_call(x, ldx, N, labels, ld_lab, t_yaw, n_yaw, t_pitch, n_pitch, t_roll, n_roll, const_cast<float*>(params), nullptr,
+                                F, batch, order, n, 0.0, 0.0, 0.0, 0, loss_out, nullptr, status);
+  bool run;
+  if (int rc = check_encoder_train("encoder_eval_losses", false, true, c, workspace, workspace_bytes, 0.0, 0.0, &run)) return rc;
+  return run ? launch_encoder_train(c, workspace, stream) : 0;
+}
+
+// the same order (encoder_train_ref.h) on host buffers: plain C++, no HIP call
+int nlml_encoder_train_steps_host(const float* h_x, int64_t ldx, int64_t N, const int32_t* h_labels, int64_t ld_lab, const float* h_t_yaw,
+                                  int n_yaw, const float* h_t_pitch, int n_pitch, const float* h_t_roll, int n_roll, float* h_params,
+                                  float* h_grads, int F, int batch, const int32_t* h_order, int64_t n, double lr, double weight_decay,
+                                  double max_norm, int zero_grad, float* h_loss_out, float* h_norm_out, int32_t* h_status) {
+  const EtCall c = encoder_call(h_x, ldx, N, h_labels, ld_lab, h_t_yaw, n_yaw, h_t_pitch, n_pitch, h_t_roll, n_roll, h_params, h_grads, F, batch,
+                                h_order, n, lr, weight_decay, max_norm, zero_grad, h_loss_out, h_norm_out, h_status);
+  bool run;
+  if (int rc = check_encoder_train("encoder_train_steps_host", true, false, c, nullptr, 0, lr, weight_decay, &run)) return rc;
+  if (run) et_host_run(c);
+  return 0;
+}
+
+int nlml_encoder_eval_losses_host(const float* h_x, int64_t ldx, int64_t N, const int32_t* h_labels, int64_t ld_lab, const float* h_t_yaw,
+                                  int n_yaw, const float* h_t_pitch, int n_pitch, const float* h_t_roll, int n_roll, const float* h_params,
+                                  int F, int batch, const int32_t* h_order, int64_t n, float* h_loss_out, int32_t* h_status) {
+  const EtCall c = encoder_call(h_x, ldx, N, h_labels, ld_lab, h_t_yaw, n_yaw, h_t_pitch, n_pitch, h_t_roll, n_roll,
+                                const_cast<float*>(h_params), nullptr, F, batch, h_order, n, 0.0, 0.0, 0.0, 0, h_loss_out, nullptr, h_status);
+  bool run;
+  if (int rc = check_encoder_train("encoder_eval_losses_host", false, false, c, nullptr, 0, 0.0, 0.0, &run)) return rc;
+  if (run) et_host_run(c);
   return 0;
 }
 

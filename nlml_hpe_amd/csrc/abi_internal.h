@@ -144,6 +144,11 @@ int launch_cosine_fit(const double* y, const double* w_deg, int64_t ld, const in
                       double ftol, double* x, double* fun, int32_t* nfev, int32_t* nit, int32_t* status, void* stream);
 int launch_cosine_fit_objective(const double* y, const double* w_deg, int n, const double* params, int64_t N, double* out, void* stream);
 
+// encoder_train.hip (K9): ceil(n / batch) training steps (c.grads == NULL: forward and loss only), all enqueued on the stream.  The
+// call is checked by the caller (abi.cpp); EtCall is encoder_train_ref.h's.
+struct EtCall;
+int launch_encoder_train(const EtCall& c, void* workspace, void* stream);
+
 // video_post.hip
 int launch_video_post(const float* pose_rad, const float* raw, const uint8_t* valid, int64_t S, double frame_w,
                       double frame_h, double alpha, double max_jump, double size, double* state, double* smoothed,

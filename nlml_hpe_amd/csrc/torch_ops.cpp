@@ -358,6 +358,59 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> cosine_fi
   return {res, fun, nfev, nit, status};
 }
 
+// K9: ceil(n / batch) training steps of the encoder, params and grads f32[P] updated in place.  x f32[N,>=F] with unit column stride
+// (a padded row stride is passed on as ldx), labels i32[N,>=3], the tables f32[.,3], order i32[n] or None (the rows in turn)
+// -> (loss f32[steps], norm f32[steps], status i32[1]); the workspace comes from torch's allocator
+std::tuple<at::Tensor, at::Tensor, at::Tensor> encoder_train_steps(const at::Tensor& x, const at::Tensor& labels_, const at::Tensor& ty_,
+                                                                   const at::Tensor& tp_, const at::Tensor& tr_, at::Tensor params,
+                                                                   at::Tensor grads, const std::optional<at::Tensor>& order_, int64_t n,
+                                                                   int64_t batch, double lr, double weight_decay, double max_norm,
+                                                                   bool zero_grad) {
+  need(x, "x", at::kFloat);
+  need(labels_, "labels", at::kInt);
+  need(ty_, "t_yaw", at::kFloat);
+  need(tp_, "t_pitch", at::kFloat);
+  need(tr_, "t_roll", at::kFloat);
+  need(params, "params", at::kFloat);
+  need(grads, "grads", at::kFloat);
+  need_dense(params, "params");
+  need_dense(grads, "grads");
+  const at::Tensor* operands[] = {&labels_, &ty_, &tp_, &tr_, &params, &grads};
+  for (const at::Tensor* t : operands) same_device(x, *t, "an operand");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && (x.size(1) == 136 || x.size(1) == F_REF) && x.stride(1) == 1 && x.stride(0) >= x.size(1),
+              "x: expected [N,136] or [N,1404] with unit column stride, got ", x.sizes(), " strides ", x.strides());
+  const int64_t N = x.size(0), F = x.size(1);
+  TORCH_CHECK(labels_.dim() == 2 && labels_.size(0) == N && labels_.size(1) >= 3, "labels: expected [", N, ",>=3], got ", labels_.sizes());
+  for (const at::Tensor* t : {&ty_, &tp_, &tr_})
+    TORCH_CHECK(t->dim() == 2 && t->size(0) >= 1 && t->size(1) == 3, "a target table: expected [rows,3], got ", t->sizes());
+  TORCH_CHECK(batch >= 1 && batch <= NLML_ENCODER_TRAIN_BATCH_MAX, "batch = ", batch, " outside [1, ", NLML_ENCODER_TRAIN_BATCH_MAX, "]");
+  TORCH_CHECK(n >= 0, "negative n");
+  const at::Tensor labels = labels_.contiguous(), ty = ty_.contiguous(), tp = tp_.contiguous(), tr = tr_.contiguous();
+  const size_t ws_bytes = nlml_encoder_train_workspace_bytes((int)F, (int)batch);
+  // P from the workspace-independent rule of the header
+  const int64_t P = 1024 * F + 1024 + 512 * 1024 + 512 + 256 * 512 + 256 + 128 * 256 + 128 + 64 * 128 + 64 + 9 * 64 + 9;
+  TORCH_CHECK(params.numel() == P && grads.numel() == P, "params and grads: expected ", P, " elements each, got ", params.numel(), ", ", grads.numel());
+  at::Tensor order;
+  if (order_.has_value()) {
+    need(*order_, "order", at::kInt);
+    same_device(x, *order_, "order");
+    TORCH_CHECK(order_->dim() == 1 && order_->size(0) >= n, "order: expected at least n = ", n, " entries, got ", order_->sizes());
+    order = order_->contiguous();
+  }
+  const int64_t steps = (n + batch - 1) / batch;
+  const auto f32 = x.options(), i32 = x.options().dtype(at::kInt);
+  at::Tensor loss = at::empty({steps}, f32), norm = at::empty({steps}, f32), status = at::zeros({1}, i32);
+  at::Tensor ws = at::empty({(int64_t)ws_bytes}, x.options().dtype(at::kByte));
+  OnDevice dev(x);
+  check(nlml_encoder_train_steps(x.data_ptr<float>(), x.stride(0), N, labels.data_ptr<int32_t>(), labels.size(1), ty.data_ptr<float>(),
+                                 (int)ty.size(0), tp.data_ptr<float>(), (int)tp.size(0), tr.data_ptr<float>(), (int)tr.size(0),
+                                 params.data_ptr<float>(), grads.data_ptr<float>(), (int)F, (int)batch,
+                                 order.defined() ? order.data_ptr<int32_t>() : nullptr, n, lr, weight_decay, max_norm, zero_grad ? 1 : 0,
+                                 loss.data_ptr<float>(), norm.data_ptr<float>(), status.data_ptr<int32_t>(), ws.data_ptr(), ws_bytes,
+                                 dev.stream), "nlml_encoder_train_steps");
+  return {loss, norm, status};
+}
+
 // K5: the evaluation block in one native pass.  pose f32[B,3] radians or f64[B,3] degrees (by dtype), valid bool/u8[B] or None,
 // gt f64[B,3]; lo / hi the inclusive GT range, intervals [K*2] (low, high) with their axes [K]; the records' workspace comes from
 // torch's allocator -> (record f64[12+2K], result f64[14+2K])
@@ -534,6 +587,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> cosine_fi
   const auto i32 = y.options().dtype(at::kInt);
   return {at::empty({C, 4}, y.options()), at::empty({C}, y.options()), at::empty({C}, i32), at::empty({C}, i32), at::empty({C}, i32)};
 }
+std::tuple<at::Tensor, at::Tensor, at::Tensor> encoder_train_steps_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                                                                        const at::Tensor&, at::Tensor, at::Tensor, const std::optional<at::Tensor>&,
+                                                                        int64_t n, int64_t batch, double, double, double, bool) {
+  const int64_t steps = batch > 0 ? (n + batch - 1) / batch : 0;
+  return {at::empty({steps}, x.options()), at::empty({steps}, x.options()), at::empty({1}, x.options().dtype(at::kInt))};
+}
 at::Tensor cosine_table_meta(const at::Tensor& angles, const at::Tensor& cosp) { return at::empty({angles.size(0), cosp.size(0)}, cosp.options()); }
 
 std::tuple<at::Tensor, at::Tensor> pose_eval_meta(const at::Tensor& pose, const std::optional<at::Tensor>&, const at::Tensor& gt,
@@ -566,6 +625,8 @@ TORCH_LIBRARY(nlml_hpe, m) {
         "Tensor(a!) state, Tensor(b!) smoothed, Tensor(c!) centre, Tensor(d!) endpoints, Tensor(e!) updated) -> ()");
   m.def("cosine_table(Tensor angles_rad, Tensor cos_params) -> Tensor");
   m.def("cosine_fit(Tensor y, Tensor w_deg, int[] n, Tensor x0, float xtol=1e-4, float ftol=1e-4) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("encoder_train_steps(Tensor x, Tensor labels, Tensor t_yaw, Tensor t_pitch, Tensor t_roll, Tensor(a!) params, Tensor(b!) grads, "
+        "Tensor? order, int n, int batch, float lr, float weight_decay, float max_norm, bool zero_grad) -> (Tensor, Tensor, Tensor)");
   m.def("pose_eval(Tensor pose, Tensor? valid, Tensor gt, float[] lo, float[] hi, int decimals, float[] intervals, int[] axes) "
         "-> (Tensor, Tensor)");
   m.def("pose_eval_merge(Tensor records, int K) -> (Tensor, Tensor)");
@@ -591,6 +652,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
   m.impl("video_post", &video_post);
   m.impl("cosine_table", &cosine_table);
   m.impl("cosine_fit", &cosine_fit);
+  m.impl("encoder_train_steps", &encoder_train_steps);
   m.impl("pose_eval", &pose_eval);
   m.impl("pose_eval_merge", &pose_eval_merge);
   m.impl("mode_gram", &mode_gram);
@@ -615,6 +677,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("video_post", &video_post_meta);
   m.impl("cosine_table", &cosine_table_meta);
   m.impl("cosine_fit", &cosine_fit_meta);
+  m.impl("encoder_train_steps", &encoder_train_steps_meta);
   m.impl("pose_eval", &pose_eval_meta);
   m.impl("pose_eval_merge", &pose_eval_merge_meta);
   m.impl("mode_gram", &mode_gram_meta);

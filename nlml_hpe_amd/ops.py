@@ -614,6 +614,122 @@ def cosine_fit_objective(y: torch.Tensor, w_deg: torch.Tensor, n, params: torch.
     return out
 
 
+# ---- K9: training steps of the encoder (csrc/encoder_train.hip; the driver is nlml_hpe_amd/EncoderTrainer.py) ------------------
+def encoder_param_count(F: int) -> int:
+    """Elements of the contiguous params / grads buffers W0,b0,...,W5,b5 for input width F."""
+    total, fan_in = 0, int(F)
+    for w in (1024, 512, 256, 128, 64, LATENT):
+        total += w * fan_in + w
+        fan_in = w
+    return total
+
+
+def encoder_param_views(buf, F: int) -> dict:
+    """The state dict `encoder.{0,2,..,10}.{weight,bias}` as VIEWS of a contiguous params (or grads) buffer."""
+    from .EncoderTrainer import state_dict_views
+    return state_dict_views(buf, F)
+
+
+def _encoder_dataset(x, labels, tables, params, order, n, batch):
+    _need_cuda(x, "x", torch.float32)
+    _need_cuda(labels, "labels", torch.int32)
+    _need_cuda(params, "params", torch.float32)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] not in (136, F_REF) or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        raise ValueError(f"x: expected [N,136] or [N,1404] with unit column stride, got {tuple(x.shape)} strides {x.stride()}")
+    N, F = x.shape
+    if labels.dim() != 2 or labels.shape[0] != N or labels.shape[1] < 3:
+        raise ValueError(f"labels: expected [{N},>=3], got {tuple(labels.shape)}")
+    if len(tables) != 3:
+        raise ValueError("tables: expected (t_yaw, t_pitch, t_roll)")
+    tables = list(tables)
+    for k, t in enumerate(tables):
+        _need_cuda(t, "a target table", torch.float32)
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != 3:
+            raise ValueError(f"a target table: expected [rows,3], got {tuple(t.shape)}")
+        tables[k] = t.contiguous()
+    if not params.is_contiguous() or params.numel() != encoder_param_count(F):
+        raise ValueError(f"params: expected a contiguous buffer of {encoder_param_count(F)} elements, got {tuple(params.shape)}")
+    batch = int(batch)
+    if not 1 <= batch <= _lib.ENCODER_TRAIN_BATCH_MAX:
+        raise ValueError(f"batch = {batch} outside [1, {_lib.ENCODER_TRAIN_BATCH_MAX}]")
+    if order is not None:
+        _need_cuda(order, "order", torch.int32)
+        if order.dim() != 1:
+            raise ValueError(f"order: expected a vector, got {tuple(order.shape)}")
+        order = order.contiguous()
+        n = order.shape[0] if n is None else int(n)
+        if n > order.shape[0]:
+            raise ValueError(f"n = {n} beyond the {order.shape[0]} entries of order")
+    else:
+        n = N if n is None else int(n)
+        if n > N:
+            raise ValueError(f"n = {n} beyond the {N} rows of x")
+    if n < 0:
+        raise ValueError("negative n")
+    return labels.contiguous(), tables, order, n, batch, N, F
+
+
+def _encoder_workspace(F, batch, workspace, device):
+    need = _lib.lib().nlml_encoder_train_workspace_bytes(F, batch)
+    if workspace is None:
+        return torch.empty((need,), dtype=torch.uint8, device=device)
+    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"workspace: expected a contiguous GPU buffer of at least {need} bytes")
+    return workspace
+
+
+def _table_args(tables):
+    return [v for t in tables for v in (t.data_ptr(), t.shape[0])]
+
+
+def encoder_train_steps(x, labels, tables, params, grads, order=None, n=None, batch=256, lr=1e-4, weight_decay=1e-5, max_norm=20.0,
+                        zero_grad=False, workspace=None):
+    """K9: ceil(n / batch) consecutive training steps of the encoder (NLML_HPE_EncoderTrainer.py:400-454) enqueued without a
+    synchronisation: forward, the three-MSE loss, backward into the persistent accumulator `grads` (the reference never calls
+    zero_grad; zero_grad=True overwrites it instead), clip_grad_norm_(max_norm) in place, SGD with weight decay.
+
+    x f32[N,F] (F 136 or 1404; a padded row stride is fine), labels i32[N,>=3], tables (t_yaw, t_pitch, t_roll) f32[.,3],
+    params / grads contiguous f32[encoder_param_count(F)] updated IN PLACE (encoder_param_views gives the state dict),
+    order i32[n] the rows in visiting order (None: 0..n-1).
+    -> (loss f32[steps], norm f32[steps] before clipping, status i32[1]: _lib.ENCODER_TRAIN_CLAMPED_* bits) on the device."""
+    labels, tables, order, n, batch, N, F = _encoder_dataset(x, labels, tables, params, order, n, batch)
+    _need_cuda(grads, "grads", torch.float32)
+    if not grads.is_contiguous() or grads.numel() != params.numel():
+        raise ValueError(f"grads: expected a contiguous buffer of {params.numel()} elements, got {tuple(grads.shape)}")
+    dev = x.device
+    steps = (n + batch - 1) // batch
+    loss = torch.empty((steps,), dtype=torch.float32, device=dev)
+    norm = torch.empty((steps,), dtype=torch.float32, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ws = _encoder_workspace(F, batch, workspace, dev)
+    with _on_device_of(("x", x), ("labels", labels), ("t_yaw", tables[0]), ("t_pitch", tables[1]), ("t_roll", tables[2]), ("params", params),
+                       ("grads", grads), ("order", order), ("workspace", ws)) as stream:
+        _lib.check(_lib.lib().nlml_encoder_train_steps(
+            x.data_ptr(), x.stride(0), N, labels.data_ptr(), labels.shape[1], *_table_args(tables), params.data_ptr(), grads.data_ptr(), F,
+            batch, order.data_ptr() if order is not None else None, n, float(lr), float(weight_decay), float(max_norm), int(bool(zero_grad)),
+            loss.data_ptr(), norm.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), stream),
+            "nlml_encoder_train_steps")
+    return loss, norm, status
+
+
+def encoder_eval_losses(x, labels, tables, params, order=None, n=None, batch=256, workspace=None):
+    """The validation pass of K9: forward and loss only, batch after batch -> (loss f32[steps], status i32[1]) on the device.  The
+    forward is the training step's, bit for bit."""
+    labels, tables, order, n, batch, N, F = _encoder_dataset(x, labels, tables, params, order, n, batch)
+    dev = x.device
+    steps = (n + batch - 1) // batch
+    loss = torch.empty((steps,), dtype=torch.float32, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ws = _encoder_workspace(F, batch, workspace, dev)
+    with _on_device_of(("x", x), ("labels", labels), ("t_yaw", tables[0]), ("t_pitch", tables[1]), ("t_roll", tables[2]), ("params", params),
+                       ("order", order), ("workspace", ws)) as stream:
+        _lib.check(_lib.lib().nlml_encoder_eval_losses(
+            x.data_ptr(), x.stride(0), N, labels.data_ptr(), labels.shape[1], *_table_args(tables), params.data_ptr(), F, batch,
+            order.data_ptr() if order is not None else None, n, loss.data_ptr(), status.data_ptr(), ws.data_ptr(),
+            ws.numel() * ws.element_size(), stream), "nlml_encoder_eval_losses")
+    return loss, status
+
+
 # ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------
 _eval_ws: dict = {}
 
@@ -721,7 +837,7 @@ def _load_torch_ops():
     for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
                  "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks", "mode_gram", "pose_grams", "project_identity",
-                 "project_pose", "cosine_fit"):
+                 "project_pose", "cosine_fit", "encoder_train_steps"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
 
