@@ -31,7 +31,10 @@
 //
 // The host form (et_host_*, below; nlml_encoder_train_steps_host) runs this order in plain C++.  It is NOT claimed to return the
 // device's bits: tanhf is ocml's on the device and glibc's on the host, and a skipped k >= K differs from fmaf(0, 0, p) in the sign
-// of a zero.
+// of a zero.  The device IS held to this prose bit for bit, launch by launch: the C oracle restates the order apart from this file
+// (oracle/csrc/oracle.c "K9", k >= K as a zero operand), tests/test_encoder_train_order_host.py holds that model to the host form's
+// values, to float64 and to deliberately wrong orders, and tests/test_encoder_train_order_gpu.py holds every launch of a step to it on
+// the device's own inputs (A_5 alone to 5 ulp of float64 tanh).
 #pragma once
 #include <math.h>
 #include <stddef.h>

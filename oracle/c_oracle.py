@@ -196,3 +196,120 @@ def project_pose(X, Uy=None, Up=None, Ur=None, out_dtype=np.float32, variant=0):
     lib().oracle_project_pose(_p(X), C.c_int(f64), C.c_int64(X.shape[0]), C.c_int(X.shape[1]), C.c_int(X.shape[2]), C.c_int(X.shape[3]),
                               C.c_int64(X.shape[4]), *args, _p(out), C.c_int(int(out.dtype == np.float64)), C.c_int(int(variant)))
     return out
+
+
+# ---- K9: the operation orders of one encoder-training step, launch by launch (oracle.c, "K9") ---------------------------------------
+def _f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _operand(a, rows):
+    """A 2-D f32 array whose rows may be strided (the columns are not) -> (array kept alive, ld in floats, rows i32 or None)."""
+    a = np.asarray(a)
+    if a.dtype != np.float32 or a.ndim != 2 or (a.shape[1] > 1 and a.strides[1] != 4) or a.strides[0] % 4:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    rows = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+    return a, a.strides[0] // 4, rows
+
+
+def et_gemm(A, B, K, start=None, a_kc=True, b_kc=False, a_rows=None, b_rows=None, M=None, N=None, variant=0):
+    """K9's GEMM order (oracle_et_gemm) -> C f32[M,N] = sum_k a(m,k) b(k,n).  A: [M,>=K] k-contiguous or (a_kc False) [>=K,M] k-outer;
+    B: [N,>=K] k-contiguous (b_kc) or [>=K,N] k-outer.  a_rows / b_rows gather the storage row of their operand (M or N must then be
+    given for a k-contiguous one).  start f32[N]: wave 0's start.  variant != 0: the wrong orders listed at the C section."""
+    A, lda, a_rows = _operand(A, a_rows)
+    B, ldb, b_rows = _operand(B, b_rows)
+    M = M if M is not None else (A.shape[0] if a_kc else A.shape[1])
+    N = N if N is not None else (B.shape[0] if b_kc else B.shape[1])
+    for name, arr, kc, rows, n in (("A", A, a_kc, a_rows, M), ("B", B, b_kc, b_rows, N)):
+        vec, red = (arr.shape[0], arr.shape[1]) if kc else (arr.shape[1], arr.shape[0])
+        idx = rows if rows is not None else None
+        if kc:
+            ok = red >= K and (idx is None and vec >= n or idx is not None and len(idx) >= n and idx[:n].min() >= 0 and idx[:n].max() < vec)
+        else:
+            ok = vec >= n and (idx is None and red >= K or idx is not None and len(idx) >= K and idx[:K].min() >= 0 and idx[:K].max() < red)
+        if not ok:
+            raise ValueError(f"et_gemm: operand {name} {arr.shape} does not cover {n} x {K}")
+    if start is not None:
+        start = _f32(start)
+        if start.shape != (N,):
+            raise ValueError("et_gemm: start: expected [N]")
+    out = np.empty((M, N), np.float32)
+    lib().oracle_et_gemm(_p(A), C.c_int64(lda), C.c_int(int(a_kc)), _p(a_rows) if a_rows is not None else None, _p(B), C.c_int64(ldb),
+                         C.c_int(int(b_kc)), _p(b_rows) if b_rows is not None else None, _p(start) if start is not None else None,
+                         C.c_int(M), C.c_int(N), C.c_int(K), _p(out), C.c_int64(N), C.c_int(int(variant)))
+    return out
+
+
+def et_bias_grad(delta, variant=0):
+    """delta f32[B,out] -> db f32[out] in K9's sixteen runs of ceil(B/16) rows."""
+    delta, ldd, _ = _operand(delta, None)
+    out = np.empty(delta.shape[1], np.float32)
+    lib().oracle_et_bias_grad(_p(delta), C.c_int64(ldd), C.c_int(delta.shape[0]), C.c_int(delta.shape[1]), _p(out), C.c_int(int(variant)))
+    return out
+
+
+def et_loss(pred, target, variant=0):
+    """pred f32[B,9] (rows may be strided), target f32[B,9] -> dict(q [B], slots [256] after the tree, loss f32 scalar, delta6 [B,9])."""
+    pred, ldp, _ = _operand(pred, None)
+    target = _f32(target)
+    B = pred.shape[0]
+    if pred.shape[1] != 9 or target.shape != (B, 9) or not 1 <= B <= 256:
+        raise ValueError("et_loss: expected pred and target [B,9] with B in 1..256")
+    q, slots, loss, d6 = np.empty(B, np.float32), np.empty(256, np.float32), np.empty(1, np.float32), np.empty((B, 9), np.float32)
+    lib().oracle_et_loss(_p(pred), C.c_int64(ldp), _p(target), C.c_int(B), _p(q), _p(slots), _p(loss), _p(d6), C.c_int(int(variant)))
+    return {"q": q, "slots": slots, "loss": loss[0], "delta6": d6}
+
+
+def et_n_partials(F):
+    return int(lib().oracle_et_n_partials(C.c_int(F)))
+
+
+def et_norm(F, G=None, partials=None, max_norm=20.0, variant=0):
+    """K9's f64 norm of the flat accumulator G f32[params], or from given tile partials f64[n_partials] ->
+    dict(partials, chains [512], tree [512] after the tree, norm f64, c f64)."""
+    n = et_n_partials(F)
+    if (G is None) == (partials is None):
+        raise ValueError("et_norm: give G or partials")
+    if G is not None:
+        G = _f32(G).ravel()
+        fan_in, total = F, 0
+        for w in (1024, 512, 256, 128, 64, 9):
+            total, fan_in = total + w * fan_in + w, w
+        if G.shape != (total,):
+            raise ValueError(f"et_norm: G: expected {total} elements")
+    else:
+        partials = np.ascontiguousarray(partials, dtype=np.float64)
+        if partials.shape != (n,):
+            raise ValueError(f"et_norm: partials: expected [{n}]")
+    out, chains, tree = np.empty(n), np.empty(512), np.empty(512)
+    norm, c = C.c_double(), C.c_double()
+    lib().oracle_et_norm(_p(G) if G is not None else None, C.c_int(F), _p(partials) if partials is not None else None, C.c_double(max_norm),
+                         _p(out), _p(chains), _p(tree), C.byref(norm), C.byref(c), C.c_int(int(variant)))
+    return {"partials": out, "chains": chains, "tree": tree, "norm": norm.value, "c": c.value}
+
+
+def et_update(p, g, c, lr, wd, variant=0):
+    """-> (p_new, g_new) f32 of K9's update; c, lr, wd are rounded to f32 as the entry point's arguments are."""
+    p, g = _f32(p).copy(), _f32(g).copy()
+    if p.shape != g.shape:
+        raise ValueError("et_update: p and g differ in shape")
+    lib().oracle_et_update(_p(p), _p(g), C.c_int64(p.size), C.c_float(c), C.c_float(lr), C.c_float(wd), C.c_int(int(variant)))
+    return p, g
+
+
+def et_act_grad(s, a, tanh_layer):
+    """s * act'(a) element by element (ReLU, or the tanh layer's fmaf(-a, a, 1))."""
+    s, a = _f32(s), _f32(a)
+    if s.shape != a.shape:
+        raise ValueError("et_act_grad: s and a differ in shape")
+    out = np.empty_like(s)
+    lib().oracle_et_act_grad(_p(s), _p(a), C.c_int64(s.size), C.c_int(int(tanh_layer)), _p(out))
+    return out
+
+
+def et_tanhf(z):
+    """This machine's libm tanhf (the host form's layer 4)."""
+    z = _f32(z)
+    out = np.empty_like(z)
+    lib().oracle_et_tanhf(_p(z), C.c_int64(z.size), _p(out))
+    return out

@@ -548,3 +548,241 @@ void oracle_project_pose(const void* X, int x_f64, int64_t I, int ny, int np, in
         }
   }
 }
+
+/* ---- K9: one training step of the landmark encoder, launch by launch ------------------------
+ * The OPERATION ORDERS of nlml_encoder_train_steps, written from the prose at the top of nlml_hpe_amd/csrc/encoder_train_ref.h
+ * ("THE GEMM ORDER", "THE OTHER SUMS"); no kernel header is included, nothing is shared with that file's et_host_* functions, and
+ * libm enters through fmaf, fma, sqrt and (oracle_et_tanhf alone) tanhf.  Unlike the host form an index k >= K is NOT skipped: it is
+ * a +0 operand of an fmaf, as on the matrix core, so the sign of a zero is the device's.  (A row or a column of a tile beyond the
+ * matrix is such an operand too; its chains end in elements nobody stores, so the model does not form them.)  variant 0 is the
+ * order; the others are deliberately WRONG orders with which tests/test_encoder_train_order_host.py shows that the inputs of
+ * tests/test_encoder_train_order_gpu.py tell them apart:
+ *   1 natural k order inside a super-chunk          5 bias runs of a fixed 16 rows
+ *   2 the wave partials added as a halving tree     6 the loss tree over B slots instead of 256
+ *   3 spw = floor(nsc / 8), the rest on wave 7      7 a tile's norm partial accumulated in f32
+ *   4 the start vector added after the wave sum     8 the update with c g contracted into the following fmaf
+ * A function ignores the variants that are not its own. */
+enum { ET9_WAVES = 8, ET9_SUPER = 16, ET9_TILE = 32, ET9_THREADS = 512, ET9_RUNS = 16, ET9_LOSS_SLOTS = 256, ET9_LATENT = 9 };
+static const int et9_widths[6] = {1024, 512, 256, 128, 64, 9};
+
+static inline int64_t et9_row(const int32_t* rows, int64_t r) { return rows ? (int64_t)rows[r] : r; }
+
+/* C[m][n] (row stride ldc) = sum_k a(m, k) b(k, n), M x N x K.  An operand is k-contiguous (kc != 0: a(m, k) = A[row(m) lda + k],
+ * b(k, n) = Bm[row(n) ldb + k]) or k-outer (a(m, k) = A[row(k) lda + m], b(k, n) = Bm[row(k) ldb + n]); row(r) = rows ? rows[r] : r
+ * gathers the STORAGE row.  start [N] or NULL: wave 0 begins its chain of column n from start[n] instead of +0.
+ * The order: k is cut into nsc = ceil(K / 16) super-chunks; wave w of 8 owns [w spw, (w + 1) spw) cut at nsc, spw = ceil(nsc / 8);
+ * inside super-chunk s it visits k = 16 s + 8 u + 4 h + j for u = 0, 1; j = 0..3; h = 0, 1 (h innermost) as p = fmaf(a, b, p); a wave
+ * without super-chunks keeps its start; the element is ((p_0 + p_1) + p_2) + ... + p_7. */
+void oracle_et_gemm(const float* A, int64_t lda, int a_kc, const int32_t* a_rows, const float* Bm, int64_t ldb, int b_kc,
+                    const int32_t* b_rows, const float* start, int M, int N, int K, float* C, int64_t ldc, int variant) {
+  const int nsc = (K + ET9_SUPER - 1) / ET9_SUPER;
+  const int spw = variant == 3 ? nsc / ET9_WAVES : (nsc + ET9_WAVES - 1) / ET9_WAVES;
+  const int Kp = ET9_SUPER * nsc;
+  int* ks = (int*)malloc((size_t)(Kp + 1) * sizeof(int));
+  int wbeg[ET9_WAVES + 1], cnt = 0;
+  for (int w = 0; w < ET9_WAVES; ++w) {
+    const int s0 = w * spw < nsc ? w * spw : nsc;
+    int s1 = s0 + spw < nsc ? s0 + spw : nsc;
+    if (variant == 3 && w == ET9_WAVES - 1) s1 = nsc;
+    wbeg[w] = cnt;
+    for (int s = s0; s < s1; ++s) {
+      if (variant == 1) {
+        for (int i = 0; i < ET9_SUPER; ++i) ks[cnt++] = ET9_SUPER * s + i;
+      } else {
+        for (int u = 0; u < 2; ++u)
+          for (int j = 0; j < 4; ++j)
+            for (int h = 0; h < 2; ++h) ks[cnt++] = ET9_SUPER * s + 8 * u + 4 * h + j;
+      }
+    }
+  }
+  wbeg[ET9_WAVES] = cnt;
+  /* both operands in visiting order, one vector per output row / column; k >= K stays the +0.0f of calloc */
+  float* Pa = (float*)calloc((size_t)M * (size_t)(cnt + 1), sizeof(float));
+  float* Pb = (float*)calloc((size_t)N * (size_t)(cnt + 1), sizeof(float));
+  for (int m = 0; m < M; ++m)
+    for (int i = 0; i < cnt; ++i) {
+      const int k = ks[i];
+      if (k < K) Pa[(size_t)m * cnt + i] = a_kc ? A[et9_row(a_rows, m) * lda + k] : A[et9_row(a_rows, k) * lda + m];
+    }
+  for (int n = 0; n < N; ++n)
+    for (int i = 0; i < cnt; ++i) {
+      const int k = ks[i];
+      if (k < K) Pb[(size_t)n * cnt + i] = b_kc ? Bm[et9_row(b_rows, n) * ldb + k] : Bm[et9_row(b_rows, k) * ldb + n];
+    }
+#pragma omp parallel for schedule(static)
+  for (int64_t e = 0; e < (int64_t)M * N; ++e) {
+    const int m = (int)(e / N), n = (int)(e % N);
+    const float *a = Pa + (size_t)m * cnt, *b = Pb + (size_t)n * cnt;
+    float p[ET9_WAVES];
+    for (int w = 0; w < ET9_WAVES; ++w) {
+      float acc = (w == 0 && start && variant != 4) ? start[n] : 0.0f;
+      for (int i = wbeg[w]; i < wbeg[w + 1]; ++i) acc = fmaf(a[i], b[i], acc);
+      p[w] = acc;
+    }
+    float t;
+    if (variant == 2) {
+      for (int stride = ET9_WAVES / 2; stride >= 1; stride /= 2)
+        for (int w = 0; w < stride; ++w) p[w] = p[w] + p[w + stride];
+      t = p[0];
+    } else {
+      t = p[0];
+      for (int w = 1; w < ET9_WAVES; ++w) t = t + p[w];
+    }
+    if (variant == 4 && start) t = t + start[n];
+    C[(int64_t)m * ldc + n] = t;
+  }
+  free(Pa);
+  free(Pb);
+  free(ks);
+}
+
+/* db[o] of delta [B, out] (row stride ldd): sixteen runs of ceil(B / 16) rows, a run summed b ascending from +0, the runs added in
+ * order beginning with run 0 (the runs beyond the batch are +0). */
+void oracle_et_bias_grad(const float* delta, int64_t ldd, int B, int out, float* db, int variant) {
+  const int rp = variant == 5 ? 16 : (B + ET9_RUNS - 1) / ET9_RUNS;
+  for (int o = 0; o < out; ++o) {
+    float run[ET9_RUNS];
+    for (int r = 0; r < ET9_RUNS; ++r) {
+      float s = 0.0f;
+      const int hi = (r + 1) * rp < B ? (r + 1) * rp : B;
+      for (int b = r * rp; b < hi; ++b) s = s + delta[(int64_t)b * ldd + o];
+      run[r] = s;
+    }
+    float total = run[0];
+    for (int r = 1; r < ET9_RUNS; ++r) total = total + run[r];
+    db[o] = total;
+  }
+}
+
+/* pred [B, 9] (row stride ldp) against target [B, 9] (tight): q[b] = the fmaf chain of the nine squared residuals, j ascending from
+ * +0; slots [256]: q then zeros, after the halving tree (slot t += slot t + stride; stride 128, 64, .., 1), so slots[0] is the total;
+ * *loss = total / float(3B); delta6 [B, 9] (tight) = residual * float(2 / (3B)). */
+void oracle_et_loss(const float* pred, int64_t ldp, const float* target, int B, float* q, float* slots, float* loss, float* delta6,
+                    int variant) {
+  const float scale = (float)(2.0 / (3.0 * (double)B));
+  for (int t = 0; t < ET9_LOSS_SLOTS; ++t) slots[t] = 0.0f;
+  for (int b = 0; b < B; ++b) {
+    float s = 0.0f;
+    for (int j = 0; j < ET9_LATENT; ++j) {
+      const float d = pred[(int64_t)b * ldp + j] - target[b * ET9_LATENT + j];
+      delta6[b * ET9_LATENT + j] = d * scale;
+      s = fmaf(d, d, s);
+    }
+    q[b] = s;
+    slots[b] = s;
+  }
+  if (variant == 6) {   /* a tree over the B slots in use: the upper half folded onto the lower until one is left */
+    for (int n = B; n > 1;) {
+      const int half = (n + 1) / 2;
+      for (int t = 0; t + half < n; ++t) slots[t] = slots[t] + slots[t + half];
+      n = half;
+    }
+  } else {
+    for (int stride = ET9_LOSS_SLOTS / 2; stride >= 1; stride /= 2)
+      for (int t = 0; t < stride; ++t) slots[t] = slots[t] + slots[t + stride];
+  }
+  *loss = slots[0] / (float)(3 * B);
+}
+
+/* the number of wgrad tiles (= norm partials) of an encoder with F inputs */
+int oracle_et_n_partials(int F) {
+  int n = 0, fan_in = F;
+  for (int l = 0; l < 6; ++l) {
+    n += ((et9_widths[l] + ET9_TILE - 1) / ET9_TILE) * ((fan_in + ET9_TILE - 1) / ET9_TILE);
+    fan_in = et9_widths[l];
+  }
+  return n;
+}
+
+static double et9_tree512(double* s) {
+  for (int stride = ET9_THREADS / 2; stride >= 1; stride /= 2)
+    for (int t = 0; t < stride; ++t) s[t] = s[t] + s[t + stride];
+  return s[0];
+}
+
+/* The norm of the accumulator G (the flat gradient buffer: W_0 [1024, F], b_0, W_1 [512, 1024], b_1, ...), f64.
+ * G != NULL: partials [n_partials] are formed from it -- layer 0's 32 x 32 tiles first, row-major within a layer; thread t of 512
+ * takes elements t and t + 512 of its tile (element e = row e / 32, column e % 32; those beyond the matrix are skipped) as
+ * s = fma(g, g, s) from +0, thread o < 32 of a tile in the first tile column then the bias gradient of the tile's row o, and a
+ * halving tree over the 512 slots gives the partial.  G == NULL: the partials are taken from partials_in.
+ * Then chains [512]: chain t = partials t, t + 512, .. added ascending from +0; tree [512]: the chains after the same halving tree;
+ * *norm = sqrt(tree[0]); *c = min(1, max_norm / (norm + 1e-6)). */
+void oracle_et_norm(const float* G, int F, const double* partials_in, double max_norm, double* partials, double* chains, double* tree,
+                    double* norm, double* c, int variant) {
+  const int n_partials = oracle_et_n_partials(F);
+  if (G) {
+    int fan_in = F, part = 0;
+    int64_t off = 0;
+    for (int l = 0; l < 6; ++l) {
+      const int out = et9_widths[l], in = fan_in;
+      const float *gW = G + off, *gb = G + off + (int64_t)out * in;
+      const int tn_n = (in + ET9_TILE - 1) / ET9_TILE;
+      for (int tm = 0; tm < (out + ET9_TILE - 1) / ET9_TILE; ++tm)
+        for (int tn = 0; tn < tn_n; ++tn) {
+          double s[ET9_THREADS];
+          float sf[ET9_THREADS];
+          for (int t = 0; t < ET9_THREADS; ++t) {
+            double acc = 0.0;
+            float accf = 0.0f;
+            for (int half = 0; half < 2; ++half) {
+              const int e = t + ET9_THREADS * half;
+              const int o = tm * ET9_TILE + e / ET9_TILE, i = tn * ET9_TILE + e % ET9_TILE;
+              if (o >= out || i >= in) continue;
+              const float g = gW[(int64_t)o * in + i];
+              acc = fma((double)g, (double)g, acc);
+              accf = fmaf(g, g, accf);
+            }
+            if (tn == 0 && t < ET9_TILE && tm * ET9_TILE + t < out) {
+              const float g = gb[tm * ET9_TILE + t];
+              acc = fma((double)g, (double)g, acc);
+              accf = fmaf(g, g, accf);
+            }
+            s[t] = acc;
+            sf[t] = accf;
+          }
+          if (variant == 7) {
+            for (int stride = ET9_THREADS / 2; stride >= 1; stride /= 2)
+              for (int t = 0; t < stride; ++t) sf[t] = sf[t] + sf[t + stride];
+            partials[part++] = (double)sf[0];
+          } else {
+            partials[part++] = et9_tree512(s);
+          }
+        }
+      off += (int64_t)out * in + out;
+      fan_in = out;
+    }
+  } else {
+    for (int i = 0; i < n_partials; ++i) partials[i] = partials_in[i];
+  }
+  for (int t = 0; t < ET9_THREADS; ++t) {
+    double s = 0.0;
+    for (int i = t; i < n_partials; i += ET9_THREADS) s = s + partials[i];
+    chains[t] = s;
+    tree[t] = s;
+  }
+  et9_tree512(tree);
+  *norm = sqrt(tree[0]);
+  const double r = max_norm / (*norm + 1e-6);
+  *c = r < 1.0 ? r : 1.0;
+}
+
+/* n elements in place: g <- c g (one rounding); d = fmaf(wd, p, g); p <- fmaf(-lr, d, p) */
+void oracle_et_update(float* p, float* g, int64_t n, float c, float lr, float wd, int variant) {
+  for (int64_t e = 0; e < n; ++e) {
+    const float gc = c * g[e];
+    float d = fmaf(wd, p[e], gc);
+    if (variant == 8) { const float t = wd * p[e]; d = fmaf(c, g[e], t); }   /* c g never rounded on its way into d */
+    g[e] = gc;
+    p[e] = fmaf(-lr, d, p[e]);
+  }
+}
+
+/* out = s * act'(a), element by element: ReLU (a > 0 ? 1 : 0) or, tanh_layer != 0, fmaf(-a, a, 1) */
+void oracle_et_act_grad(const float* s, const float* a, int64_t n, int tanh_layer, float* out) {
+  for (int64_t e = 0; e < n; ++e) out[e] = s[e] * (tanh_layer ? fmaf(-a[e], a[e], 1.0f) : (a[e] > 0.0f ? 1.0f : 0.0f));
+}
+
+/* this machine's libm tanhf: the host form's layer 4, NOT the device's */
+void oracle_et_tanhf(const float* z, int64_t n, float* out) {
+  for (int64_t e = 0; e < n; ++e) out[e] = tanhf(z[e]);
+}
