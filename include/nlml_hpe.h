@@ -709,6 +709,64 @@ int nlml_encoder_eval_losses_host(const float* h_x, int64_t ldx, int64_t N, cons
                                   int n_roll, const float* h_params, int F, int batch, const int32_t* h_order, int64_t n,
                                   float* h_loss_out, int32_t* h_status);
 
+/* K10: training steps of the yaw, pitch and roll heads -- the inner loop of the reference's NLML_HPE_MLPHeadsTrainer.train_network
+ * (:89-113) for up to three INDEPENDENT networks at once, each
+ *   Linear(R,128) ReLU Linear(128,256) ReLU Linear(256,128) ReLU Linear(128,64) ReLU Linear(64,1)
+ * on the rows of a cosine table (nlml_cosine_table, cast to f32) with the angle in radians as the target.  Every network of a call has
+ * its own data, parameters, Adam state, visiting order and row count (one nlml_heads_net each) and shares every launch with the
+ * others: the call runs max_i ceil(n_i / batch) steps, network i takes part in the first ceil(n_i / batch) of them, and afterwards
+ * nothing of it is read or written and its Adam step count stays.  A step of a network on its batch of B rows (the last may be
+ * partial), all in f32 on v_mfma_f32_32x32x2_f32 (csrc/heads_train_ref.h states every operation order):
+ *   forward on the rows x[order[slot]];  loss = sum (pred - y)^2 / B  (MSELoss);  G <- grad (the reference's zero_grad);
+ *   n = ||G||_2 over the ten tensors (summed in f64), c = min(1, max_norm / (n + 1e-6)), G <- c G in place (clip_grad_norm_);
+ *   Adam with betas 0.9 / 0.999, eps 1e-8 and weight_decay added to the gradient (L2, not AdamW), in torch's single-tensor order, every
+ *   operation rounded on its own; the step count t of the bias corrections is step0 + (the network's steps in this call so far) + 1.
+ *     x        f32[N,ldx]  the network's table, row stride ldx >= R;   y  f32[N]  its targets
+ *     params, grads, m, v  f32[P] each, W0,b0,...,W4,b4 contiguous, W [out,in] row-major: the state dict's tensors are views of
+ *              params; P = 128 R + 128 + 256*128 + 256 + 128*256 + 128 + 64*128 + 64 + 64 + 1 (74,753 at R = 3).  params, m and v are
+ *              updated in place, grads is overwritten (the clipped gradient of the network's last step).  The evaluation pass reads
+ *              params only; grads, m and v may be NULL there.
+ *     order    i32[n] or NULL (= 0, 1, .., n - 1);   n >= 1 rows are visited
+ *     step0    Adam steps the network has taken before this call (the caller carries it: step0 += ceil(n / batch))
+ *     loss_out f32[ceil(n / batch)], norm_out f32[ceil(n / batch)] (n before clipping), either may be NULL
+ *     status   i32[1] or NULL: NLML_HEADS_TRAIN_CLAMPED_ORDER if an order entry lay outside [0, N) (it is clamped into range, nothing
+ *              is read out of bounds), overwritten by the call
+ *   R 1..NLML_HEADS_TRAIN_R_MAX, the same for all networks of a call;  batch 1..NLML_ENCODER_TRAIN_BATCH_MAX;  lr of this call (StepLR
+ *   changes it between calls)
+ *   workspace  nlml_heads_train_workspace_bytes(R, batch, n_nets) bytes (0 for an argument outside the above), contents irrelevant.
+ *              Network i owns the i-th n_nets-th of it; inside, in this order and each padded to 16 bytes: the norm partials f64[78],
+ *              the batch's resolved rows i32[256], A_1..A_5 f32[batch,out_l], delta_1..delta_5 f32[batch,out_l] -- the network's last
+ *              step.  No other word of it is written.
+ * Every step is twelve launches ordered by the stream: no atomics, no grid-wide barrier, no host synchronisation, nothing copied to
+ * the host.  nlml_heads_eval_losses: forward and loss only -- the validation pass; the forward is the training step's, bit for bit.
+ * The *_host forms run heads_train_ref.h on HOST buffers in plain C++ (no GPU involved) and return the device's bits, word for
+ * word; h_workspace may be NULL, or a host buffer that receives what the device's workspace would hold.
+ * K10 argument checks, in this order, each NLML_E_BADARG with a message and before any GPU call: n_nets outside 1..3; R outside 1..16;
+ * batch outside 1..256; a NULL required pointer (nets; x, y, params of a network; grads, m, v when training; workspace on the
+ * device); n <= 0 of a network; workspace_bytes too small; step0 < 0; N outside 1..2^31-1; ldx < R or N ldx beyond 64-bit byte
+ * offsets; training: lr, weight_decay or max_norm not finite, or max_norm < 0; device: params, grads, m, v or workspace not 16-byte
+ * aligned, any other buffer not 4-byte aligned. */
+#define NLML_HEADS_TRAIN_NETS_MAX      3
+#define NLML_HEADS_TRAIN_R_MAX         16
+#define NLML_HEADS_TRAIN_CLAMPED_ORDER 1
+typedef struct nlml_heads_net {
+  const float* x; int64_t ldx; int64_t N;
+  const float* y;
+  float* params; float* grads; float* m; float* v;
+  const int32_t* order; int64_t n;
+  int64_t step0;
+  float* loss_out; float* norm_out; int32_t* status;
+} nlml_heads_net;
+size_t nlml_heads_train_workspace_bytes(int R, int batch, int n_nets);
+int nlml_heads_train_steps(const nlml_heads_net* nets, int n_nets, int R, int batch, double lr, double weight_decay, double max_norm,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int nlml_heads_eval_losses(const nlml_heads_net* nets, int n_nets, int R, int batch, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int nlml_heads_train_steps_host(const nlml_heads_net* h_nets, int n_nets, int R, int batch, double lr, double weight_decay,
+                                double max_norm, void* h_workspace, size_t workspace_bytes);
+int nlml_heads_eval_losses_host(const nlml_heads_net* h_nets, int n_nets, int R, int batch, void* h_workspace,
+                                size_t workspace_bytes);
+
 /* Host-side stepping of the same Powell state machine (no GPU involved): the caller evaluates
  * the objective.  Used to check the restated control flow against scipy on the CPU.
  *   h_state: caller-allocated buffer of nlml_powell_state_bytes() bytes.

@@ -51,6 +51,18 @@ _ET_DATA = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void
 _ET_RUN = [C.c_int, C.c_int, C.c_void_p, C.c_int64]
 _ET_HYPER = [C.c_double, C.c_double, C.c_double, C.c_int]
 
+
+
+class HeadsNet(C.Structure):
+    """nlml_heads_net: one network of a K10 call (include/nlml_hpe.h)."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("N", C.c_int64), ("y", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
+                ("m", C.c_void_p), ("v", C.c_void_p), ("order", C.c_void_p), ("n", C.c_int64), ("step0", C.c_int64),
+                ("loss_out", C.c_void_p), ("norm_out", C.c_void_p), ("status", C.c_void_p)]
+
+
+# K10: nets, n_nets, R, batch[, lr, weight_decay, max_norm], workspace, workspace_bytes[, stream]
+_HT_CALL = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+
 SYMBOLS = {
     **dict(_k2_forwards()),
     **dict(_td_entries()),
@@ -124,6 +136,11 @@ SYMBOLS = {
     "nlml_encoder_eval_losses": (C.c_int, _ET_DATA + [C.c_void_p] + _ET_RUN + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "nlml_encoder_train_steps_host": (C.c_int, _ET_DATA + [C.c_void_p, C.c_void_p] + _ET_RUN + _ET_HYPER + [C.c_void_p] * 3),
     "nlml_encoder_eval_losses_host": (C.c_int, _ET_DATA + [C.c_void_p] + _ET_RUN + [C.c_void_p] * 2),
+    "nlml_heads_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nlml_heads_train_steps": (C.c_int, _HT_CALL + [C.c_double] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_heads_eval_losses": (C.c_int, _HT_CALL + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nlml_heads_train_steps_host": (C.c_int, _HT_CALL + [C.c_double] * 3 + [C.c_void_p, C.c_size_t]),
+    "nlml_heads_eval_losses_host": (C.c_int, _HT_CALL + [C.c_void_p, C.c_size_t]),
     "nlml_powell_state_bytes": (C.c_size_t, []),
     "nlml_powell_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "nlml_powell_step": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
@@ -160,6 +177,10 @@ COSINE_FIT_ROWS_MAX = 64          # NLML_COSINE_FIT_ROWS_MAX
 ENCODER_TRAIN_BATCH_MAX = 256      # NLML_ENCODER_TRAIN_BATCH_MAX
 ENCODER_TRAIN_CLAMPED_ORDER = 1    # NLML_ENCODER_TRAIN_CLAMPED_ORDER
 ENCODER_TRAIN_CLAMPED_LABEL = 2    # NLML_ENCODER_TRAIN_CLAMPED_LABEL
+HEADS_TRAIN_NETS_MAX = 3           # NLML_HEADS_TRAIN_NETS_MAX
+HEADS_TRAIN_R_MAX = 16             # NLML_HEADS_TRAIN_R_MAX
+HEADS_TRAIN_CLAMPED_ORDER = 1      # NLML_HEADS_TRAIN_CLAMPED_ORDER
+HEADS_WIDTHS = (128, 256, 128, 64, 1)
 POSE_EVAL_MAX_INTERVALS = 64       # NLML_POSE_EVAL_MAX_INTERVALS
 POSE_EVAL_FACES_PER_RECORD = 2048  # NLML_POSE_EVAL_FACES_PER_RECORD
 

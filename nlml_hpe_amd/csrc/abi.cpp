@@ -16,6 +16,7 @@
 #include "centroid_ref.h"
 #include "cosine_fit_ref.h"
 #include "encoder_train_ref.h"
+#include "heads_train_ref.h"
 #include "layout.h"
 #include "powell.h"
 #include "rotate_ref.h"
@@ -828,6 +829,104 @@ int nlml_encoder_eval_losses_host(const float* h_x, int64_t ldx, int64_t N, cons
   bool run;
   if (int rc = check_encoder_train("encoder_eval_losses_host", false, false, c, nullptr, 0, 0.0, 0.0, &run)) return rc;
   if (run) et_host_run(c);
+  return 0;
+}
+
+// ---- K10: training steps of the yaw, pitch and roll heads (heads_train_ref.h, heads_train.hip) --------------------------------
+static_assert(HT_NETS_MAX == NLML_HEADS_TRAIN_NETS_MAX && HT_R_MAX == NLML_HEADS_TRAIN_R_MAX &&
+              HT_STATUS_ORDER == NLML_HEADS_TRAIN_CLAMPED_ORDER, "the header's constants are the kernels'");
+static_assert(sizeof(HtNet) == sizeof(nlml_heads_net) && offsetof(HtNet, y) == offsetof(nlml_heads_net, y) &&
+              offsetof(HtNet, v) == offsetof(nlml_heads_net, v) && offsetof(HtNet, step0) == offsetof(nlml_heads_net, step0) &&
+              offsetof(HtNet, status) == offsetof(nlml_heads_net, status), "HtNet is the header's nlml_heads_net");
+// The checks of include/nlml_hpe.h ("K10 argument checks") in their stated order, shared by the four forms; fills *c.
+static int check_heads_train(const char* who, bool train, bool device, const nlml_heads_net* nets, int n_nets, int R, int batch, double lr,
+                             double weight_decay, double max_norm, const void* workspace, size_t workspace_bytes, HtCall* c) {
+  if (n_nets < 1 || n_nets > NLML_HEADS_TRAIN_NETS_MAX)
+    return refuse(NLML_E_BADARG, who, "n_nets = %d outside [1, %d]", n_nets, NLML_HEADS_TRAIN_NETS_MAX);
+  if (R < 1 || R > NLML_HEADS_TRAIN_R_MAX) return refuse(NLML_E_BADARG, who, "R = %d outside [1, %d]", R, NLML_HEADS_TRAIN_R_MAX);
+  if (batch < 1 || batch > NLML_ENCODER_TRAIN_BATCH_MAX)
+    return refuse(NLML_E_BADARG, who, "batch = %d outside [1, %d]", batch, NLML_ENCODER_TRAIN_BATCH_MAX);
+  if (!nets || (device && !workspace)) return refuse(NLML_E_BADARG, who, "null buffer");
+  for (int i = 0; i < n_nets; ++i)
+    if (!nets[i].x || !nets[i].y || !nets[i].params || (train && (!nets[i].grads || !nets[i].m || !nets[i].v)))
+      return refuse(NLML_E_BADARG, who, "network %d: null buffer", i);
+  for (int i = 0; i < n_nets; ++i)
+    if (nets[i].n <= 0) return refuse(NLML_E_BADARG, who, "network %d: n = %lld, expected at least 1", i, (long long)nets[i].n);
+  const size_t need = ht_workspace(R, batch).net_bytes * (size_t)n_nets;
+  if ((device || workspace) && workspace_bytes < need)
+    return refuse(NLML_E_BADARG, who, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  for (int i = 0; i < n_nets; ++i)
+    if (nets[i].step0 < 0) return refuse(NLML_E_BADARG, who, "network %d: step0 = %lld is negative", i, (long long)nets[i].step0);
+  for (int i = 0; i < n_nets; ++i) {
+    const nlml_heads_net& a = nets[i];
+    if (a.N < 1 || a.N > (int64_t)INT32_MAX) return refuse(NLML_E_BADARG, who, "network %d: N = %lld outside [1, 2^31 - 1]", i, (long long)a.N);
+    if (a.ldx < R) return refuse(NLML_E_BADARG, who, "network %d: ldx = %lld < R = %d", i, (long long)a.ldx, R);
+    if (a.ldx > INT64_MAX / 4 / a.N) return refuse(NLML_E_BADARG, who, "network %d: table too large for 64-bit byte offsets", i);
+  }
+  if (train && !(std::isfinite(lr) && std::isfinite(weight_decay) && std::isfinite(max_norm) && max_norm >= 0.0))
+    return refuse(NLML_E_BADARG, who, "lr, weight_decay and max_norm must be finite, max_norm not negative");
+  if (device) {
+    if (!aligned(workspace, 16)) return refuse(NLML_E_BADARG, who, "params, grads, m, v and workspace must be 16-byte aligned");
+    for (int i = 0; i < n_nets; ++i) {
+      const nlml_heads_net& a = nets[i];
+      if (!aligned(a.params, 16) || (train && (!aligned(a.grads, 16) || !aligned(a.m, 16) || !aligned(a.v, 16))))
+        return refuse(NLML_E_BADARG, who, "params, grads, m, v and workspace must be 16-byte aligned");
+      if (!aligned(a.x, 4) || !aligned(a.y, 4) || !aligned(a.order, 4) || !aligned(a.loss_out, 4) || !aligned(a.norm_out, 4) ||
+          !aligned(a.status, 4))
+        return refuse(NLML_E_BADARG, who, "f32 and i32 buffers must be 4-byte aligned");
+    }
+  }
+  *c = HtCall{};
+  for (int i = 0; i < n_nets; ++i) {
+    const nlml_heads_net& a = nets[i];
+    c->net[i] = HtNet{a.x, a.ldx, a.N, a.y, a.params, train ? a.grads : nullptr, train ? a.m : nullptr, train ? a.v : nullptr,
+                      a.order, a.n, a.step0, a.loss_out, train ? a.norm_out : nullptr, a.status};
+  }
+  c->n_nets = n_nets; c->R = R; c->batch = batch; c->train = train ? 1 : 0;
+  c->lr = lr; c->weight_decay = weight_decay; c->max_norm = max_norm;
+  return 0;
+}
+
+size_t nlml_heads_train_workspace_bytes(int R, int batch, int n_nets) {
+  if (R < 1 || R > NLML_HEADS_TRAIN_R_MAX || batch < 1 || batch > NLML_ENCODER_TRAIN_BATCH_MAX || n_nets < 1 ||
+      n_nets > NLML_HEADS_TRAIN_NETS_MAX)
+    return 0;
+  return ht_workspace(R, batch).net_bytes * (size_t)n_nets;
+}
+
+int nlml_heads_train_steps(const nlml_heads_net* nets, int n_nets, int R, int batch, double lr, double weight_decay, double max_norm,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  HtCall c;
+  if (int rc = check_heads_train("heads_train_steps", true, true, nets, n_nets, R, batch, lr, weight_decay, max_norm, workspace,
+                                 workspace_bytes, &c))
+    return rc;
+  return launch_heads_train(c, workspace, stream);
+}
+
+int nlml_heads_eval_losses(const nlml_heads_net* nets, int n_nets, int R, int batch, void* workspace, size_t workspace_bytes, void* stream) {
+  HtCall c;
+  if (int rc = check_heads_train("heads_eval_losses", false, true, nets, n_nets, R, batch, 0.0, 0.0, 0.0, workspace, workspace_bytes, &c))
+    return rc;
+  return launch_heads_train(c, workspace, stream);
+}
+
+// the same order (heads_train_ref.h) on host buffers: plain C++, no HIP call
+int nlml_heads_train_steps_host(const nlml_heads_net* h_nets, int n_nets, int R, int batch, double lr, double weight_decay, double max_norm,
+                                void* h_workspace, size_t workspace_bytes) {
+  HtCall c;
+  if (int rc = check_heads_train("heads_train_steps_host", true, false, h_nets, n_nets, R, batch, lr, weight_decay, max_norm, h_workspace,
+                                 workspace_bytes, &c))
+    return rc;
+  ht_host_run(c, h_workspace);
+  return 0;
+}
+
+int nlml_heads_eval_losses_host(const nlml_heads_net* h_nets, int n_nets, int R, int batch, void* h_workspace, size_t workspace_bytes) {
+  HtCall c;
+  if (int rc = check_heads_train("heads_eval_losses_host", false, false, h_nets, n_nets, R, batch, 0.0, 0.0, 0.0, h_workspace,
+                                 workspace_bytes, &c))
+    return rc;
+  ht_host_run(c, h_workspace);
   return 0;
 }
 

@@ -149,6 +149,11 @@ int launch_cosine_fit_objective(const double* y, const double* w_deg, int n, con
 struct EtCall;
 int launch_encoder_train(const EtCall& c, void* workspace, void* stream);
 
+// heads_train.hip (K10): the steps of up to three head networks (c.train == 0: forward and loss only), every launch shared by all of
+// them, all enqueued on the stream.  The call is checked by the caller (abi.cpp); HtCall is heads_train_ref.h's.
+struct HtCall;
+int launch_heads_train(const HtCall& c, void* workspace, void* stream);
+
 // video_post.hip
 int launch_video_post(const float* pose_rad, const float* raw, const uint8_t* valid, int64_t S, double frame_w,
                       double frame_h, double alpha, double max_jump, double size, double* state, double* smoothed,

@@ -169,9 +169,12 @@ struct EtHostMat { const float* base; int64_t ld; const int32_t* rows; };
 static inline const float* et_host_row(const EtHostMat& m, int r) { return m.base + (int64_t)(m.rows ? m.rows[r] : r) * m.ld; }
 
 // C[m][n] (row stride N) = the GEMM order above.  B is k-outer: element (k, n) = Bm(k, n); A is k-contiguous (a_kc: element (m, k) =
-// Am(m, k)) or k-outer (element (m, k) = Am(k, m)).  init [N] or NULL: wave 0's start.
+// Am(m, k)) or k-outer (element (m, k) = Am(k, m)).  init [N] or NULL: wave 0's start.  pad: an index k >= K of a visited super-chunk is
+// the zero operand the device feeds its matrix cores (fmaf(0, 0, p): a -0 becomes +0) instead of a skipped one -- K10's host form,
+// which is claimed to return the device's bits (heads_train_ref.h); K9's stays as it was.
 static inline __attribute__((always_inline)) void et_host_gemm_body(int M, int N, int K, const EtHostMat& Am, bool a_kc, const EtHostMat& Bm,
-                                                                    const float* init, float* __restrict C, float* __restrict part) {
+                                                                    const float* init, float* __restrict C, float* __restrict part,
+                                                                    const bool pad) {
   for (int m = 0; m < M; ++m) {
     for (int w = 0; w < ET_WAVES; ++w) {
       float* __restrict p = part + (size_t)w * N;
@@ -183,7 +186,11 @@ static inline __attribute__((always_inline)) void et_host_gemm_body(int M, int N
           for (int j = 0; j < 4; ++j)
             for (int h = 0; h < 2; ++h) {
               const int k = ET_SUPER * s + 8 * u + 4 * h + j;
-              if (k >= K) continue;
+              if (k >= K) {
+                if (pad)
+                  for (int n = 0; n < N; ++n) p[n] = fmaf(0.0f, 0.0f, p[n]);
+                continue;
+              }
               const float av = a_kc ? et_host_row(Am, m)[k] : et_host_row(Am, k)[m];
               const float* __restrict br = et_host_row(Bm, k);
               for (int n = 0; n < N; ++n) p[n] = fmaf(av, br[n], p[n]);
@@ -199,21 +206,24 @@ static inline __attribute__((always_inline)) void et_host_gemm_body(int M, int N
 }
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
 __attribute__((target("avx2,fma"))) static void et_host_gemm_fma(int M, int N, int K, const EtHostMat& Am, bool a_kc, const EtHostMat& Bm,
-                                                                 const float* init, float* C, float* part) {
-  et_host_gemm_body(M, N, K, Am, a_kc, Bm, init, C, part);
+                                                                 const float* init, float* C, float* part, bool pad) {
+  if (pad) et_host_gemm_body(M, N, K, Am, a_kc, Bm, init, C, part, true);
+  else et_host_gemm_body(M, N, K, Am, a_kc, Bm, init, C, part, false);
 }
 #endif
 static void et_host_gemm_plain(int M, int N, int K, const EtHostMat& Am, bool a_kc, const EtHostMat& Bm, const float* init, float* C,
-                               float* part) {
-  et_host_gemm_body(M, N, K, Am, a_kc, Bm, init, C, part);
+                               float* part, bool pad) {
+  if (pad) et_host_gemm_body(M, N, K, Am, a_kc, Bm, init, C, part, true);
+  else et_host_gemm_body(M, N, K, Am, a_kc, Bm, init, C, part, false);
 }
 // the same values either way (fmaf is fmaf); the first is the second with the machine's own fused multiply-add and vectors
-static inline void et_host_gemm(int M, int N, int K, const EtHostMat& Am, bool a_kc, const EtHostMat& Bm, const float* init, float* C) {
+static inline void et_host_gemm(int M, int N, int K, const EtHostMat& Am, bool a_kc, const EtHostMat& Bm, const float* init, float* C,
+                                bool pad = false) {
   std::vector<float> part((size_t)ET_WAVES * N);
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-  if (__builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma")) return et_host_gemm_fma(M, N, K, Am, a_kc, Bm, init, C, part.data());
+  if (__builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma")) return et_host_gemm_fma(M, N, K, Am, a_kc, Bm, init, C, part.data(), pad);
 #endif
-  et_host_gemm_plain(M, N, K, Am, a_kc, Bm, init, C, part.data());
+  et_host_gemm_plain(M, N, K, Am, a_kc, Bm, init, C, part.data(), pad);
 }
 
 template <int SLOTS> static inline double et_host_tree(double* s) {

@@ -411,6 +411,72 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> encoder_train_steps(const at::Ten
   return {loss, norm, status};
 }
 
+// K10: the training steps of up to three head networks, params / grads / m / v f32[P] each updated in place.  x[i] f32[N_i,R] with unit
+// column stride (a padded row stride is passed on as ldx), y[i] f32[N_i], order[i] i32[>= n_i] or None (the rows in turn), n[i] rows
+// visited, step0[i] Adam steps taken before -> (loss f32[steps_i] per network, norm likewise, status i32[n_nets]); the workspace comes
+// from torch's allocator
+std::tuple<std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor> heads_train_steps(
+    at::TensorList x, at::TensorList y_, at::TensorList params, at::TensorList grads, at::TensorList m, at::TensorList v,
+    const c10::List<std::optional<at::Tensor>>& order_, at::IntArrayRef n, at::IntArrayRef step0, int64_t batch, double lr,
+    double weight_decay, double max_norm) {
+  const int64_t nets = (int64_t)x.size();
+  TORCH_CHECK(nets >= 1 && nets <= NLML_HEADS_TRAIN_NETS_MAX, "expected 1..", NLML_HEADS_TRAIN_NETS_MAX, " networks, got ", nets);
+  TORCH_CHECK((int64_t)y_.size() == nets && (int64_t)params.size() == nets && (int64_t)grads.size() == nets && (int64_t)m.size() == nets &&
+              (int64_t)v.size() == nets && (int64_t)order_.size() == nets && (int64_t)n.size() == nets && (int64_t)step0.size() == nets,
+              "every per-network list must have ", nets, " entries");
+  TORCH_CHECK(batch >= 1 && batch <= NLML_ENCODER_TRAIN_BATCH_MAX, "batch = ", batch, " outside [1, ", NLML_ENCODER_TRAIN_BATCH_MAX, "]");
+  need(x[0], "x", at::kFloat);
+  const int64_t R = x[0].dim() == 2 ? x[0].size(1) : 0;
+  TORCH_CHECK(R >= 1 && R <= NLML_HEADS_TRAIN_R_MAX, "x: expected [N,R] with R in [1, ", NLML_HEADS_TRAIN_R_MAX, "], got ", x[0].sizes());
+  int64_t P = 0, fan_in = R;
+  for (int64_t w : {128, 256, 128, 64, 1}) { P += w * fan_in + w; fan_in = w; }
+  const auto f32 = x[0].options(), i32 = x[0].options().dtype(at::kInt);
+  std::vector<at::Tensor> keep, loss, norm;
+  at::Tensor status = at::zeros({nets}, i32);
+  nlml_heads_net call[NLML_HEADS_TRAIN_NETS_MAX] = {};
+  for (int64_t i = 0; i < nets; ++i) {
+    need(x[i], "x", at::kFloat);
+    need(y_[i], "y", at::kFloat);
+    same_device(x[0], x[i], "x");
+    same_device(x[0], y_[i], "y");
+    TORCH_CHECK(x[i].dim() == 2 && x[i].size(0) >= 1 && x[i].size(1) == R && x[i].stride(1) == 1 && x[i].stride(0) >= R,
+                "x: expected [N,", R, "] with unit column stride, got ", x[i].sizes(), " strides ", x[i].strides());
+    TORCH_CHECK(y_[i].dim() == 1 && y_[i].size(0) == x[i].size(0), "y: expected [", x[i].size(0), "], got ", y_[i].sizes());
+    for (const at::Tensor* t : {&params[i], &grads[i], &m[i], &v[i]}) {
+      need(*t, "params, grads, m, v", at::kFloat);
+      need_dense(*t, "params, grads, m, v");
+      same_device(x[0], *t, "params, grads, m, v");
+      TORCH_CHECK(t->numel() == P, "params, grads, m, v: expected ", P, " elements each, got ", t->numel());
+    }
+    TORCH_CHECK(n[i] >= 1 && step0[i] >= 0, "n must be at least 1 and step0 not negative");
+    const at::Tensor y = y_[i].contiguous();
+    keep.push_back(y);
+    const std::optional<at::Tensor> order_i = order_.get(i);
+    const int32_t* order = nullptr;
+    if (order_i.has_value()) {
+      need(*order_i, "order", at::kInt);
+      same_device(x[0], *order_i, "order");
+      TORCH_CHECK(order_i->dim() == 1 && order_i->size(0) >= n[i], "order: expected at least n = ", n[i], " entries, got ", order_i->sizes());
+      keep.push_back(order_i->contiguous());
+      order = keep.back().data_ptr<int32_t>();
+    } else {
+      TORCH_CHECK(n[i] <= x[i].size(0), "n = ", n[i], " beyond the ", x[i].size(0), " rows of x");
+    }
+    const int64_t steps = (n[i] + batch - 1) / batch;
+    loss.push_back(at::empty({steps}, f32));
+    norm.push_back(at::empty({steps}, f32));
+    call[i] = nlml_heads_net{x[i].data_ptr<float>(), x[i].stride(0), x[i].size(0), y.data_ptr<float>(), params[i].data_ptr<float>(),
+                             grads[i].data_ptr<float>(), m[i].data_ptr<float>(), v[i].data_ptr<float>(), order, n[i], step0[i],
+                             loss[i].data_ptr<float>(), norm[i].data_ptr<float>(), status.data_ptr<int32_t>() + i};
+  }
+  const size_t ws_bytes = nlml_heads_train_workspace_bytes((int)R, (int)batch, (int)nets);
+  at::Tensor ws = at::empty({(int64_t)ws_bytes}, x[0].options().dtype(at::kByte));
+  OnDevice dev(x[0]);
+  check(nlml_heads_train_steps(call, (int)nets, (int)R, (int)batch, lr, weight_decay, max_norm, ws.data_ptr(), ws_bytes, dev.stream),
+        "nlml_heads_train_steps");
+  return {loss, norm, status};
+}
+
 // K5: the evaluation block in one native pass.  pose f32[B,3] radians or f64[B,3] degrees (by dtype), valid bool/u8[B] or None,
 // gt f64[B,3]; lo / hi the inclusive GT range, intervals [K*2] (low, high) with their axes [K]; the records' workspace comes from
 // torch's allocator -> (record f64[12+2K], result f64[14+2K])
@@ -593,6 +659,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> encoder_train_steps_meta(const at
   const int64_t steps = batch > 0 ? (n + batch - 1) / batch : 0;
   return {at::empty({steps}, x.options()), at::empty({steps}, x.options()), at::empty({1}, x.options().dtype(at::kInt))};
 }
+std::tuple<std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor> heads_train_steps_meta(
+    at::TensorList x, at::TensorList, at::TensorList, at::TensorList, at::TensorList, at::TensorList, const c10::List<std::optional<at::Tensor>>&,
+    at::IntArrayRef n, at::IntArrayRef, int64_t batch, double, double, double) {
+  std::vector<at::Tensor> loss, norm;
+  for (size_t i = 0; i < x.size(); ++i) {
+    const int64_t steps = batch > 0 && i < n.size() ? (n[i] + batch - 1) / batch : 0;
+    loss.push_back(at::empty({steps}, x[i].options()));
+    norm.push_back(at::empty({steps}, x[i].options()));
+  }
+  return {loss, norm, at::empty({(int64_t)x.size()}, x[0].options().dtype(at::kInt))};
+}
 at::Tensor cosine_table_meta(const at::Tensor& angles, const at::Tensor& cosp) { return at::empty({angles.size(0), cosp.size(0)}, cosp.options()); }
 
 std::tuple<at::Tensor, at::Tensor> pose_eval_meta(const at::Tensor& pose, const std::optional<at::Tensor>&, const at::Tensor& gt,
@@ -627,6 +704,8 @@ TORCH_LIBRARY(nlml_hpe, m) {
   m.def("cosine_fit(Tensor y, Tensor w_deg, int[] n, Tensor x0, float xtol=1e-4, float ftol=1e-4) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("encoder_train_steps(Tensor x, Tensor labels, Tensor t_yaw, Tensor t_pitch, Tensor t_roll, Tensor(a!) params, Tensor(b!) grads, "
         "Tensor? order, int n, int batch, float lr, float weight_decay, float max_norm, bool zero_grad) -> (Tensor, Tensor, Tensor)");
+  m.def("heads_train_steps(Tensor[] x, Tensor[] y, Tensor(a!)[] params, Tensor(b!)[] grads, Tensor(c!)[] m, Tensor(d!)[] v, Tensor?[] order, "
+        "int[] n, int[] step0, int batch, float lr, float weight_decay, float max_norm) -> (Tensor[], Tensor[], Tensor)");
   m.def("pose_eval(Tensor pose, Tensor? valid, Tensor gt, float[] lo, float[] hi, int decimals, float[] intervals, int[] axes) "
         "-> (Tensor, Tensor)");
   m.def("pose_eval_merge(Tensor records, int K) -> (Tensor, Tensor)");
@@ -653,6 +732,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
   m.impl("cosine_table", &cosine_table);
   m.impl("cosine_fit", &cosine_fit);
   m.impl("encoder_train_steps", &encoder_train_steps);
+  m.impl("heads_train_steps", &heads_train_steps);
   m.impl("pose_eval", &pose_eval);
   m.impl("pose_eval_merge", &pose_eval_merge);
   m.impl("mode_gram", &mode_gram);
@@ -678,6 +758,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("cosine_table", &cosine_table_meta);
   m.impl("cosine_fit", &cosine_fit_meta);
   m.impl("encoder_train_steps", &encoder_train_steps_meta);
+  m.impl("heads_train_steps", &heads_train_steps_meta);
   m.impl("pose_eval", &pose_eval_meta);
   m.impl("pose_eval_merge", &pose_eval_merge_meta);
   m.impl("mode_gram", &mode_gram_meta);

@@ -730,6 +730,120 @@ def encoder_eval_losses(x, labels, tables, params, order=None, n=None, batch=256
     return loss, status
 
 
+# ---- K10: training steps of the three heads (csrc/heads_train.hip; the driver is nlml_hpe_amd/MLPHeadsTrainer.py) ----------------
+def heads_param_count(R: int) -> int:
+    """Elements of a head network's contiguous params / grads / m / v buffers W0,b0,...,W4,b4 for input width R (74,753 at R = 3)."""
+    from .MLPHeadsTrainer import param_count
+    return param_count(R)
+
+
+def heads_param_views(buf, R: int) -> dict:
+    """The state dict `model.{0,2,4,6,8}.{weight,bias}` as VIEWS of a contiguous params (grads, m, v) buffer, numpy or torch."""
+    from .MLPHeadsTrainer import state_dict_views
+    return state_dict_views(buf, R)
+
+
+def _heads_nets(nets, batch, train):
+    """Checks the networks of a K10 call (dicts: x, y, params[, grads, m, v][, order][, n][, step0]) -> (normalised dicts, R, batch)."""
+    nets = [dict(net) for net in nets]
+    if not 1 <= len(nets) <= _lib.HEADS_TRAIN_NETS_MAX:
+        raise ValueError(f"expected 1..{_lib.HEADS_TRAIN_NETS_MAX} networks, got {len(nets)}")
+    batch = int(batch)
+    if not 1 <= batch <= _lib.ENCODER_TRAIN_BATCH_MAX:
+        raise ValueError(f"batch = {batch} outside [1, {_lib.ENCODER_TRAIN_BATCH_MAX}]")
+    R = None
+    for i, net in enumerate(nets):
+        x, y = net["x"], net["y"]
+        _need_cuda(x, f"network {i}: x", torch.float32)
+        _need_cuda(y, f"network {i}: y", torch.float32)
+        if x.dim() != 2 or x.shape[0] < 1 or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            raise ValueError(f"network {i}: x: expected [N,R] with unit column stride, got {tuple(x.shape)} strides {x.stride()}")
+        R = x.shape[1] if R is None else R
+        if x.shape[1] != R or not 1 <= R <= _lib.HEADS_TRAIN_R_MAX:
+            raise ValueError(f"network {i}: x has {x.shape[1]} columns: expected the same R in [1, {_lib.HEADS_TRAIN_R_MAX}] for every network")
+        if y.dim() != 1 or y.shape[0] != x.shape[0]:
+            raise ValueError(f"network {i}: y: expected [{x.shape[0]}], got {tuple(y.shape)}")
+        net["y"] = y.contiguous()
+        for key in ("params", "grads", "m", "v") if train else ("params",):
+            t = net[key]
+            _need_cuda(t, f"network {i}: {key}", torch.float32)
+            if not t.is_contiguous() or t.numel() != heads_param_count(R):
+                raise ValueError(f"network {i}: {key}: expected a contiguous buffer of {heads_param_count(R)} elements, got {tuple(t.shape)}")
+        order = net.get("order")
+        if order is not None:
+            _need_cuda(order, f"network {i}: order", torch.int32)
+            if order.dim() != 1:
+                raise ValueError(f"network {i}: order: expected a vector, got {tuple(order.shape)}")
+            net["order"] = order = order.contiguous()
+        limit = order.shape[0] if order is not None else x.shape[0]
+        n = limit if net.get("n") is None else int(net["n"])
+        if not 1 <= n <= limit:
+            raise ValueError(f"network {i}: n = {n} outside [1, {limit}]")
+        net["n"] = n
+        net["step0"] = int(net.get("step0") or 0)
+        if net["step0"] < 0:
+            raise ValueError(f"network {i}: negative step0")
+    return nets, int(R), batch
+
+
+def _heads_call(nets, R, batch, train, workspace):
+    """The C array of nlml_heads_net, the outputs (loss, norm per network; status i32[n_nets]) and the workspace of a K10 call."""
+    dev = nets[0]["x"].device
+    arr = (_lib.HeadsNet * len(nets))()
+    loss, norm = [], []
+    status = torch.zeros((len(nets),), dtype=torch.int32, device=dev)
+    for i, net in enumerate(nets):
+        steps = (net["n"] + batch - 1) // batch
+        loss.append(torch.empty((steps,), dtype=torch.float32, device=dev))
+        norm.append(torch.empty((steps,), dtype=torch.float32, device=dev) if train else None)
+        a = arr[i]
+        a.x, a.ldx, a.N, a.y = net["x"].data_ptr(), net["x"].stride(0), net["x"].shape[0], net["y"].data_ptr()
+        a.params = net["params"].data_ptr()
+        if train:
+            a.grads, a.m, a.v = net["grads"].data_ptr(), net["m"].data_ptr(), net["v"].data_ptr()
+            a.norm_out = norm[i].data_ptr()
+        a.order = net["order"].data_ptr() if net.get("order") is not None else None
+        a.n, a.step0 = net["n"], net["step0"]
+        a.loss_out, a.status = loss[i].data_ptr(), status.data_ptr() + 4 * i
+    need = _lib.lib().nlml_heads_train_workspace_bytes(R, batch, len(nets))
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"workspace: expected a contiguous GPU buffer of at least {need} bytes")
+    operands = [(f"network {i}: {k}", net.get(k)) for i, net in enumerate(nets) for k in ("x", "y", "params", "grads", "m", "v", "order")]
+    return arr, loss, norm, status, workspace, operands + [("workspace", workspace)]
+
+
+def heads_train_steps(nets, batch=256, lr=5e-3, weight_decay=1e-5, max_norm=1.0, workspace=None):
+    """K10: the training steps of up to three independent head networks (NLML_HPE_MLPHeadsTrainer.py:93-103) enqueued without a
+    synchronisation, every launch shared by all of them: zero_grad, forward, MSELoss, backward, clip_grad_norm_(max_norm), Adam with
+    L2 weight decay.  The call runs max_i ceil(n_i / batch) steps; a network whose rows are used up is left alone.
+
+    nets  a sequence of dicts, one per network: x f32[N,R] (R 1..16, the same for all; a padded row stride is fine), y f32[N],
+          params / grads / m / v contiguous f32[heads_param_count(R)] updated IN PLACE (heads_param_views gives the state dict),
+          order i32[n] the rows in visiting order (absent or None: 0..n-1), n (default: all), step0 the Adam steps the network has
+          taken before this call (default 0; the caller carries it: step0 += ceil(n / batch))
+    -> (loss [f32[steps_i] per network], norm [f32[steps_i] before clipping], status i32[n_nets]: _lib.HEADS_TRAIN_CLAMPED_ORDER) on
+    the device."""
+    nets, R, batch = _heads_nets(nets, batch, True)
+    arr, loss, norm, status, ws, operands = _heads_call(nets, R, batch, True, workspace)
+    with _on_device_of(*operands) as stream:
+        _lib.check(_lib.lib().nlml_heads_train_steps(C.addressof(arr), len(nets), R, batch, float(lr), float(weight_decay), float(max_norm),
+                                                     ws.data_ptr(), ws.numel() * ws.element_size(), stream), "nlml_heads_train_steps")
+    return loss, norm, status
+
+
+def heads_eval_losses(nets, batch=256, workspace=None):
+    """The validation pass of K10: forward and loss only, batch after batch, all networks in the same launches -> (loss [f32[steps_i]
+    per network], status i32[n_nets]) on the device.  The forward is the training step's, bit for bit.  nets: x, y, params[, order, n]."""
+    nets, R, batch = _heads_nets(nets, batch, False)
+    arr, loss, _, status, ws, operands = _heads_call(nets, R, batch, False, workspace)
+    with _on_device_of(*operands) as stream:
+        _lib.check(_lib.lib().nlml_heads_eval_losses(C.addressof(arr), len(nets), R, batch, ws.data_ptr(), ws.numel() * ws.element_size(),
+                                                     stream), "nlml_heads_eval_losses")
+    return loss, status
+
+
 # ---- K5 evaluation (nlml_pose_eval) -------------------------------------------------------------------------------------------
 _eval_ws: dict = {}
 
@@ -837,7 +951,7 @@ def _load_torch_ops():
     for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
                  "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks", "mode_gram", "pose_grams", "project_identity",
-                 "project_pose", "cosine_fit", "encoder_train_steps"):
+                 "project_pose", "cosine_fit", "encoder_train_steps", "heads_train_steps"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
 
