@@ -756,7 +756,7 @@ static int check_encoder_train(const char* who, bool train, bool device, const E
   if (train && !(std::isfinite(lr) && std::isfinite(weight_decay) && std::isfinite(c.max_norm) && c.max_norm >= 0.0))
     return refuse(NLML_E_BADARG, who, "lr, weight_decay and max_norm must be finite, max_norm not negative");
   if (device) {
-    const size_t need = et_workspace(c.F, c.batch).bytes;
+    const size_t need = et_workspace(c.F, c.batch).net_bytes;
     if (workspace_bytes < need) return refuse(NLML_E_BADARG, who, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
     if (!aligned(c.params, 16) || !aligned(c.grads, 16) || !aligned(workspace, 16))
       return refuse(NLML_E_BADARG, who, "params, grads and workspace must be 16-byte aligned");
@@ -783,7 +783,7 @@ static EtCall encoder_call(const float* x, int64_t ldx, int64_t N, const int32_t
 
 size_t nlml_encoder_train_workspace_bytes(int F, int batch) {
   if ((F != 136 && F != NLML_F_REFERENCE) || batch < 1 || batch > NLML_ENCODER_TRAIN_BATCH_MAX) return 0;
-  return et_workspace(F, batch).bytes;
+  return et_workspace(F, batch).net_bytes;
 }
 
 int nlml_encoder_train_steps(const float* x, int64_t ldx, int64_t N, const int32_t* labels, int64_t ld_lab, const float* t_yaw, int n_yaw,

@@ -148,6 +148,19 @@ int launch_cosine_fit_objective(const double* y, const double* w_deg, int n, con
 // call is checked by the caller (abi.cpp); EtCall is encoder_train_ref.h's.
 struct EtCall;
 int launch_encoder_train(const EtCall& c, void* workspace, void* stream);
+// The launches K9 shares with K10: a step's forward layers and its backward layers over the 1..3 networks of a call, one launch per
+// layer, the grid sized for the largest batch (MlpDims, MlpWorkspace: encoder_train_ref.h's).
+struct MlpDims;
+struct MlpWorkspace;
+struct MlpLaunchNet {
+  const float* x; int64_t ldx, N;       // the dataset rows
+  const int32_t* order;
+  const float* params; float* grads;    // grads unused by the forward launches
+  char* block;                          // the network's workspace block (mlp_workspace)
+  int B;                                // rows of this step's batch; 0: the network is exhausted
+};
+void mlp_launch_forward(const MlpDims& d, const MlpWorkspace& ws, const MlpLaunchNet* nets, int n_nets, int64_t slot0, void* stream);
+void mlp_launch_backward(const MlpDims& d, const MlpWorkspace& ws, const MlpLaunchNet* nets, int n_nets, int zero_grad, void* stream);
 
 // heads_train.hip (K10): the steps of up to three head networks (c.train == 0: forward and loss only), every launch shared by all of
 // them, all enqueued on the stream.  The call is checked by the caller (abi.cpp); HtCall is heads_train_ref.h's.

@@ -35,6 +35,12 @@
 // (oracle/csrc/oracle.c "K9", k >= K as a zero operand), tests/test_encoder_train_order_host.py holds that model to the host form's
 // values, to float64 and to deliberately wrong orders, and tests/test_encoder_train_order_gpu.py holds every launch of a step to it on
 // the device's own inputs (A_5 alone to 5 ulp of float64 tanh).
+//
+// K10 (heads_train_ref.h, the yaw, pitch and roll heads) is the same design on another network, so what the two share is written here
+// once, over a description of the network (MlpShape: layer count, widths, which layer's output goes through Tanh, the last layer's row
+// stride in the workspace): the dims and the workspace layout (mlp_dims, mlp_workspace), and the host form's row resolution, forward,
+// dgrad, wgrad + bias + norm partials and norm (mlp_host_*), which write into a workspace block in the device's layout.  K9 is
+// ET_SHAPE, one network, pad = false, zero_grad from the call; its own part is the residual and loss, and the SGD update.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -49,7 +55,8 @@
 
 namespace nlml {
 
-constexpr int ET_LAYERS = 6;
+constexpr int ET_LAYERS = 6;             // K9's layers, and the most a network may have
+constexpr int MLP_NETS_MAX = 3;          // networks that may share a launch (blockIdx.y); K9 is the case of one
 constexpr int ET_TILE = 32;
 constexpr int ET_WAVES = 8;              // waves of a workgroup = the split of K
 constexpr int ET_NT = 64 * ET_WAVES;
@@ -64,55 +71,66 @@ constexpr int ET_STATUS_LABEL = 2;       // NLML_ENCODER_TRAIN_CLAMPED_LABEL
 
 ET_HD int et_tiles(int n) { return (n + ET_TILE - 1) / ET_TILE; }
 
+// a network both trainers can run: Linear(fan_in, widths[0]) .. Linear(widths[layers-2], widths[layers-1]), ReLU after every layer but
+// the last, except Tanh after layer `tanh_layer` (-1: none); last_ld: the row stride of the last layer's output in the workspace.
+// K9 is ET_SHAPE with fan_in = F; K10 is HT_SHAPE (heads_train_ref.h) with fan_in = R.
+struct MlpShape { int layers, widths[ET_LAYERS], tanh_layer, last_ld; };
+constexpr MlpShape ET_SHAPE = {ET_LAYERS, {1024, 512, 256, 128, 64, ET_LATENT}, 4, ET_LATENT_LD};
+constexpr int MLP_ACT_NONE = 0, MLP_ACT_RELU = 1, MLP_ACT_TANH = 2;
+
 // widths and the offsets (in floats) of W_l [out,in] and b_l [out] inside the contiguous params / grads buffers, state-dict order
-struct EtDims {
+struct MlpDims {
+  int layers, tanh_layer, last_ld;
   int in[ET_LAYERS], out[ET_LAYERS];
   int64_t w_off[ET_LAYERS], b_off[ET_LAYERS];
   int64_t total;
   int part_off[ET_LAYERS];   // first norm partial of layer l's wgrad tiles
   int n_partials;
 };
-ET_HD EtDims et_dims(int F) {
-  const int widths[ET_LAYERS] = {1024, 512, 256, 128, 64, ET_LATENT};
-  EtDims d;
+ET_HD MlpDims mlp_dims(const MlpShape& s, int fan_in) {
+  MlpDims d = {};
+  d.layers = s.layers; d.tanh_layer = s.tanh_layer; d.last_ld = s.last_ld;
   int64_t off = 0;
-  int fan_in = F, parts = 0;
-  for (int l = 0; l < ET_LAYERS; ++l) {
-    d.in[l] = fan_in; d.out[l] = widths[l];
-    d.w_off[l] = off; off += (int64_t)widths[l] * fan_in;
-    d.b_off[l] = off; off += widths[l];
-    d.part_off[l] = parts; parts += et_tiles(widths[l]) * et_tiles(fan_in);
-    fan_in = widths[l];
+  int parts = 0;
+  for (int l = 0; l < s.layers; ++l) {
+    d.in[l] = fan_in; d.out[l] = s.widths[l];
+    d.w_off[l] = off; off += (int64_t)s.widths[l] * fan_in;
+    d.b_off[l] = off; off += s.widths[l];
+    d.part_off[l] = parts; parts += et_tiles(s.widths[l]) * et_tiles(fan_in);
+    fan_in = s.widths[l];
   }
   d.total = off;
   d.n_partials = parts;
   return d;
 }
+ET_HD int mlp_act(const MlpDims& d, int l) { return l == d.layers - 1 ? MLP_ACT_NONE : (l == d.tanh_layer ? MLP_ACT_TANH : MLP_ACT_RELU); }
 
-// the workspace of one batch, byte offsets: the norm partials (f64), the batch's resolved dataset rows (i32), A_1..A_6 and
-// delta_1..delta_6 (index l - 1; A_6 = pred); rows of A_l / delta_l have stride out[l-1] (ET_LATENT_LD for l = 6)
-struct EtWorkspace {
-  size_t partials, rows, act[ET_LAYERS], delta[ET_LAYERS], bytes;
+// the workspace of one network's batch, byte offsets: the norm partials (f64), the batch's resolved dataset rows (i32[256]), A_1..A_L
+// and delta_1..delta_L (index l - 1; A_L = pred), each [batch, ld[l-1]] and padded to 16 bytes; ld is the layer's width (last_ld for
+// the last).  It holds the network's LAST step; words outside these ranges, and rows b >= B of that step, are never written.
+struct MlpWorkspace {
+  size_t partials, rows, act[ET_LAYERS], delta[ET_LAYERS], net_bytes;
   int ld[ET_LAYERS];
 };
-ET_HD EtWorkspace et_workspace(int F, int batch) {
-  const EtDims d = et_dims(F);
-  EtWorkspace w;
+ET_HD MlpWorkspace mlp_workspace(const MlpDims& d, int batch) {
+  MlpWorkspace w = {};
   size_t off = 0;
   w.partials = off; off += (size_t)((d.n_partials + 1) / 2 * 2) * 8;
   w.rows = off; off += (size_t)ET_BATCH_MAX * 4;
-  for (int l = 0; l < ET_LAYERS; ++l) {
-    w.ld[l] = l == ET_LAYERS - 1 ? ET_LATENT_LD : d.out[l];
+  for (int l = 0; l < d.layers; ++l) {
+    w.ld[l] = l == d.layers - 1 ? d.last_ld : d.out[l];
     w.act[l] = off; off += (size_t)batch * w.ld[l] * 4;
     off = (off + 15) / 16 * 16;
   }
-  for (int l = 0; l < ET_LAYERS; ++l) {
+  for (int l = 0; l < d.layers; ++l) {
     w.delta[l] = off; off += (size_t)batch * w.ld[l] * 4;
     off = (off + 15) / 16 * 16;
   }
-  w.bytes = off;
+  w.net_bytes = off;
   return w;
 }
+ET_HD MlpDims et_dims(int F) { return mlp_dims(ET_SHAPE, F); }
+ET_HD MlpWorkspace et_workspace(int F, int batch) { return mlp_workspace(et_dims(F), batch); }
 
 // the dataset row of batch slot `slot`: order[slot] (order == NULL: slot itself) clamped into [0, N); *clamped: it was outside
 ET_HD int32_t et_resolve_row(const int32_t* order, int64_t slot, int64_t N, bool* clamped) {
@@ -226,83 +244,82 @@ static inline void et_host_gemm(int M, int N, int K, const EtHostMat& Am, bool a
   et_host_gemm_plain(M, N, K, Am, a_kc, Bm, init, C, part.data(), pad);
 }
 
-template <int SLOTS> static inline double et_host_tree(double* s) {
+template <class T, int SLOTS> static inline T et_host_tree(T* s) {
   for (int stride = SLOTS / 2; stride >= 1; stride /= 2)
     for (int t = 0; t < stride; ++t) s[t] = s[t] + s[t + stride];
   return s[0];
 }
 
-struct EtHostState {
-  std::vector<float> act[ET_LAYERS], delta[ET_LAYERS], wt, c;
-  std::vector<double> partials;
-  std::vector<int32_t> rows;
+// ---- the part of a step K9 and K10 share, into one network's workspace block (the device's layout, mlp_workspace) ---------------------
+struct MlpHostWs {
+  MlpWorkspace ws;
+  int32_t* rows; double* partials;
+  float* act[ET_LAYERS]; float* delta[ET_LAYERS];
 };
-
-// one batch: forward, loss (-> *loss, status bits OR-ed into *status), and with grads the backward pass, the norm and the update
-static inline void et_host_step(const EtCall& a, int64_t slot0, int B, EtHostState& st, float* loss, float* norm_out, int* status) {
-  const EtDims d = et_dims(a.F);
-  const EtWorkspace ws = et_workspace(a.F, B);
-  int flags = 0;
-  st.rows.assign(B, 0);
+static inline MlpHostWs mlp_host_ws(const MlpDims& d, int batch, char* block) {
+  MlpHostWs v = {};
+  v.ws = mlp_workspace(d, batch);
+  v.rows = reinterpret_cast<int32_t*>(block + v.ws.rows);
+  v.partials = reinterpret_cast<double*>(block + v.ws.partials);
+  for (int l = 0; l < d.layers; ++l) {
+    v.act[l] = reinterpret_cast<float*>(block + v.ws.act[l]);
+    v.delta[l] = reinterpret_cast<float*>(block + v.ws.delta[l]);
+  }
+  return v;
+}
+// the batch's dataset rows -> v.rows; true: an entry of order was outside [0, N)
+static inline bool mlp_host_rows(const MlpHostWs& v, const int32_t* order, int64_t slot0, int64_t N, int B) {
+  bool any = false;
   for (int b = 0; b < B; ++b) {
     bool cl;
-    st.rows[b] = et_resolve_row(a.order, slot0 + b, a.N, &cl);
-    if (cl) flags |= ET_STATUS_ORDER;
+    v.rows[b] = et_resolve_row(order, slot0 + b, N, &cl);
+    any = any || cl;
   }
-  const EtHostMat X = {a.x, a.ldx, st.rows.data()};
-  // forward
-  for (int l = 0; l < ET_LAYERS; ++l) {
-    const int K = d.in[l], N = d.out[l], ld = ws.ld[l];
-    const float* W = a.params + d.w_off[l];
-    st.wt.resize((size_t)K * N);
+  return any;
+}
+// A_{l-1} as a GEMM operand: the gathered rows of x for l = 0
+static inline EtHostMat mlp_host_input(const MlpHostWs& v, const EtHostMat& X, int l) {
+  return l == 0 ? X : EtHostMat{v.act[l - 1], v.ws.ld[l - 1], nullptr};
+}
+// A_1 .. A_L
+static inline void mlp_host_forward(const MlpDims& d, const MlpHostWs& v, const EtHostMat& X, const float* params, int B, bool pad) {
+  std::vector<float> wt, c;
+  for (int l = 0; l < d.layers; ++l) {
+    const int K = d.in[l], N = d.out[l], ld = v.ws.ld[l], act = mlp_act(d, l);
+    const float* W = params + d.w_off[l];
+    wt.resize((size_t)K * N);
     for (int o = 0; o < N; ++o)
-      for (int k = 0; k < K; ++k) st.wt[(size_t)k * N + o] = W[(size_t)o * K + k];
-    st.c.resize((size_t)B * N);
-    const EtHostMat Am = l == 0 ? X : EtHostMat{st.act[l - 1].data(), ws.ld[l - 1], nullptr};
-    et_host_gemm(B, N, K, Am, true, EtHostMat{st.wt.data(), N, nullptr}, a.params + d.b_off[l], st.c.data());
-    st.act[l].assign((size_t)B * ld, 0.0f);
+      for (int k = 0; k < K; ++k) wt[(size_t)k * N + o] = W[(size_t)o * K + k];
+    c.resize((size_t)B * N);
+    et_host_gemm(B, N, K, mlp_host_input(v, X, l), true, EtHostMat{wt.data(), N, nullptr}, params + d.b_off[l], c.data(), pad);
     for (int b = 0; b < B; ++b)
       for (int o = 0; o < N; ++o) {
-        const float z = st.c[(size_t)b * N + o];
-        st.act[l][(size_t)b * ld + o] = l < 4 ? (z > 0.0f ? z : 0.0f) : (l == 4 ? tanhf(z) : z);
+        const float z = c[(size_t)b * N + o];
+        v.act[l][(size_t)b * ld + o] = act == MLP_ACT_RELU ? (z > 0.0f ? z : 0.0f) : (act == MLP_ACT_TANH ? tanhf(z) : z);
       }
   }
-  // residual and loss
-  {
-    const int ld = ET_LATENT_LD;
-    const float scale = (float)(2.0 / (3.0 * B));
-    st.delta[5].assign((size_t)B * ld, 0.0f);
-    float fslots[ET_BATCH_MAX];
-    for (int b = 0; b < ET_BATCH_MAX; ++b) fslots[b] = 0.0f;
-    for (int b = 0; b < B; ++b) {
-      bool cl = false;
-      float q = 0.0f;
-      for (int j = 0; j < ET_LATENT; ++j) {
-        const int t = j / 3;
-        const int row = et_clamp_label(a.labels[(int64_t)st.rows[b] * a.ld_lab + t], a.rows[t], &cl);
-        const float dd = st.act[5][(size_t)b * ld + j] - a.table[t][row * 3 + j % 3];
-        st.delta[5][(size_t)b * ld + j] = dd * scale;
-        q = fmaf(dd, dd, q);
-      }
-      if (cl) flags |= ET_STATUS_LABEL;
-      fslots[b] = q;
-    }
-    for (int stride = ET_BATCH_MAX / 2; stride >= 1; stride /= 2)
-      for (int t = 0; t < stride; ++t) fslots[t] = fslots[t] + fslots[t + stride];
-    *loss = fslots[0] / (float)(3 * B);
+}
+// delta_{L-1} .. delta_1 from delta_L
+static inline void mlp_host_dgrad(const MlpDims& d, const MlpHostWs& v, const float* params, int B, bool pad) {
+  std::vector<float> c;
+  for (int l = d.layers - 1; l >= 1; --l) {
+    const int in = d.in[l], out = d.out[l], ldp = v.ws.ld[l - 1];
+    c.resize((size_t)B * in);
+    et_host_gemm(B, in, out, EtHostMat{v.delta[l], v.ws.ld[l], nullptr}, true, EtHostMat{params + d.w_off[l], in, nullptr}, nullptr, c.data(), pad);
+    for (int b = 0; b < B; ++b)
+      for (int i = 0; i < in; ++i)
+        v.delta[l - 1][(size_t)b * ldp + i] = c[(size_t)b * in + i] * et_act_grad(v.act[l - 1][(size_t)b * ldp + i], l - 1 == d.tanh_layer);
   }
-  if (status) *status |= flags;
-  if (!a.grads) return;
-  // backward
-  st.partials.assign(d.n_partials, 0.0);
-  for (int l = ET_LAYERS - 1; l >= 0; --l) {
-    const int in = d.in[l], out = d.out[l], ldd = ws.ld[l];
-    const EtHostMat D = {st.delta[l].data(), ldd, nullptr};
-    const EtHostMat Ap = l == 0 ? X : EtHostMat{st.act[l - 1].data(), ws.ld[l - 1], nullptr};
-    float* gW = a.grads + d.w_off[l];
-    float* gb = a.grads + d.b_off[l];
-    st.c.resize((size_t)out * in);
-    et_host_gemm(out, in, B, D, false, Ap, nullptr, st.c.data());
+}
+// G (+)= dW, G_b (+)= db and every wgrad tile's norm partial
+static inline void mlp_host_wgrad(const MlpDims& d, const MlpHostWs& v, const EtHostMat& X, float* grads, int B, int zero_grad, bool pad) {
+  std::vector<float> c;
+  for (int l = 0; l < d.layers; ++l) {
+    const int in = d.in[l], out = d.out[l], ldd = v.ws.ld[l];
+    float* gW = grads + d.w_off[l];
+    float* gb = grads + d.b_off[l];
+    c.resize((size_t)out * in);
+    et_host_gemm(out, in, B, EtHostMat{v.delta[l], ldd, nullptr}, false, mlp_host_input(v, X, l), nullptr, c.data(), pad);
     const int tn_n = et_tiles(in);
     const int rp = (B + ET_BIAS_RUNS - 1) / ET_BIAS_RUNS;
     for (int tm = 0; tm < et_tiles(out); ++tm)
@@ -314,7 +331,7 @@ static inline void et_host_step(const EtCall& a, int64_t slot0, int B, EtHostSta
             const int o = tm * ET_TILE + (e >> 5), i = tn * ET_TILE + (e & 31);
             if (o >= out || i >= in) continue;
             float* g = gW + (size_t)o * in + i;
-            *g = a.zero_grad ? st.c[(size_t)o * in + i] : *g + st.c[(size_t)o * in + i];
+            *g = zero_grad ? c[(size_t)o * in + i] : *g + c[(size_t)o * in + i];
             s[t] = fma((double)*g, (double)*g, s[t]);
           }
         }
@@ -325,45 +342,71 @@ static inline void et_host_step(const EtCall& a, int64_t slot0, int B, EtHostSta
             float total = 0.0f;
             for (int r = 0; r < ET_BIAS_RUNS; ++r) {
               float run = 0.0f;
-              for (int b = r * rp; b < B && b < (r + 1) * rp; ++b) run = run + st.delta[l][(size_t)b * ldd + o];
+              for (int b = r * rp; b < B && b < (r + 1) * rp; ++b) run = run + v.delta[l][(size_t)b * ldd + o];
               total = r == 0 ? run : total + run;
             }
-            gb[o] = a.zero_grad ? total : gb[o] + total;
+            gb[o] = zero_grad ? total : gb[o] + total;
             s[t] = fma((double)gb[o], (double)gb[o], s[t]);
           }
-        st.partials[d.part_off[l] + tm * tn_n + tn] = et_host_tree<ET_NT>(s);
+        v.partials[d.part_off[l] + tm * tn_n + tn] = et_host_tree<double, ET_NT>(s);
       }
-    if (l == 0) break;
-    // dgrad: delta_{l-1} [B, in]
-    st.c.resize((size_t)B * in);
-    et_host_gemm(B, in, out, D, true, EtHostMat{a.params + d.w_off[l], in, nullptr}, nullptr, st.c.data());
-    const int ldp = ws.ld[l - 1];
-    st.delta[l - 1].assign((size_t)B * ldp, 0.0f);
-    for (int b = 0; b < B; ++b)
-      for (int i = 0; i < in; ++i)
-        st.delta[l - 1][(size_t)b * ldp + i] = st.c[(size_t)b * in + i] * et_act_grad(st.act[l - 1][(size_t)b * ldp + i], l - 1 == 4);
   }
-  // norm and update
+}
+// the clip coefficient from the norm partials; *norm: the norm
+static inline float mlp_host_clip(const MlpDims& d, const MlpHostWs& v, double max_norm, double* norm) {
   double s[ET_NT];
   for (int t = 0; t < ET_NT; ++t) {
     s[t] = 0.0;
-    for (int i = t; i < d.n_partials; i += ET_NT) s[t] = s[t] + st.partials[i];
+    for (int i = t; i < d.n_partials; i += ET_NT) s[t] = s[t] + v.partials[i];
   }
+  return (float)et_clip_coefficient(et_host_tree<double, ET_NT>(s), max_norm, norm);
+}
+
+// ---- K9's own part ---------------------------------------------------------------------------------------------------------------------
+// one batch: forward, loss (-> *loss, status bits OR-ed into *status), and with grads the backward pass, the norm and the update
+static inline void et_host_step(const EtCall& a, int64_t slot0, int B, char* block, float* loss, float* norm_out, int* status) {
+  const MlpDims d = et_dims(a.F);
+  const MlpHostWs v = mlp_host_ws(d, a.batch, block);
+  int flags = mlp_host_rows(v, a.order, slot0, a.N, B) ? ET_STATUS_ORDER : 0;
+  const EtHostMat X = {a.x, a.ldx, v.rows};
+  mlp_host_forward(d, v, X, a.params, B, false);
+  // residual and loss
+  const float scale = (float)(2.0 / (3.0 * B));
+  float slots[ET_BATCH_MAX];
+  for (int b = 0; b < ET_BATCH_MAX; ++b) slots[b] = 0.0f;
+  for (int b = 0; b < B; ++b) {
+    bool cl = false;
+    float q = 0.0f;
+    for (int j = 0; j < ET_LATENT; ++j) {
+      const int t = j / 3;
+      const int row = et_clamp_label(a.labels[(int64_t)v.rows[b] * a.ld_lab + t], a.rows[t], &cl);
+      const float dd = v.act[5][b * ET_LATENT_LD + j] - a.table[t][row * 3 + j % 3];
+      v.delta[5][b * ET_LATENT_LD + j] = dd * scale;
+      q = fmaf(dd, dd, q);
+    }
+    if (cl) flags |= ET_STATUS_LABEL;
+    slots[b] = q;
+  }
+  *loss = et_host_tree<float, ET_BATCH_MAX>(slots) / (float)(3 * B);
+  if (status) *status |= flags;
+  if (!a.grads) return;
+  mlp_host_dgrad(d, v, a.params, B, false);
+  mlp_host_wgrad(d, v, X, a.grads, B, a.zero_grad, false);
   double norm;
-  const float c = (float)et_clip_coefficient(et_host_tree<ET_NT>(s), a.max_norm, &norm);
+  const float c = mlp_host_clip(d, v, a.max_norm, &norm);
   if (norm_out) *norm_out = (float)norm;
   for (int64_t e = 0; e < d.total; ++e) et_update(a.params + e, a.grads + e, c, a.lr, a.wd);
 }
 
-// ceil(n / batch) consecutive batches
+// ceil(n / batch) consecutive batches, in a workspace of its own
 static inline void et_host_run(const EtCall& a) {
-  EtHostState st;
+  std::vector<char> block(et_workspace(a.F, a.batch).net_bytes, 0);
   if (a.status) *a.status = 0;
   int64_t step = 0;
   for (int64_t s0 = 0; s0 < a.n; s0 += a.batch, ++step) {
     const int B = (int)(a.n - s0 < a.batch ? a.n - s0 : a.batch);
     float loss = 0.0f, norm = 0.0f;
-    et_host_step(a, s0, B, st, &loss, &norm, a.status);
+    et_host_step(a, s0, B, block.data(), &loss, &norm, a.status);
     if (a.loss_out) a.loss_out[step] = loss;
     if (a.grads && a.norm_out) a.norm_out[step] = norm;
   }

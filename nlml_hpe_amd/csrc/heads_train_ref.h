@@ -21,7 +21,8 @@
 //   loss     row b: d = pred_b - y_b, q_b = d * d; the q_b (slots b >= B hold +0) through K9's halving tree over 256 slots
 //            (slot t += slot t + stride, stride 128, 64, .. 1); loss = total / float(B); delta_5[b] = d * float(2.0 / B).
 //   norm     f64, K9's way.  A wgrad tile's 512 threads each take the squares of their G (elements t and t + 512 of the tile,
-//            row-major; thread o < 32 of a first-column tile then its G_b) as s = s + g * g (the product of two f32 is exact in f64);
+//            row-major; thread o < 32 of a first-column tile then its G_b) as K9's s = fma(g, g, s) (the product of two f32 is exact in
+//            f64, so s + g * g rounded separately is the same number);
 //            a halving tree over the 512 slots gives the tile's partial.  The 78 partials (layer 0's tiles first, row-major: 4, 32, 32,
 //            8, 2 tiles) are summed by 512 strided chains (i = t, t + 512, ..) and the same tree; n = sqrt(total),
 //            c = min(1, max_norm / (n + 1e-6))  (et_clip_coefficient).
@@ -34,67 +35,27 @@
 //
 // The host form (ht_host_*, below; nlml_heads_train_steps_host) runs this order in plain C++ and, with no tanhf in this network, IS
 // claimed to return the device's bits: every word of the parameters, the state, the losses and the workspace.
+//
+// What is written here is what differs from K9: the network (HT_SHAPE), the loss, Adam and the steps of a call.  The dims and the
+// workspace layout, the forward, wgrad, dgrad and norm of the host form (mlp_host_*, called with pad = true and zero_grad = 1) and of
+// the device (mlp_forward_kernel, mlp_backward_kernel, the loss tail, the clip prologue) are encoder_train_ref.h's, encoder_train_dev.h's
+// and encoder_train.hip's.
 #pragma once
 #include "encoder_train_ref.h"
 
 namespace nlml {
 
 constexpr int HT_LAYERS = 5;
-constexpr int HT_NETS_MAX = 3;           // NLML_HEADS_TRAIN_NETS_MAX
+constexpr int HT_NETS_MAX = MLP_NETS_MAX; // NLML_HEADS_TRAIN_NETS_MAX
 constexpr int HT_R_MAX = 16;             // NLML_HEADS_TRAIN_R_MAX
 constexpr int HT_STATUS_ORDER = 1;       // NLML_HEADS_TRAIN_CLAMPED_ORDER
 constexpr double HT_BETA1 = 0.9, HT_BETA2 = 0.999, HT_EPS = 1e-8;
 
-// widths and the offsets (in floats) of W_l [out,in] and b_l [out] inside a network's contiguous params / grads / m / v buffers
-struct HtDims {
-  int in[HT_LAYERS], out[HT_LAYERS];
-  int64_t w_off[HT_LAYERS], b_off[HT_LAYERS];
-  int64_t total;
-  int part_off[HT_LAYERS];   // first norm partial of layer l's wgrad tiles
-  int n_partials;
-};
-ET_HD HtDims ht_dims(int R) {
-  const int widths[HT_LAYERS] = {128, 256, 128, 64, 1};
-  HtDims d;
-  int64_t off = 0;
-  int fan_in = R, parts = 0;
-  for (int l = 0; l < HT_LAYERS; ++l) {
-    d.in[l] = fan_in; d.out[l] = widths[l];
-    d.w_off[l] = off; off += (int64_t)widths[l] * fan_in;
-    d.b_off[l] = off; off += widths[l];
-    d.part_off[l] = parts; parts += et_tiles(widths[l]) * et_tiles(fan_in);
-    fan_in = widths[l];
-  }
-  d.total = off;
-  d.n_partials = parts;
-  return d;
-}
-
-// the workspace, byte offsets.  Network i owns the block [i net_bytes, (i + 1) net_bytes); inside it: the norm partials (f64), the
-// batch's resolved dataset rows (i32[256]), A_1..A_5 and delta_1..delta_5 (index l - 1; A_5 = pred), each dense [batch, out[l-1]] and
-// padded to 16 bytes.  It holds the network's LAST step; words outside these ranges, and rows b >= B of that step, are never written.
-struct HtWorkspace {
-  size_t partials, rows, act[HT_LAYERS], delta[HT_LAYERS], net_bytes;
-  int ld[HT_LAYERS];
-};
-ET_HD HtWorkspace ht_workspace(int R, int batch) {
-  const HtDims d = ht_dims(R);
-  HtWorkspace w;
-  size_t off = 0;
-  w.partials = off; off += (size_t)((d.n_partials + 1) / 2 * 2) * 8;
-  w.rows = off; off += (size_t)ET_BATCH_MAX * 4;
-  for (int l = 0; l < HT_LAYERS; ++l) {
-    w.ld[l] = d.out[l];
-    w.act[l] = off; off += (size_t)batch * w.ld[l] * 4;
-    off = (off + 15) / 16 * 16;
-  }
-  for (int l = 0; l < HT_LAYERS; ++l) {
-    w.delta[l] = off; off += (size_t)batch * w.ld[l] * 4;
-    off = (off + 15) / 16 * 16;
-  }
-  w.net_bytes = off;
-  return w;
-}
+// the network, its dims and its workspace are K9's structs (encoder_train_ref.h); network i of a call owns the workspace block
+// [i net_bytes, (i + 1) net_bytes), every A_l and delta_l dense
+constexpr MlpShape HT_SHAPE = {HT_LAYERS, {128, 256, 128, 64, 1}, -1, 1};
+ET_HD MlpDims ht_dims(int R) { return mlp_dims(HT_SHAPE, R); }
+ET_HD MlpWorkspace ht_workspace(int R, int batch) { return mlp_workspace(ht_dims(R), batch); }
 
 // ---- separately rounded f32 operations, the same text for both compilers.  The device's *_rn intrinsics are NOT used: without
 // OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define __fmul_rn(x, y) as x * y, which the device compiler's default
@@ -178,106 +139,31 @@ static inline int ht_batch_rows(const HtCall& c, int i, int64_t s) {
 // ---- the host form ---------------------------------------------------------------------------------------------------------------
 namespace nlml {
 
-// one batch of one network into its workspace block `wsb`: forward, loss, and (c.train) backward, norm and Adam with step count t
+// one batch of one network into its workspace block `wsb`: forward, loss, and (c.train) backward, norm and Adam with step count t.
+// The shared part (mlp_host_*, encoder_train_ref.h) with pad = true: the device's zero operands.
 static inline void ht_host_step(const HtCall& c, int i, int64_t slot0, int B, int64_t t, char* wsb, float* loss, float* norm_out, int* status) {
   const HtNet& a = c.net[i];
-  const HtDims d = ht_dims(c.R);
-  const HtWorkspace ws = ht_workspace(c.R, c.batch);
-  int32_t* rows = reinterpret_cast<int32_t*>(wsb + ws.rows);
-  double* partials = reinterpret_cast<double*>(wsb + ws.partials);
-  float* act[HT_LAYERS];
-  float* delta[HT_LAYERS];
-  for (int l = 0; l < HT_LAYERS; ++l) {
-    act[l] = reinterpret_cast<float*>(wsb + ws.act[l]);
-    delta[l] = reinterpret_cast<float*>(wsb + ws.delta[l]);
-  }
-  int flags = 0;
-  for (int b = 0; b < B; ++b) {
-    bool cl;
-    rows[b] = et_resolve_row(a.order, slot0 + b, a.N, &cl);
-    if (cl) flags |= HT_STATUS_ORDER;
-  }
-  if (status) *status |= flags;
-  const EtHostMat X = {a.x, a.ldx, rows};
-  std::vector<float> wt, cm;
-  // forward
-  for (int l = 0; l < HT_LAYERS; ++l) {
-    const int K = d.in[l], N = d.out[l];
-    const float* W = a.params + d.w_off[l];
-    wt.resize((size_t)K * N);
-    for (int o = 0; o < N; ++o)
-      for (int k = 0; k < K; ++k) wt[(size_t)k * N + o] = W[(size_t)o * K + k];
-    const EtHostMat Am = l == 0 ? X : EtHostMat{act[l - 1], ws.ld[l - 1], nullptr};
-    et_host_gemm(B, N, K, Am, true, EtHostMat{wt.data(), N, nullptr}, a.params + d.b_off[l], act[l], true);
-    if (l < HT_LAYERS - 1)
-      for (size_t e = 0; e < (size_t)B * N; ++e) act[l][e] = act[l][e] > 0.0f ? act[l][e] : 0.0f;
-  }
+  const MlpDims d = ht_dims(c.R);
+  const MlpHostWs v = mlp_host_ws(d, c.batch, wsb);
+  const bool clamped = mlp_host_rows(v, a.order, slot0, a.N, B);
+  if (status && clamped) *status |= HT_STATUS_ORDER;
+  const EtHostMat X = {a.x, a.ldx, v.rows};
+  mlp_host_forward(d, v, X, a.params, B, true);
   // residual and loss
-  {
-    const float scale = (float)(2.0 / B);
-    float slots[ET_BATCH_MAX];
-    for (int b = 0; b < ET_BATCH_MAX; ++b) slots[b] = 0.0f;
-    for (int b = 0; b < B; ++b) {
-      float dd;
-      slots[b] = ht_loss_q(act[HT_LAYERS - 1][b], a.y[rows[b]], &dd);
-      if (c.train) delta[HT_LAYERS - 1][b] = ht_mul(dd, scale);
-    }
-    for (int stride = ET_BATCH_MAX / 2; stride >= 1; stride /= 2)
-      for (int s = 0; s < stride; ++s) slots[s] = slots[s] + slots[s + stride];
-    *loss = ht_div(slots[0], (float)B);
+  const float scale = (float)(2.0 / B);
+  float slots[ET_BATCH_MAX];
+  for (int b = 0; b < ET_BATCH_MAX; ++b) slots[b] = 0.0f;
+  for (int b = 0; b < B; ++b) {
+    float dd;
+    slots[b] = ht_loss_q(v.act[HT_LAYERS - 1][b], a.y[v.rows[b]], &dd);
+    if (c.train) v.delta[HT_LAYERS - 1][b] = ht_mul(dd, scale);
   }
+  *loss = ht_div(et_host_tree<float, ET_BATCH_MAX>(slots), (float)B);
   if (!c.train) return;
-  // backward
-  for (int l = HT_LAYERS - 1; l >= 0; --l) {
-    const int in = d.in[l], out = d.out[l], ldd = ws.ld[l];
-    const EtHostMat D = {delta[l], ldd, nullptr};
-    const EtHostMat Ap = l == 0 ? X : EtHostMat{act[l - 1], ws.ld[l - 1], nullptr};
-    float* gW = a.grads + d.w_off[l];
-    float* gb = a.grads + d.b_off[l];
-    et_host_gemm(out, in, B, D, false, Ap, nullptr, gW, true);
-    const int tn_n = et_tiles(in);
-    const int rp = (B + ET_BIAS_RUNS - 1) / ET_BIAS_RUNS;
-    for (int tm = 0; tm < et_tiles(out); ++tm)
-      for (int tn = 0; tn < tn_n; ++tn) {
-        double s[ET_NT];
-        for (int q = 0; q < ET_NT; ++q) {
-          s[q] = 0.0;
-          for (int e = q; e < ET_TILE * ET_TILE; e += ET_NT) {
-            const int o = tm * ET_TILE + (e >> 5), ii = tn * ET_TILE + (e & 31);
-            if (o >= out || ii >= in) continue;
-            const double g = gW[(size_t)o * in + ii];
-            s[q] = s[q] + g * g;
-          }
-        }
-        if (tn == 0)
-          for (int q = 0; q < ET_TILE; ++q) {
-            const int o = tm * ET_TILE + q;
-            if (o >= out) continue;
-            float total = 0.0f;
-            for (int r = 0; r < ET_BIAS_RUNS; ++r) {
-              float run = 0.0f;
-              for (int b = r * rp; b < B && b < (r + 1) * rp; ++b) run = run + delta[l][(size_t)b * ldd + o];
-              total = r == 0 ? run : total + run;
-            }
-            gb[o] = total;
-            s[q] = s[q] + (double)total * (double)total;
-          }
-        partials[d.part_off[l] + tm * tn_n + tn] = et_host_tree<ET_NT>(s);
-      }
-    if (l == 0) break;
-    // dgrad: delta_{l-1} [B, in]
-    cm.resize((size_t)B * in);
-    et_host_gemm(B, in, out, D, true, EtHostMat{a.params + d.w_off[l], in, nullptr}, nullptr, cm.data(), true);
-    for (size_t e = 0; e < (size_t)B * in; ++e) delta[l - 1][e] = cm[e] * et_act_grad(act[l - 1][e], false);
-  }
-  // norm, clip and Adam
-  double s[ET_NT];
-  for (int q = 0; q < ET_NT; ++q) {
-    s[q] = 0.0;
-    for (int e = q; e < d.n_partials; e += ET_NT) s[q] = s[q] + partials[e];
-  }
+  mlp_host_dgrad(d, v, a.params, B, true);
+  mlp_host_wgrad(d, v, X, a.grads, B, 1, true);
   double norm;
-  const float cc = (float)et_clip_coefficient(et_host_tree<ET_NT>(s), c.max_norm, &norm);
+  const float cc = mlp_host_clip(d, v, c.max_norm, &norm);
   if (norm_out) *norm_out = (float)norm;
   const HtAdam k = ht_adam_constants(c.weight_decay);
   float ss, s2;
@@ -287,7 +173,7 @@ static inline void ht_host_step(const HtCall& c, int i, int64_t slot0, int B, in
 
 // every step of a call, network after network; workspace: the caller's (the layout above) or NULL
 static inline void ht_host_run(const HtCall& c, void* workspace) {
-  const HtWorkspace ws = ht_workspace(c.R, c.batch);
+  const MlpWorkspace ws = ht_workspace(c.R, c.batch);
   std::vector<char> own;
   if (!workspace) {
     own.assign(ws.net_bytes * c.n_nets, 0);

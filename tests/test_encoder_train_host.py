@@ -194,6 +194,7 @@ def test_host_form_under_asan_ubsan(tmp_path, repo_root):
     res = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
     assert res.returncode == 0, res.stdout + res.stderr
     assert "encoder train host ok" in res.stdout
+    assert "heads train host ok" in res.stdout, "the K10 case (two networks in an exact-size workspace) runs the shared host functions too"
 
 
 # ---- the trainer on the host backend -------------------------------------------------------------------------------------------------

@@ -19,7 +19,7 @@ def main():
     with open(args.trace, newline="") as f:
         for r in csv.DictReader(f):
             name = r.get("Kernel_Name") or r.get("kernel_name") or ""
-            if "et_" not in name:
+            if "et_" not in name and "mlp_" not in name:   # K9's own kernels, and the forward / backward kernels it shares with K10
                 continue
             grid = r.get("Grid_Size_X") or r.get("Grid_Size") or r.get("grid_size_x") or "?"
             wg = r.get("Workgroup_Size_X") or r.get("Workgroup_Size") or "?"

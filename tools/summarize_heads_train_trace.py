@@ -18,7 +18,7 @@ def main():
     with open(args.trace, newline="") as f:
         for r in csv.DictReader(f):
             name = r.get("Kernel_Name") or r.get("kernel_name") or ""
-            if "ht_" not in name:
+            if "ht_" not in name and "mlp_" not in name:   # K10's own kernels, and the forward / backward kernels it shares with K9
                 continue
             grid = (r.get("Grid_Size_X") or r.get("Grid_Size") or "?", r.get("Grid_Size_Y") or "?")
             wg = r.get("Workgroup_Size_X") or r.get("Workgroup_Size") or "?"
