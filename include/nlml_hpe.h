@@ -613,6 +613,37 @@ int nlml_project_identity_ex(const float* A, int64_t I, int64_t K, const double*
 int nlml_project_pose_ex(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
                          int rp, const double* Ur, int rr, void* out, int out_f64, void* stream);
 
+/* K11: expand a Tucker model and compare it with the tensor in one pass -- tensorly's tucker_to_tensor and the reconstruction error
+ * norm(X - reconstructed) / norm(X) of TD_main.py:221-224, without a second tensor of X's size.
+ *   X     f32[I,ny,np,nr,M] or NULL (expand only: xhat is required, sums and res_id are not written, no workspace is needed)
+ *   W     f32[R,ry,rp,rr,M];  U_id f64[I,R], Uy f64[ny,ry], Up f64[np,rp], Ur f64[nr,rr], row-major (column r = the r-th vector)
+ *   1 <= R <= NLML_TUCKER_RANK_MAX, ry, rp, rr in 1..NLML_POSE_RANK_MAX, ny, np, nr in 1..NLML_POSE_BINS_MAX; all offsets are 64-bit
+ *   sums   f64[2] = {sum (X - X_hat)^2, sum X^2}: the error is sqrt(sums[0] / sums[1]).  Required when X is given.
+ *   res_id f64[I] or NULL: each identity's sum of squared residuals
+ *   xhat   f32[I,ny,np,nr,M] or NULL: X_hat itself, rounded once (tucker_to_tensor; with I = 1 and a row of U_id, one identity)
+ * The order (csrc/tucker_residual_ref.h holds it in code).  Per element, every chain ascending from +0.0 and every fma f64:
+ *   v[b][c][d] = fma(U_id[i][a], (double)W[a][b][c][d][m], v[b][c][d]) over a;  per yaw bin y: ty[c][d] = fma(Uy[y][b], v[b][c][d],
+ *   ty[c][d]) over b;  per pitch bin p: tp[d] = fma(Up[p][c], ty[c][d], tp[d]) over c;  per roll bin r: xhat = fma(Ur[r][d], tp[d],
+ *   xhat) over d;  e = (double)X[i][y][p][r][m] - xhat;  s[i][m] = fma(e, e, s[i][m]), q[i][m] = fma(x, x, q[i][m]) over the cells
+ *   (y, p, r) in row-major order.  The sums: column group g of G = ceil(M / 64) holds the columns 64 g + l, l = 0..63 (a column past
+ *   M counts +0.0); its 64 values are added by the halving tree t[l] = t[l] + t[l + h] for l < h, h = 32, 16, .., 1, and t[0] is the
+ *   partial P[i][g] in the workspace (f64[I][G][2], s and q).  A second launch of one workgroup of 256 threads: thread t takes the
+ *   identities t, t + 256, .. ascending; res_id[i] = (0.0 + P[i][0]) + .. + P[i][G-1]; the thread adds its res_id ascending from
+ *   +0.0; the 256 totals are added by the same halving tree, h = 128, .., 1.  No floating-point atomics; two calls give the same bits.
+ * nlml_tucker_residual_host runs the same header on HOST buffers in plain C++ (no GPU involved; the workspace is a host buffer of the
+ * same size) and returns the same bits.
+ * Checks, the K7 list in the K7 order, each NLML_E_BADARG with a message and before any GPU call: a NULL required buffer (W, the four
+ * factors, X or xhat; with X: sums and the workspace); an extent < 1 or a rank or bin count beyond its limit; a product of extents
+ * beyond 64-bit byte offsets; a pointer that is not aligned to its element (4 bytes f32, 8 bytes f64 and workspace); with X, a
+ * workspace shorter than nlml_tucker_residual_workspace_bytes (which returns 0 for a shape the entry point refuses). */
+size_t nlml_tucker_residual_workspace_bytes(int64_t I, int ny, int np, int nr, int64_t M);
+int nlml_tucker_residual(const float* X, const float* W, const double* U_id, const double* Uy, const double* Up, const double* Ur,
+                         int64_t I, int ny, int np, int nr, int64_t M, int R, int ry, int rp, int rr, double* sums, double* res_id,
+                         float* xhat, void* workspace, size_t workspace_bytes, void* stream);
+int nlml_tucker_residual_host(const float* h_X, const float* h_W, const double* h_U_id, const double* h_Uy, const double* h_Up,
+                              const double* h_Ur, int64_t I, int ny, int np, int nr, int64_t M, int R, int ry, int rp, int rr,
+                              double* h_sums, double* h_res_id, float* h_xhat, void* h_workspace, size_t workspace_bytes);
+
 /* K8: the cosine fit of the pose factors -- a batch of independent fits of  a cos(b radians(w) + c) + d  to a column, each a whole
  * Powell minimisation, in one launch.  Replaces TD_Trainer.Train's scipy.optimize.minimize(objective, guess, method='Powell') per
  * column of U_yaw, U_pitch and U_roll (TD_Trainer.py:37-42,70-93,320-322); its results are the optimized_* rows of Trained_data.npz.

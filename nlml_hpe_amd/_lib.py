@@ -121,6 +121,12 @@ SYMBOLS = {
     "nlml_project_identity_ex": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "nlml_project_pose_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_void_p, C.c_int] * 3
                              + [C.c_void_p, C.c_int, C.c_void_p]),
+    # K11 (expand and compare): X, W, U_id, Uy, Up, Ur, I, ny, np, nr, M, R, ry, rp, rr, sums, res_id, xhat, ws, ws_bytes[, stream]
+    "nlml_tucker_residual_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "nlml_tucker_residual": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_int] * 4
+                             + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "nlml_tucker_residual_host": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_int] * 4
+                                  + [C.c_void_p] * 4 + [C.c_size_t]),
     # K8 (cosine fit): y, w_deg, ld, [n,] h_n, C, x0, xtol, ftol, x, fun, nfev, nit, status[, stream] | y, w_deg, n, params, N, out[, stream]
     "nlml_cosine_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double]
                         + [C.c_void_p] * 6),

@@ -21,6 +21,7 @@
 #include "powell.h"
 #include "rotate_ref.h"
 #include "tucker_grad_ref.h"
+#include "tucker_residual_ref.h"
 
 namespace nlml {
 static thread_local char g_err[256] = "";
@@ -514,6 +515,51 @@ int nlml_project_pose_ex(const void* X, int x_f64, int64_t I, int ny, int np, in
   if (!aligned(X, x_f64 ? 8 : 4) || !aligned(out, out_f64 ? 8 : 4) || !aligned(Uy, 8) || !aligned(Up, 8) || !aligned(Ur, 8))
     return refuse(NLML_E_BADARG, who, "X and out must be aligned to their element (4 bytes f32, 8 bytes f64), the factors 8-byte aligned");
   return launch_project_pose(X, x_f64 != 0, I, ny, np, nr, M, Uy, ry, Up, rp, Ur, rr, out, out_f64 != 0, stream);
+}
+
+// ---- K11: expand and compare in one pass (tucker_residual.hip) -----------------------------------------
+static bool k11_shape_ok(int64_t I, int ny, int np, int nr, int64_t M) {
+  return k7_bins_ok(ny, np, nr) && k7_tensor_ok(I, ny, np, nr, M) && M <= INT64_MAX / (8 * 27 * NLML_TUCKER_RANK_MAX);
+}
+size_t nlml_tucker_residual_workspace_bytes(int64_t I, int ny, int np, int nr, int64_t M) {
+  return k11_shape_ok(I, ny, np, nr, M) ? tucker_residual_workspace_bytes(I, M) : 0;
+}
+
+// the checks of include/nlml_hpe.h in their stated order, shared by the device and the host forms
+static int check_tucker_residual(const char* who, const TrArgs& a, int ry, int rp, int rr, const double* sums, const double* res_id,
+                                 const void* workspace, size_t workspace_bytes) {
+  if (!a.W || !a.Uid || !a.Uy || !a.Up || !a.Ur || (!a.X && !a.xhat) || (a.X && (!sums || !workspace)))
+    return refuse(NLML_E_BADARG, who, "null buffer (W, the four factors, X or xhat; with X: sums and the workspace)");
+  if (a.I < 1 || a.M < 1) return refuse(NLML_E_BADARG, who, "I < 1 or M < 1");
+  if (!k7_bins_ok(a.ny, a.np, a.nr)) return refuse(NLML_E_BADARG, who, "ny, np, nr outside 1..NLML_POSE_BINS_MAX (32)");
+  if (a.R < NLML_TUCKER_RANK_MIN || a.R > NLML_TUCKER_RANK_MAX) return refuse(NLML_E_BADARG, who, "R outside 1..NLML_TUCKER_RANK_MAX (16)");
+  if (ry < 1 || ry > NLML_POSE_RANK_MAX || rp < 1 || rp > NLML_POSE_RANK_MAX || rr < 1 || rr > NLML_POSE_RANK_MAX)
+    return refuse(NLML_E_BADARG, who, "ry, rp, rr outside 1..NLML_POSE_RANK_MAX (3)");
+  if (!k11_shape_ok(a.I, a.ny, a.np, a.nr, a.M)) return refuse(NLML_E_BADARG, who, "tensor too large for 64-bit byte offsets");
+  if (!aligned(a.X, 4) || !aligned(a.W, 4) || !aligned(a.xhat, 4) || !aligned(a.Uid, 8) || !aligned(a.Uy, 8) || !aligned(a.Up, 8) ||
+      !aligned(a.Ur, 8) || !aligned(sums, 8) || !aligned(res_id, 8) || !aligned(workspace, 8))
+    return refuse(NLML_E_BADARG, who, "X, W and xhat must be 4-byte aligned, the factors, sums, res_id and the workspace 8-byte aligned");
+  if (a.X && workspace_bytes < tucker_residual_workspace_bytes(a.I, a.M))
+    return refuse(NLML_E_BADARG, who, "workspace too small (nlml_tucker_residual_workspace_bytes)");
+  return 0;
+}
+
+int nlml_tucker_residual(const float* X, const float* W, const double* U_id, const double* Uy, const double* Up, const double* Ur,
+                         int64_t I, int ny, int np, int nr, int64_t M, int R, int ry, int rp, int rr, double* sums, double* res_id,
+                         float* xhat, void* workspace, size_t workspace_bytes, void* stream) {
+  const TrArgs a{X, W, U_id, Uy, Up, Ur, xhat, I, M, R, ny, np, nr};
+  if (const int rc = check_tucker_residual("tucker_residual", a, ry, rp, rr, sums, res_id, workspace, workspace_bytes)) return rc;
+  return launch_tucker_residual(a, ry, rp, rr, sums, res_id, workspace, stream);
+}
+
+// the same operation order (tucker_residual_ref.h) on host buffers: plain C++, no HIP call
+int nlml_tucker_residual_host(const float* h_X, const float* h_W, const double* h_U_id, const double* h_Uy, const double* h_Up,
+                              const double* h_Ur, int64_t I, int ny, int np, int nr, int64_t M, int R, int ry, int rp, int rr,
+                              double* h_sums, double* h_res_id, float* h_xhat, void* h_workspace, size_t workspace_bytes) {
+  const TrArgs a{h_X, h_W, h_U_id, h_Uy, h_Up, h_Ur, h_xhat, I, M, R, ny, np, nr};
+  if (const int rc = check_tucker_residual("tucker_residual_host", a, ry, rp, rr, h_sums, h_res_id, h_workspace, workspace_bytes)) return rc;
+  tr_host(a, ry, rp, rr, static_cast<double*>(h_workspace), h_sums, h_res_id);
+  return 0;
 }
 
 // ---- K5 evaluation ---------------------------------------------------------------------------------

@@ -139,6 +139,11 @@ int launch_project_identity(const float* A, int64_t I, int64_t K, const double* 
 int launch_project_pose(const void* X, int x_f64, int64_t I, int ny, int np, int nr, int64_t M, const double* Uy, int ry, const double* Up,
                         int rp, const double* Ur, int rr, void* out, int out_f64, void* stream);
 
+// tucker_residual.hip (K11): the call is checked by the caller (abi.cpp); TrArgs is tucker_residual_ref.h's.  ws unused when a.X is NULL.
+struct TrArgs;
+size_t tucker_residual_workspace_bytes(int64_t I, int64_t M);
+int launch_tucker_residual(const TrArgs& a, int ry, int rp, int rr, double* sums, double* res_id, void* ws, void* stream);
+
 // cosine_fit.hip (K8): C fits, one wave each; n i32[C] on the device.  The arguments are checked by the caller (abi.cpp).
 int launch_cosine_fit(const double* y, const double* w_deg, int64_t ld, const int32_t* n, int64_t C, const double* x0, double xtol,
                       double ftol, double* x, double* fun, int32_t* nfev, int32_t* nit, int32_t* status, void* stream);

@@ -606,6 +606,52 @@ at::Tensor project_pose(const at::Tensor& X_, const std::optional<at::Tensor>& U
   return out;
 }
 
+// K11: X f32[I,ny,np,nr,M] or None (expand only), W f32[R,ry,rp,rr,M], the four factors f64[n,r] -> (sums f64[2], res_id f64[I],
+// xhat f32[I,ny,np,nr,M]); an output that is not asked for (or, without X, not computed) is an empty tensor
+std::tuple<at::Tensor, at::Tensor, at::Tensor> tucker_residual(const std::optional<at::Tensor>& X_, const at::Tensor& W_, const at::Tensor& Uid_,
+                                                               const at::Tensor& Uy_, const at::Tensor& Up_, const at::Tensor& Ur_,
+                                                               bool want_res_id, bool want_xhat) {
+  need(W_, "W", at::kFloat);
+  TORCH_CHECK(W_.dim() == 5, "W: expected [R,ry,rp,rr,M], got ", W_.sizes());
+  TORCH_CHECK(W_.size(0) >= NLML_TUCKER_RANK_MIN && W_.size(0) <= NLML_TUCKER_RANK_MAX, "W: identity rank outside 1..", NLML_TUCKER_RANK_MAX);
+  const at::Tensor* const in[] = {&Uid_, &Uy_, &Up_, &Ur_};
+  const char* const names[] = {"U_id", "U_yaw", "U_pitch", "U_roll"};
+  at::Tensor U[4];
+  for (int k = 0; k < 4; ++k) {
+    need(*in[k], names[k], at::kDouble);
+    same_device(W_, *in[k], names[k]);
+    TORCH_CHECK(in[k]->dim() == 2 && in[k]->size(0) >= 1 && in[k]->size(1) == W_.size(k), names[k], ": expected [n,", W_.size(k), "], got ",
+                in[k]->sizes());
+    TORCH_CHECK(k == 0 || (in[k]->size(1) <= NLML_POSE_RANK_MAX && in[k]->size(0) <= NLML_POSE_BINS_MAX), names[k], ": at most ",
+                NLML_POSE_BINS_MAX, " bins and rank ", NLML_POSE_RANK_MAX, ", got ", in[k]->sizes());
+    U[k] = in[k]->contiguous();
+  }
+  const at::Tensor W = W_.contiguous();
+  const int64_t I = U[0].size(0), ny = U[1].size(0), np = U[2].size(0), nr = U[3].size(0), M = W.size(4);
+  TORCH_CHECK(M >= 1, "W: no columns");
+  at::Tensor X;
+  if (X_.has_value()) {
+    X = need_tensor5(*X_, "X");
+    same_device(W, X, "X");
+    TORCH_CHECK(X.size(0) == I && X.size(1) == ny && X.size(2) == np && X.size(3) == nr && X.size(4) == M,
+                "X: expected the factors' rows by W's columns, got ", X.sizes());
+  } else {
+    want_xhat = true;
+    want_res_id = false;
+  }
+  const auto f64 = W.options().dtype(at::kDouble);
+  at::Tensor sums = at::empty({X.defined() ? 2 : 0}, f64), res_id = at::empty({want_res_id ? I : 0}, f64);
+  at::Tensor xhat = want_xhat ? at::empty({I, ny, np, nr, M}, W.options()) : at::empty({0}, W.options());
+  at::Tensor ws = at::empty({ws_doubles(X.defined() ? nlml_tucker_residual_workspace_bytes(I, (int)ny, (int)np, (int)nr, M) : 0)}, f64);
+  OnDevice dev(W);
+  check(nlml_tucker_residual(X.defined() ? X.data_ptr<float>() : nullptr, W.data_ptr<float>(), U[0].data_ptr<double>(), U[1].data_ptr<double>(),
+                             U[2].data_ptr<double>(), U[3].data_ptr<double>(), I, (int)ny, (int)np, (int)nr, M, (int)W.size(0), (int)W.size(1),
+                             (int)W.size(2), (int)W.size(3), X.defined() ? sums.data_ptr<double>() : nullptr,
+                             want_res_id ? res_id.data_ptr<double>() : nullptr, want_xhat ? xhat.data_ptr<float>() : nullptr, ws.data_ptr(),
+                             (size_t)ws.numel() * 8, dev.stream), "nlml_tucker_residual");
+  return {sums, res_id, xhat};
+}
+
 // ---- shapes only (Meta backend: tracing / fake tensors) -------------------------------------------------------------
 at::Tensor mode_gram_meta(const at::Tensor& A) { return at::empty({A.size(0), A.size(0)}, A.options().dtype(at::kDouble)); }
 std::tuple<at::Tensor, at::Tensor, at::Tensor> pose_grams_meta(const at::Tensor& X) {
@@ -617,6 +663,14 @@ at::Tensor project_pose_meta(const at::Tensor& X, const std::optional<at::Tensor
                              const std::optional<at::Tensor>& Ur) {
   return at::empty({X.size(0), Uy.has_value() ? Uy->size(1) : X.size(1), Up.has_value() ? Up->size(1) : X.size(2),
                     Ur.has_value() ? Ur->size(1) : X.size(3), X.size(4)}, X.options());
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> tucker_residual_meta(const std::optional<at::Tensor>& X, const at::Tensor& W, const at::Tensor& Uid,
+                                                                    const at::Tensor& Uy, const at::Tensor& Up, const at::Tensor& Ur,
+                                                                    bool want_res_id, bool want_xhat) {
+  const auto f64 = W.options().dtype(at::kDouble);
+  const bool x = X.has_value();
+  return {at::empty({x ? 2 : 0}, f64), at::empty({x && want_res_id ? Uid.size(0) : 0}, f64),
+          want_xhat || !x ? at::empty({Uid.size(0), Uy.size(0), Up.size(0), Ur.size(0), W.size(4)}, W.options()) : at::empty({0}, W.options())};
 }
 at::Tensor normalize_ipd_meta(const at::Tensor& raw, bool) { return at::empty({raw.size(0), F_REF}, raw.options()); }
 at::Tensor normalize_centroid_meta(const at::Tensor& raw) { return at::empty({raw.size(0), F_REF}, raw.options()); }
@@ -713,6 +767,8 @@ TORCH_LIBRARY(nlml_hpe, m) {
   m.def("pose_grams(Tensor X) -> (Tensor, Tensor, Tensor)");
   m.def("project_identity(Tensor A, Tensor U) -> Tensor");
   m.def("project_pose(Tensor X, Tensor? U_yaw, Tensor? U_pitch, Tensor? U_roll) -> Tensor");
+  m.def("tucker_residual(Tensor? X, Tensor W, Tensor U_id, Tensor U_yaw, Tensor U_pitch, Tensor U_roll, bool want_res_id=False, "
+        "bool want_xhat=False) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CUDA key
@@ -739,6 +795,7 @@ TORCH_LIBRARY_IMPL(nlml_hpe, CUDA, m) {   // ROCm tensors dispatch on torch's CU
   m.impl("pose_grams", &pose_grams);
   m.impl("project_identity", &project_identity);
   m.impl("project_pose", &project_pose);
+  m.impl("tucker_residual", &tucker_residual);
 }
 
 TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
@@ -765,4 +822,5 @@ TORCH_LIBRARY_IMPL(nlml_hpe, Meta, m) {
   m.impl("pose_grams", &pose_grams_meta);
   m.impl("project_identity", &project_identity_meta);
   m.impl("project_pose", &project_pose_meta);
+  m.impl("tucker_residual", &tucker_residual_meta);
 }

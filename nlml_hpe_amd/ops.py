@@ -545,6 +545,59 @@ def project_pose(X: torch.Tensor, U_yaw=None, U_pitch=None, U_roll=None, out_dty
     return out
 
 
+# ---- K11: expand a Tucker model and compare it with the tensor in one pass (csrc/tucker_residual.hip) ---------------------------
+def _tucker_model(W: torch.Tensor, U_id: torch.Tensor, U_yaw: torch.Tensor, U_pitch: torch.Tensor, U_roll: torch.Tensor):
+    """-> (W, [U_id, U_yaw, U_pitch, U_roll]) contiguous, checked against each other: W f32[R,ry,rp,rr,M], every factor f64[n,r]."""
+    _need_cuda(W, "W", torch.float32)
+    if W.dim() != 5 or min(W.shape) < 1:
+        raise ValueError(f"W: expected a non-empty [R,ry,rp,rr,M], got {tuple(W.shape)}")
+    if not _lib.TUCKER_RANK_MIN <= W.shape[0] <= _lib.TUCKER_RANK_MAX or max(W.shape[1:4]) > _lib.POSE_RANK_MAX:
+        raise ValueError(f"W: identity rank in [{_lib.TUCKER_RANK_MIN}, {_lib.TUCKER_RANK_MAX}] and pose ranks <= {_lib.POSE_RANK_MAX} "
+                         f"expected, got {tuple(W.shape)}")
+    Us = []
+    for k, (U, name) in enumerate(((U_id, "U_id"), (U_yaw, "U_yaw"), (U_pitch, "U_pitch"), (U_roll, "U_roll"))):
+        _need_cuda(U, name, torch.float64)
+        if U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != W.shape[k]:
+            raise ValueError(f"{name}: expected [n, {W.shape[k]}] (W is {tuple(W.shape)}), got {tuple(U.shape)}")
+        if k and U.shape[0] > _lib.POSE_BINS_MAX:
+            raise ValueError(f"{name}: at most {_lib.POSE_BINS_MAX} bins per pose mode, got {U.shape[0]}")
+        Us.append(U.contiguous())
+    return W.contiguous(), Us
+
+
+def tucker_residual(X, W: torch.Tensor, U_id: torch.Tensor, U_yaw: torch.Tensor, U_pitch: torch.Tensor, U_roll: torch.Tensor,
+                    want_res_id: bool = False, want_xhat: bool = False):
+    """K11: X f32[I,ny,np,nr,M] against the Tucker model (W f32[R,ry,rp,rr,M], factors f64[n,r]) in one pass over X ->
+    (sums f64[2] = {sum (X - X_hat)^2, sum X^2}, res_id f64[I] or None, xhat f32[I,ny,np,nr,M] or None); the relative reconstruction
+    error is sqrt(sums[0] / sums[1]).  X = None: expand only -> (None, None, xhat).  The same bits on every call."""
+    W, Us = _tucker_model(W, U_id, U_yaw, U_pitch, U_roll)
+    shape = tuple(U.shape[0] for U in Us) + (W.shape[4],)
+    if X is None:
+        want_xhat, want_res_id = True, False
+    else:
+        X = _tensor5(X)
+        if X.dtype != torch.float32 or tuple(X.shape) != shape:
+            raise ValueError(f"X: expected float32 {shape} (the factors' rows by W's columns), got {X.dtype} {tuple(X.shape)}")
+    dev = W.device
+    I, ny, np_, nr, M = shape
+    sums = torch.empty((2,), dtype=torch.float64, device=dev) if X is not None else None
+    res_id = torch.empty((I,), dtype=torch.float64, device=dev) if want_res_id else None
+    xhat = torch.empty(shape, dtype=torch.float32, device=dev) if want_xhat else None
+    ws = _k7_workspace(_lib.lib().nlml_tucker_residual_workspace_bytes(I, ny, np_, nr, M), dev) if X is not None else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _on_device_of(("W", W), ("X", X), ("U_id", Us[0]), ("U_yaw", Us[1]), ("U_pitch", Us[2]), ("U_roll", Us[3])) as stream:
+        _lib.check(_lib.lib().nlml_tucker_residual(ptr(X), W.data_ptr(), *[U.data_ptr() for U in Us], I, ny, np_, nr, M, *W.shape[:4],
+                                                   ptr(sums), ptr(res_id), ptr(xhat), ptr(ws), ws.numel() * 8 if ws is not None else 0,
+                                                   stream), "nlml_tucker_residual")
+    return sums, res_id, xhat
+
+
+def tucker_to_tensor(W: torch.Tensor, U_id: torch.Tensor, U_yaw: torch.Tensor, U_pitch: torch.Tensor, U_roll: torch.Tensor) -> torch.Tensor:
+    """K11's expand-only form: W x_1 U_id x_2 U_yaw x_3 U_pitch x_4 U_roll -> f32[I,ny,np,nr,M], f64 sums, one rounding (tensorly's
+    tucker_to_tensor; a one-row U_id gives one identity)."""
+    return tucker_residual(None, W, U_id, U_yaw, U_pitch, U_roll)[2]
+
+
 # ---- K8: the cosine fit of the pose factors (csrc/cosine_fit.hip; the driver is nlml_hpe_amd/TD_Trainer.py) -------------------
 def _fit_rows(y: torch.Tensor, w_deg: torch.Tensor):
     _need_cuda(y, "y", torch.float64)
@@ -951,7 +1004,7 @@ def _load_torch_ops():
     for name in ("normalize_ipd", "normalize_centroid", "encoder_heads_fwd", "landmarks_to_pose", "encoder_heads_fwd_small", "landmarks_to_pose_small",
                  "landmarks_to_pose_valid", "tucker_objective", "tucker_gradient", "tucker_powell", "video_post", "cosine_table", "pose_eval",
                  "pose_eval_merge", "compose_rotation_tensor", "rotate_landmarks", "mode_gram", "pose_grams", "project_identity",
-                 "project_pose", "cosine_fit", "encoder_train_steps", "heads_train_steps"):
+                 "project_pose", "cosine_fit", "encoder_train_steps", "heads_train_steps", "tucker_residual"):
         getattr(torch.ops.nlml_hpe, name)       # AttributeError if the library did not register it
 
 
